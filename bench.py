@@ -9,7 +9,7 @@ Workload = BASELINE.json configs[1]: Moving-MNIST shape [B=64, H=64, T=30, W=64,
 scaling_coef=1/15, epsilon=1, 100 Sinkhorn iterations (the as-called behaviour of the
 reference: gan_utils.py:221-223).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).
@@ -31,6 +31,9 @@ Prints ONE JSON line (rank 0).
                        at the N a config names when --gpus matches it.
   cpu_baseline         the CPU oracle in the reference's own formulation on this box's host cores, bounded sample
                        (N=1, rank 0 only).
+  dumped_outputs       with --dump-outputs DIR: the loss and the five gradients of the LAST timed step, written as
+                       DIR/loss.npy, DIR/grad_<name>.npy (float32, in full).  The inputs are seeded (tests/golden/cases.py),
+                       so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -78,6 +81,22 @@ def loss_step(G, t):
                                    t["m_fake"], video=True)
     grads = torch.autograd.grad(loss, [t[k] for k in WRT])
     return loss, grads
+
+
+def dump_outputs(out_dir, loss, grads, suffix=""):
+    """What a caller of the timed step receives -- the loss and its gradients w.r.t. WRT -- as `out_dir/<name><suffix>.npy`
+    (float32, in full: 31.7 MB at the headline shape).  Returns the names written."""
+    if not isinstance(grads, dict):
+        grads = dict(zip(WRT, grads))
+    arrays = {"loss": loss}
+    arrays.update(("grad_" + k, grads[k]) for k in WRT)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "outputs of one step are %d bytes, more than the 64 MB a dump may hold" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return sorted(n + suffix for n in arrays)
 
 
 def event_stats(step, reps):
@@ -663,8 +682,13 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the configs[2..4] block")
     ap.add_argument("--no-pmc", action="store_true", help="do not re-measure roofline.traffic (two rocprofv3 counter passes "
                                                           "over a child process); report the committed figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and gradients of the last timed step to DIR/<name>.npy (N > 1: <name>.rank<r>.npy, "
+                         "each rank its shard)")
     ap.add_argument("--pmc-child", nargs="?", const="gram", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pmc_child:
         pmc_child(args.pmc_child)
         return
@@ -778,6 +802,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt)
     ms = el / args.steps * 1e3
+    # before anything replays the step again: the graphed step returns static buffers that the next replay overwrites
+    dumped = dump_outputs(args.dump_outputs, loss, _g, ".rank%d" % rank if world > 1 else "") if args.dump_outputs else None
     if world > 1 and mode.startswith("RCCL"):
         nits, nexec = gstep.nits.tolist(), gstep.nits_executed.tolist()
     elif world > 1:
@@ -802,6 +828,8 @@ def main():
                    "sinkhorn_iters": nits, "sinkhorn_iters_executed": nexec, "sinkhorn_exact_shortcut": "off",
                    "launch": mode, "loss": float(loss)},
     }
+    if dumped:
+        out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
     # ---- per-step distribution with HIP events (all ranks replay -- the sharded step has collectives; rank 0 reports)
     try:
         reps = max(100, args.steps)
