@@ -331,9 +331,47 @@ int kccot_sinkhorn_loss_fused_bwd_f32(const float* gloss, const float* dC3_unit,
 
 /* Mixed Sinkhorn divergence (gan_utils.py:225): loss = 2*cost3[0] - cost3[1] - cost3[2] for
  * cost3 = [W(real,fake), W(real,real), W(fake,fake)], and its backward gcost3 = gloss*[2,-1,-1].
- * All arguments are device pointers (one launch each, no host round trip). */
+ * All arguments are device pointers (one launch each, no host round trip).
+ * NOTE: "mixed_divergence" is the reference's name for the ONE-batch combine {2,-1,-1}; the two-minibatch
+ * estimator of COT-GAN is kccot_mixed_sinkhorn_loss_* below. */
 int kccot_mixed_divergence_fwd_f32(const float* cost3, float* loss_out, kccot_stream_t stream);
 int kccot_mixed_divergence_bwd_f32(const float* gloss, float* gcost3_out, kccot_stream_t stream);
+
+/* Mixed Sinkhorn divergence over TWO minibatches (COT-GAN's estimator; an extension -- the reference's
+ * compute_sinkhorn_loss describes it in its docstring, gan_utils.py:207-208, but evaluates the one-batch form):
+ *   loss = (W1 + W2) - W3 - W4,  W = compute_sinkhorn (gan_utils.py:124, bi_causal = False),
+ *   W1 = W(x, y;   h_fake,   m_real)    W2 = W(x', y'; h_fake_p, m_real_p)
+ *   W3 = W(x, x';  h_real_p, m_real)    W4 = W(y, y';  h_fake_p, m_fake)     (h indexes rows, M columns)
+ * R = [x; x'] and F = [y; y'] are the stacked minibatches, [2B,K] each; the six features are [B,T,J].
+ *   forward : Cmix [4,B,B] (the four cost matrices), cost4_out [4], nits_out [8] (see kccot_sinkhorn_fwd_f32),
+ *             loss_out [1].  Two modes:
+ *               dCmix_unit != NULL (u_hist = v_hist = NULL): the four solves, the combination and the reverse sweep in
+ *                 one launch (eligible when kccot_sinkhorn_fused_eligible(B, L)); dCmix_unit [4,B,B] = d loss / d Cmix
+ *                 at dLoss = 1; `ticket` = one device int32, zero on entry, left zero;
+ *               dCmix_unit == NULL: the solves, then the combination; u_hist / v_hist [4,max(L,1),B] receive the dual
+ *                 history for the backward (both NULL: forward only).  `ticket` unused.
+ *   backward: gloss = ONE device float.  After a fused forward pass dCmix_unit (Cmix / u_hist / v_hist / nits may be
+ *             NULL), otherwise Cmix, u_hist, v_hist, nits as written by the forward and dCmix_unit = NULL.
+ *             dF [2B,K] = d loss / d [y; y'] and the six feature gradients [B,T,J] -- each may be NULL.  Real videos
+ *             never receive a gradient (kernel_train.py:252,289).
+ * One FFI crossing per direction, no host synchronisation (graph-capturable).
+ * Workspace (both directions): kccot_mixed_sinkhorn_loss_workspace_bytes(B, K). */
+size_t kccot_mixed_sinkhorn_loss_workspace_bytes(int B, int64_t K);
+int kccot_mixed_sinkhorn_loss_fwd_f32(const float* R, const float* F, int B, int64_t K, float sc,
+                                      const float* h_fake, const float* m_real, const float* h_real_p,
+                                      const float* m_fake, const float* h_fake_p, const float* m_real_p,
+                                      int T, int J, float eps, int L, int Lmin, float thresh, unsigned flags,
+                                      float* Cmix, float* u_hist, float* v_hist, float* dCmix_unit,
+                                      float* cost4_out, int32_t* nits_out, float* loss_out, int32_t* ticket,
+                                      void* ws, size_t ws_bytes, kccot_stream_t stream);
+int kccot_mixed_sinkhorn_loss_bwd_f32(const float* gloss, const float* R, const float* F, int B, int64_t K,
+                                      float sc, const float* h_fake, const float* m_real, const float* h_real_p,
+                                      const float* m_fake, const float* h_fake_p, const float* m_real_p,
+                                      int T, int J, float eps, int L, const float* Cmix, const float* u_hist,
+                                      const float* v_hist, const int32_t* nits, const float* dCmix_unit,
+                                      float* dF, float* dh_fake, float* dm_real, float* dh_real_p,
+                                      float* dm_fake, float* dh_fake_p, float* dm_real_p,
+                                      void* ws, size_t ws_bytes, kccot_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Martingale penalty.  Replaces scale_invariante_martingale_regularization (gan_utils.py:179-201):

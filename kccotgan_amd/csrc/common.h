@@ -136,4 +136,10 @@ __device__ __forceinline__ float block_max(float v, float* scratch) {
     return r;
 }
 
+// sinkhorn.hip: `nprob` (3 or 4) fused solves + weighted combination + reverse sweep in one launch (sinkhorn_fused_reg);
+// loss_out = sum_p w[p] cost[p], dC_unit = d loss / d C at dLoss = 1.  Eligibility: kccot_sinkhorn_fused_eligible(n, L).
+int sinkhorn_fused_weighted(const float* C, int nprob, const float* w, int n, float eps, int L, int Lmin, float thresh,
+                            float* cost_out, int32_t* nits_out, float* loss_out, int32_t* ticket, float* dC_unit,
+                            hipStream_t st);
+
 }  // namespace kccot

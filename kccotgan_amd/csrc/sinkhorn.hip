@@ -29,6 +29,7 @@
 namespace kccot {
 
 constexpr int SK_MAXN = 128;      // register-resident kernels
+constexpr int SK_FUSED_MAXPROB = 4;  // problems of one fused solve + sweep launch (sinkhorn_fused_reg)
 constexpr int SK_MAXT = 1024;
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
@@ -526,25 +527,28 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
 //   * the reverse sweep starts the moment the final cost is known and reads U_t / V_t / V_{t-1} straight from LDS:
 //     no second launch, no reload of C (it is still in registers in both orientations), no 2*L*n-float history
 //     round trip through global memory, no prefetch / refill step inside the sweep;
-//   * d loss / d C3 is produced for dLoss = 1 with the weights {2,-1,-1} of gan_utils.py:225; the cost backward
+//   * d loss / d C is produced for dLoss = 1 with the per-problem weights of the launch: {2,-1,-1} of gan_utils.py:225
+//     on three problems (compute_sinkhorn_loss), {+1,+1,-1,-1} on four (compute_mixed_sinkhorn_loss); the cost backward
 //     multiplies by the upstream scalar when it builds its coefficients (the gradient is linear in it).
 // Arithmetic is that of sinkhorn_fwd_body / sinkhorn_bwd_reg, instruction for instruction: costs, iteration counts and
 // duals are bit-identical to the two-kernel path, dC to the two-kernel path at the same lanes-per-line.
 // Eligibility (host): n <= 128 and 2 (L+1) NS floats of history within the CU's LDS; otherwise the two kernels run.
 // ------------------------------------------------------------------------------------------
 struct SinkFusedArgs {
-    const float* C;       // [3,n,n]
+    const float* C;       // [nprob,n,n], nprob = gridDim.x (3 or 4)
     int n, L, Lmin;
     float eps, inv_eps, thresh;
-    float* cost_out;      // [3]
-    int32_t* nits_out;    // [6]
-    float* loss_out;      // [1]
+    float* cost_out;      // [nprob]
+    int32_t* nits_out;    // [2 nprob]
+    float* loss_out;      // [1] = sum_p w[p] cost[p], added left to right
     int* ticket;          // zero on entry, left zero
-    float* dC;            // [3,n,n]
+    float* dC;            // [nprob,n,n]
+    float w[SK_FUSED_MAXPROB];   // loss weights (w[p] = +-1 or 2: every product below is exact)
 };
 
-template <int EPT, int LPR, bool SHORTCUT>
+template <int EPT, int LPR, bool SHORTCUT, int NPROB>
 __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) void sinkhorn_fused_reg(SinkFusedArgs a) {
+    static_assert(NPROB == 3 || NPROB == 4, "three (compute_sinkhorn_loss) or four (mixed, two minibatches) problems");
     constexpr int NS = EPT * LPR;                              // history row stride (>= n, a multiple of 4)
     extern __shared__ __attribute__((aligned(16))) float hist[];
     __shared__ __attribute__((aligned(16))) float gu[SK_MAXN + 16 * 16];
@@ -672,16 +676,34 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const int tk = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (tk == (int)gridDim.x - 1) {
-            const float c0 = __hip_atomic_load(a.cost_out + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float c1 = __hip_atomic_load(a.cost_out + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const float c2 = __hip_atomic_load(a.cost_out + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.loss_out[0] = (2.0f * c0 - c1) - c2;
+            // sum_p w[p] c[p] left to right: (2 c0 - c1) - c2 on three problems, ((c0 + c1) - c2) - c3 on four (w[p] c[p]
+            // is exact and x + (-c) == x - c).  Three words are read back either way: on four problems the combining
+            // workgroup's own cost is the one in its register.
+            float c[NPROB];
+            if constexpr (NPROB == 3) {
+#pragma unroll
+                for (int pp = 0; pp < 3; ++pp) c[pp] = __hip_atomic_load(a.cost_out + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+                float o[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    o[k] = __hip_atomic_load(a.cost_out + ((p + 1 + k) & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+                for (int pp = 0; pp < 4; ++pp) {
+                    const int k = (pp - p - 1) & 3;                    // pp = (p + 1 + k) & 3; k = 3 is p itself
+                    c[pp] = k == 0 ? o[0] : k == 1 ? o[1] : k == 2 ? o[2] : cost;
+                }
+            }
+            float l = a.w[0] * c[0];
+#pragma unroll
+            for (int pp = 1; pp < NPROB; ++pp) l += a.w[pp] * c[pp];
+            a.loss_out[0] = l;
             __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 
     // ---------------------------------------------------------------- reverse sweep (see sinkhorn_bwd_reg)
-    const float g = (p == 0) ? 2.0f : -1.0f;                  // d(2 xy - xx - yy) at dLoss = 1
+    const float g = a.w[p];                                   // d(sum_p w[p] cost[p]) / d cost[p] at dLoss = 1
     const int lsafe = active ? line : 0;
     float drow[EPT], dcol[EPT];
     {
@@ -952,28 +974,52 @@ extern "C" int kccot_sinkhorn_fused_eligible(int n, int L) {
     return fused_hist_bytes(n, L) <= (size_t)144 * 1024;  // + ~4 KB of static LDS, inside the CU's 160 KB
 }
 
-template <int EPT, int LPR, bool SC>
-static int launch_fused(const SinkFusedArgs& a, size_t lds, hipStream_t st) {
+template <int EPT, int LPR, bool SC, int NP>
+static int launch_fused_np(const SinkFusedArgs& a, size_t lds, hipStream_t st) {
     // on every launch: the attribute belongs to the current device's copy of the function (a per-process "done" flag
     // would be wrong on a second device and racy between threads); it is a host-side table write
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_fused_reg<EPT, LPR, SC>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_fused_reg<EPT, LPR, SC, NP>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
         return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL((sinkhorn_fused_reg<EPT, LPR, SC>), dim3(3), dim3((a.n * LPR + 63) / 64 * 64), lds, st, a);
+    hipLaunchKernelGGL((sinkhorn_fused_reg<EPT, LPR, SC, NP>), dim3(NP), dim3((a.n * LPR + 63) / 64 * 64), lds, st, a);
     return launch_status("sinkhorn_fused_reg");
 }
 
+template <int EPT, int LPR, bool SC>
+static int launch_fused(const SinkFusedArgs& a, int nprob, size_t lds, hipStream_t st) {
+    return nprob == 3 ? launch_fused_np<EPT, LPR, SC, 3>(a, lds, st) : launch_fused_np<EPT, LPR, SC, 4>(a, lds, st);
+}
+
 template <bool SC>
-static int dispatch_fused(const SinkGeom& g, const SinkFusedArgs& a, size_t lds, hipStream_t st) {
+static int dispatch_fused(const SinkGeom& g, const SinkFusedArgs& a, int nprob, size_t lds, hipStream_t st) {
     if (g.lpr == 16) {
         switch (g.ept) {
-            case 1: return launch_fused<1, 16, SC>(a, lds, st);
-            case 2: return launch_fused<2, 16, SC>(a, lds, st);
-            default: return launch_fused<4, 16, SC>(a, lds, st);
+            case 1: return launch_fused<1, 16, SC>(a, nprob, lds, st);
+            case 2: return launch_fused<2, 16, SC>(a, nprob, lds, st);
+            default: return launch_fused<4, 16, SC>(a, nprob, lds, st);
         }
     }
-    if (g.lpr == 4) return launch_fused<16, 4, SC>(a, lds, st);
-    return g.ept == 8 ? launch_fused<8, 8, SC>(a, lds, st) : launch_fused<16, 8, SC>(a, lds, st);
+    if (g.lpr == 4) return launch_fused<16, 4, SC>(a, nprob, lds, st);
+    return g.ept == 8 ? launch_fused<8, 8, SC>(a, nprob, lds, st) : launch_fused<16, 8, SC>(a, nprob, lds, st);
+}
+
+// `nprob` (3 or 4) weighted solves, their combination AND the reverse sweep in ONE launch (one workgroup per problem):
+// dC_unit [nprob,n,n] = d loss / d C at dLoss = 1 for loss = sum_p w[p] cost[p].  No dual history leaves the CU.
+int kccot::sinkhorn_fused_weighted(const float* C, int nprob, const float* w, int n, float eps, int L, int Lmin,
+                                   float thresh, float* cost_out, int32_t* nits_out, float* loss_out, int32_t* ticket,
+                                   float* dC_unit, hipStream_t st) {
+    if (!C || !cost_out || !nits_out || !loss_out || !ticket || !dC_unit || !w)
+        return fail(KCCOT_EINVAL, "sinkhorn_fused: null pointer");
+    if (nprob != 3 && nprob != SK_FUSED_MAXPROB) return fail(KCCOT_EINVAL, "sinkhorn_fused: nprob=%d (3 or 4)", nprob);
+    if (!(eps > 0.f)) return fail(KCCOT_EINVAL, "sinkhorn_fused: eps=%g", (double)eps);
+    if (!kccot_sinkhorn_fused_eligible(n, L))
+        return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused: n=%d L=%d does not fit (see kccot_sinkhorn_fused_eligible)", n, L);
+    const SinkGeom g = sink_geom(n, true);
+    SinkFusedArgs a{C, n, L, Lmin, eps, (float)(1.0 / (double)eps), thresh, cost_out, nits_out, loss_out,
+                    reinterpret_cast<int*>(ticket), dC_unit, {0.f, 0.f, 0.f, 0.f}};
+    for (int p = 0; p < nprob; ++p) a.w[p] = w[p];
+    const size_t lds = fused_hist_bytes(n, L);
+    return sink_shortcut_enabled() ? dispatch_fused<true>(g, a, nprob, lds, st) : dispatch_fused<false>(g, a, nprob, lds, st);
 }
 
 // The three solves of compute_sinkhorn_loss, their combination AND the reverse sweep in ONE launch:
@@ -981,17 +1027,11 @@ static int dispatch_fused(const SinkGeom& g, const SinkFusedArgs& a, size_t lds,
 extern "C" int kccot_sinkhorn_divergence_fused_f32(const float* C3, int n, float eps, int L, int Lmin, float thresh,
                                                    float* cost3_out, int32_t* nits_out, float* loss_out, int32_t* ticket,
                                                    float* dC3_unit, kccot_stream_t stream) {
+    static const float w[3] = {2.0f, -1.0f, -1.0f};             // gan_utils.py:225
     if (!C3 || !cost3_out || !nits_out || !loss_out || !ticket || !dC3_unit)
         return fail(KCCOT_EINVAL, "sinkhorn_divergence_fused: null pointer");
-    if (!(eps > 0.f)) return fail(KCCOT_EINVAL, "sinkhorn_divergence_fused: eps=%g", (double)eps);
-    if (!kccot_sinkhorn_fused_eligible(n, L))
-        return fail(KCCOT_EUNSUPPORTED, "sinkhorn_divergence_fused: n=%d L=%d does not fit (see kccot_sinkhorn_fused_eligible)", n, L);
-    const SinkGeom g = sink_geom(n, true);
-    SinkFusedArgs a{C3, n, L, Lmin, eps, (float)(1.0 / (double)eps), thresh, cost3_out, nits_out, loss_out,
-                    reinterpret_cast<int*>(ticket), dC3_unit};
-    const size_t lds = fused_hist_bytes(n, L);
-    hipStream_t st = (hipStream_t)stream;
-    return sink_shortcut_enabled() ? dispatch_fused<true>(g, a, lds, st) : dispatch_fused<false>(g, a, lds, st);
+    return sinkhorn_fused_weighted(C3, 3, w, n, eps, L, Lmin, thresh, cost3_out, nits_out, loss_out, ticket, dC3_unit,
+                                   (hipStream_t)stream);
 }
 
 // Mixed Sinkhorn divergence in one launch each way (compute_sinkhorn_loss, gan_utils.py:221-225):

@@ -15,7 +15,7 @@ from ._lib import lib, check, ptr, stream_of, workspace
 
 __all__ = ["cost_xy", "modified_cost", "bi_causal_modified_cost", "benchmark_sinkhorn",
            "compute_sinkhorn", "compute_N", "scale_invariante_martingale_regularization",
-           "compute_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
+           "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
 
 # executed Sinkhorn iteration counts (device int32 tensors, no host sync) of the latest calls;
 # the reference keeps them in a local (gan_utils.py:148,158) although its docstring promises them
@@ -330,6 +330,82 @@ class _SinkhornLoss(torch.autograd.Function):
         return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
 
 
+class _MixedSinkhornLoss(torch.autograd.Function):
+    """compute_mixed_sinkhorn_loss as ONE library call each way (kccot_mixed_sinkhorn_loss_{fwd,bwd}_f32): the stacked cost
+    assembly R = [x; x'], F = [y; y'] + the four cost blocks, the four solves + their combination (W1 + W2) - W3 - W4, and
+    back.  Fused solve + sweep when a gradient is wanted and the shape is eligible, the dual history path otherwise."""
+
+    @staticmethod
+    def forward(ctx, R, F, h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, sc, eps, L, Lmin, tag):
+        B2, K = R.shape
+        B = B2 // 2
+        if F.shape != R.shape or B2 % 2:
+            raise ValueError("the four videos must have the same shape")
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        for t in (h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p):
+            if tuple(t.shape) != (B, T, J):
+                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
+                                      "use compute_sinkhorn for a gradient w.r.t. both operands")
+        dev = R.device
+        keep = any(ctx.needs_input_grad[1:8])
+        Lh = max(int(L), 1)
+        nc, nh = _pad64(4 * B * B), _pad64(4 * Lh * B)
+        small = _lib.empty((5,), torch.float32, dev)                                 # cost4 | loss
+        nits = _lib.empty((8,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
+        ws, wsb = workspace(lib.kccot_mixed_sinkhorn_loss_workspace_bytes(B, K), R)
+        fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
+        if fused:
+            state = _lib.empty((2 * nc,), torch.float32, dev)                        # Cmix | dCmix at dLoss = 1
+            uh = vh = None
+            dCu = state[nc:]
+        else:
+            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # Cmix | u_hist | v_hist
+            uh, vh = (state[nc:nc + nh], state[nc + nh:]) if keep else (None, None)
+            dCu = None
+        Cmix = state[:nc]
+        check(lib.kccot_mixed_sinkhorn_loss_fwd_f32(ptr(R), ptr(F), B, K, sc, ptr(h_fake), ptr(m_real), ptr(h_real_p),
+                                                    ptr(m_fake), ptr(h_fake_p), ptr(m_real_p), T, J, float(eps), int(L),
+                                                    int(Lmin), _THRESH, cost_flags, ptr(Cmix), ptr(uh), ptr(vh), ptr(dCu),
+                                                    ptr(small), ptr(nits), ptr(small[4:]), ptr(_ticket(dev)), ws, wsb,
+                                                    stream_of(R)), "mixed_sinkhorn_loss_fwd")
+        last_info[tag], last_info[tag + "_executed"] = nits[:4], nits[4:]
+        last_info[tag + "_costs"] = small[:4]
+        last_info[tag + "_Cmix"] = Cmix[:4 * B * B].view(4, B, B)
+        last_info[tag + "_fused_sweep"] = fused
+        if keep:
+            ctx.save_for_backward(R, F, h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, state, nits)
+        ctx.cfg = (float(sc), float(eps), Lh, fused)
+        return small[4:].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        R, F, h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, state, nits = ctx.saved_tensors
+        sc, eps, Lh, fused = ctx.cfg
+        B2, K = R.shape
+        B = B2 // 2
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        nc, nh = _pad64(4 * B * B), _pad64(4 * Lh * B)
+        need = ctx.needs_input_grad
+        g = g.reshape(1).contiguous().float()
+        dF = _lib.empty_like(F) if need[1] else None
+        feats = _lib.empty((6, B, T, J), torch.float32, R.device) if any(need[2:8]) else None
+        df = [(feats[i] if need[2 + i] else None) for i in range(6)]
+        ws, wsb = workspace(lib.kccot_mixed_sinkhorn_loss_workspace_bytes(B, K), R)
+        if fused:
+            Cmix = uh = vh = nt = None
+            dCu = state[nc:]
+        else:
+            Cmix, uh, vh, nt, dCu = state[:nc], state[nc:nc + nh], state[nc + nh:], nits, None
+        check(lib.kccot_mixed_sinkhorn_loss_bwd_f32(ptr(g), ptr(R), ptr(F), B, K, sc, ptr(h_fake), ptr(m_real),
+                                                    ptr(h_real_p), ptr(m_fake), ptr(h_fake_p), ptr(m_real_p), T, J, eps,
+                                                    Lh, ptr(Cmix), ptr(uh), ptr(vh), ptr(nt), ptr(dCu), ptr(dF),
+                                                    *[ptr(d) for d in df], ws, wsb, stream_of(R)),
+              "mixed_sinkhorn_loss_bwd")
+        return (None, dF, *df, None, None, None, None, None)
+
+
 class _MixedDivergence(torch.autograd.Function):
     """loss = 2*W_xy - W_xx - W_yy (gan_utils.py:225) as one launch each way."""
 
@@ -438,6 +514,38 @@ def compute_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l
     # one library call each way; equivalent to _Cost3 (C3 = [xy, xx, yy]) followed by _SinkhornDivergence
     return _SinkhornLoss.apply(real, fake, _feat(h_fake), _feat(h_real), _feat(m_real), _feat(m_fake),
                                float(scaling_coef), eps, L, _LMIN, "compute_sinkhorn_loss")
+
+
+def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef, sinkhorn_eps, sinkhorn_l,
+                                h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, video=True, *, honor_eps_l=False):
+    """Mixed Sinkhorn divergence of COT-GAN over two minibatches of real (x, x') and generated (y, y') data:
+
+        loss = (W(x, y) + W(x', y')) - W(x, x') - W(y, y')
+
+    with W = compute_sinkhorn (gan_utils.py:124, bi_causal=False) and the (h, M) pairs
+    W(x,y; h_fake, m_real), W(x',y'; h_fake_p, m_real_p), W(x,x'; h_real_p, m_real), W(y,y'; h_fake_p, m_fake)
+    (h indexes rows, M columns).  EXTENSION: the reference describes this estimator in the docstring of
+    compute_sinkhorn_loss (gan_utils.py:207-208) and names it in kernel_train.py's ``--mixed_sinkhorn`` flag, but
+    evaluates only the one-batch form.  With x' = x, y' = y, h_fake_p = h_fake, m_real_p = m_real, h_real_p = h_real
+    it equals compute_sinkhorn_loss(f_real, f_fake, ..., h_fake, m_real, h_real, m_fake) term by term.
+
+    ``sinkhorn_eps`` / ``sinkhorn_l`` are ignored by default (epsilon = 1, L = 100) exactly as in compute_sinkhorn_loss;
+    ``honor_eps_l=True`` applies them.  Differentiable w.r.t. the fake videos and all six features; a real video that
+    requires a gradient raises NotImplementedError.  Records last_info["compute_mixed_sinkhorn_loss"] (the four
+    reference-equivalent iteration counts), ``..._executed``, ``..._costs`` [4] and ``..._Cmix`` [4,B,B].
+    """
+    del video  # both layouts flatten to [B, K]
+    eps, L = (float(sinkhorn_eps), int(sinkhorn_l)) if honor_eps_l else (1.0, 100)
+    vids = [_flat2(v) for v in (f_real, f_fake, f_real_p, f_fake_p)]
+    if any(v.shape != vids[0].shape for v in vids[1:]):
+        raise ValueError("the four videos must have the same shape: %s" % ([tuple(v.shape) for v in vids],))
+    feats = [_feat(t) for t in (h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p)]
+    if any(t.shape != feats[0].shape for t in feats[1:]) or feats[0].shape[0] != vids[0].shape[0]:
+        raise ValueError("the six features must all be [B,T,J] with the videos' B; got %s" % ([tuple(t.shape) for t in feats],))
+    # stacked minibatches (2 B K floats copied); cat's backward hands d[y; y'] back to y and y' as two views
+    R = torch.cat([vids[0], vids[2]], 0)
+    F = torch.cat([vids[1], vids[3]], 0)
+    return _MixedSinkhornLoss.apply(R, F, *feats, float(scaling_coef), eps, L, _LMIN, "compute_mixed_sinkhorn_loss")
 
 
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):

@@ -87,8 +87,14 @@ class KCCOTTrainer:
     def __init__(self, batch_size, total_time_steps=15, int_time_steps=5, x_height=64, x_width=64, channels=3,
                  g_state_size=8, d_state_size=8, g_filter_size=8, d_filter_size=8, z_channels=128, bn=True,
                  lr=5e-4, warmup=10000, sinkhorn_eps=0.8, sinkhorn_l=100, scaling_coef=15.0, reg_penalty=1.0,
-                 kernel="none", device="cuda", seed=1, group=None):
+                 kernel="none", device="cuda", seed=1, group=None, mixed_sinkhorn=False):
         # defaults = kernel_train.py:363-409
+        # mixed_sinkhorn=True: the loss is COT-GAN's mixed Sinkhorn divergence over two minibatches
+        # (gan_utils.compute_mixed_sinkhorn_loss) -- what the reference's --mixed_sinkhorn flag (:393) names but never runs
+        data_parallel = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        if mixed_sinkhorn and data_parallel:
+            raise NotImplementedError("mixed_sinkhorn=True has no batch-sharded (data-parallel) form")
+        self.mixed_sinkhorn = bool(mixed_sinkhorn)
         torch.manual_seed(seed)
         self.batch_size, self.device, self.group = batch_size, torch.device(device), group
         self.int_time_steps = int_time_steps
@@ -99,7 +105,6 @@ class KCCOTTrainer:
         self.sinkhorn_eps, self.sinkhorn_l, self.reg_penalty = sinkhorn_eps, sinkhorn_l, reg_penalty
         self.kernel_choice = kernel
         self.convolution_mode = gan.convolution_mode()      # 'miopen' or 'native:...' (the slow fallback; see gan.py)
-        data_parallel = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         # :216; data-parallel: the division is by the maximum of the GLOBAL batch, as in the single-process run
         self.gaussian_kernel = KernelSmoothing(temporal_kernel_size=6, spatial_kernel_size=6, group=group, sharded=data_parallel)
         mk = dict(z_width=4, z_height=4, bn=bn, nchannel=channels)
@@ -160,6 +165,40 @@ class KCCOTTrainer:
                                                    self.sinkhorn_l, h_fake, m_real, h_real, m_fake, video=True)  # :247
         return loss, m_real
 
+    def _smooth(self, v, sigma):
+        if self.kernel_choice == "1d":                                           # :229-239
+            return self.gaussian_kernel.temporal_convolution(v, sigma)
+        if self.kernel_choice == "2d":
+            return self.gaussian_kernel.spatial_convolution(v, sigma)
+        if self.kernel_choice == "3d":
+            return self.gaussian_kernel.gaussian_convolution3D(v, sigma)
+        return v
+
+    def _forward_mixed(self, real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad=True):
+        """The two-minibatch forward of COT-GAN: two independent z, the generator run on each minibatch separately (its
+        BatchNorm statistics stay per B-sample minibatch, as in the one-batch step), each of the four videos smoothed by
+        its own call, D_h on y, y', x' and D_m on x, x', y; loss = compute_mixed_sinkhorn_loss."""
+        vids = []
+        for r_in, r_pred in ((real_in, real_pred), (real_in_p, real_pred_p)):
+            hidden_z = torch.randn(self.z_shape, device=self.device)
+            with torch.set_grad_enabled(generator_grad):
+                fake_pred = self.decoder(self.context_encoder(torch.cat((r_in, r_pred), dim=2)), hidden_z)
+            vids.append((torch.cat((r_in, r_pred), dim=2), torch.cat((r_in, fake_pred), dim=2)))
+        (real, fake), (real_p, fake_p) = ((self._smooth(r, sigma), self._smooth(f, sigma)) for r, f in vids)
+        h_fake, h_fake_p, h_real_p = (self.discriminator_h(v) for v in (fake, fake_p, real_p))
+        m_real, m_real_p, m_fake = (self.discriminator_m(v) for v in (real, real_p, fake))
+        loss = gan_utils.compute_mixed_sinkhorn_loss(real.detach(), fake, real_p.detach(), fake_p, self.scaling_coef,
+                                                     self.sinkhorn_eps, self.sinkhorn_l, h_fake, m_real, h_real_p, m_fake,
+                                                     h_fake_p, m_real_p, video=True)
+        return loss, m_real
+
+    def _loss_and_m(self, real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad=True):
+        if not self.mixed_sinkhorn:
+            return self._forward(real_in, real_pred, sigma, generator_grad)
+        if real_in_p is None or real_pred_p is None:
+            raise ValueError("mixed_sinkhorn=True needs the second real minibatch (real_in_p, real_pred_p)")
+        return self._forward_mixed(real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad)
+
     def _world(self):
         return dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
 
@@ -183,16 +222,16 @@ class KCCOTTrainer:
         optimiser.apply_gradients(zip(grads[n0:], nets[1]))
 
     # ------------------------------------------------------------------ kernel_train.py:219-256
-    def disc_training_step(self, real_in, real_pred, sigma):
+    def disc_training_step(self, real_in, real_pred, sigma, real_in_p=None, real_pred_p=None):
         with gan.conv_guard():                   # forward AND backward off MIOpen when native convolutions are selected
-            return self._disc_training_step(real_in, real_pred, sigma)
+            return self._disc_training_step(real_in, real_pred, sigma, real_in_p, real_pred_p)
 
-    def gen_training_step(self, real_in, real_pred, sigma):
+    def gen_training_step(self, real_in, real_pred, sigma, real_in_p=None, real_pred_p=None):
         with gan.conv_guard():
-            return self._gen_training_step(real_in, real_pred, sigma)
+            return self._gen_training_step(real_in, real_pred, sigma, real_in_p, real_pred_p)
 
-    def _disc_training_step(self, real_in, real_pred, sigma):
-        loss, m_real = self._forward(real_in, real_pred, sigma, generator_grad=False)
+    def _disc_training_step(self, real_in, real_pred, sigma, real_in_p=None, real_pred_p=None):
+        loss, m_real = self._loss_and_m(real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad=False)
         if self._world() > 1:               # pM couples the whole batch (std and mean over b): use the global M
             from . import dist as kd
             m_real = kd.all_gather_local_grad(m_real, self.group)
@@ -203,8 +242,8 @@ class KCCOTTrainer:
         return pm1.detach()                                                      # :256
 
     # ------------------------------------------------------------------ kernel_train.py:259-292
-    def _gen_training_step(self, real_in, real_pred, sigma):
-        loss, _ = self._forward(real_in, real_pred, sigma)
+    def _gen_training_step(self, real_in, real_pred, sigma, real_in_p=None, real_pred_p=None):
+        loss, _ = self._loss_and_m(real_in, real_pred, real_in_p, real_pred_p, sigma)
         grads = torch.autograd.grad(loss, self.g_params, allow_unused=True)      # :289
         self._apply(self.gen_optimiser, self.g_nets, grads)                      # :290-291
         return loss.detach()                                                     # :292
@@ -240,16 +279,26 @@ class KCCOTTrainer:
         ``log(name, value, step)`` receives 'pM' and 'Sinkhorn Loss' every iteration (:318-321) and 'Training data'
         (the sample image) at iteration 1 and every ``save_freq`` iterations when ``test_x`` (one [B,H,T,W,C] batch)
         is given (:331,338-355).  A non-finite generator loss ends the run (:323-329).  Returns a dict with the
-        iteration count, the scalar history and ``exploded``."""
+        iteration count, the scalar history and ``exploded``.  With ``mixed_sinkhorn`` every iteration consumes two
+        batches (x, x'); an incomplete last pair is dropped."""
         history = {"pM": [], "Sinkhorn Loss": []}
         it_counts, exploded = 0, False
+        pending = None
         for x in batched_x:
             if x.shape[0] != self.batch_size:                                    # :298-299
                 continue
+            if self.mixed_sinkhorn and pending is None:
+                pending = x
+                continue
             it_counts += 1
-            real_data = x.to(self.device, torch.float32)
             sig = (self.gaussian_kernel.annealing_sigma(init_sigma, it_counts) if decaying_sigma else init_sigma)  # :308-311
-            pm, loss = self.train_iteration(real_data, sig)
+            if self.mixed_sinkhorn:
+                real_data, real_data_p = (v.to(self.device, torch.float32) for v in (pending, x))
+                pending = None
+                pm, loss = self.train_iteration(real_data, sig, real_data_p)
+            else:
+                real_data = x.to(self.device, torch.float32)
+                pm, loss = self.train_iteration(real_data, sig)
             pm, loss = float(pm), float(loss)
             history["pM"].append(pm)
             history["Sinkhorn Loss"].append(loss)
@@ -257,7 +306,9 @@ class KCCOTTrainer:
                 log("pM", pm, it_counts)
                 log("Sinkhorn Loss", loss, it_counts)
             if not math.isfinite(loss):                                          # :323
-                gan_utils.raise_if_solver_aborted()        # an aborted multi-CU solve is an error, not an exploded loss
+                # an aborted multi-CU solve is an error, not an exploded loss
+                gan_utils.raise_if_solver_aborted(("compute_mixed_sinkhorn_loss",) if self.mixed_sinkhorn
+                                                  else ("compute_sinkhorn_loss",))
                 exploded = True
                 break
             if test_x is not None and (it_counts % save_freq == 0 or it_counts == 1) and log is not None:   # :331
@@ -266,10 +317,21 @@ class KCCOTTrainer:
                 break
         return {"iterations": it_counts, "history": history, "exploded": exploded}
 
-    def train_iteration(self, real_data, sigma=5.0):
-        """One pass of the loop body kernel_train.py:301-314 on a [B,H,T,W,C] batch."""
+    def train_iteration(self, real_data, sigma=5.0, real_data_p=None):
+        """One pass of the loop body kernel_train.py:301-314 on a [B,H,T,W,C] batch (with ``mixed_sinkhorn``: and the
+        second, independent [B,H,T,W,C] batch ``real_data_p``)."""
         real_inputs = real_data[:, :, :self.int_time_steps]
         real_preds = real_data[:, :, self.int_time_steps:]
-        pm = self.disc_training_step(real_inputs, real_preds, sigma)
-        loss = self.gen_training_step(real_inputs, real_preds, sigma)
+        if not self.mixed_sinkhorn:
+            pm = self.disc_training_step(real_inputs, real_preds, sigma)
+            loss = self.gen_training_step(real_inputs, real_preds, sigma)
+            return pm, loss
+        if real_data_p is None:
+            raise ValueError("mixed_sinkhorn=True: train_iteration needs the second batch real_data_p")
+        if real_data_p.shape != real_data.shape:
+            raise ValueError("real_data_p must have the shape of real_data: %s vs %s"
+                             % (tuple(real_data_p.shape), tuple(real_data.shape)))
+        p_inputs, p_preds = real_data_p[:, :, :self.int_time_steps], real_data_p[:, :, self.int_time_steps:]
+        pm = self.disc_training_step(real_inputs, real_preds, sigma, p_inputs, p_preds)
+        loss = self.gen_training_step(real_inputs, real_preds, sigma, p_inputs, p_preds)
         return pm, loss
