@@ -373,6 +373,47 @@ int kccot_mixed_sinkhorn_loss_bwd_f32(const float* gloss, const float* R, const 
                                       float* dm_fake, float* dh_fake_p, float* dm_real_p,
                                       void* ws, size_t ws_bytes, kccot_stream_t stream);
 
+/* Bi-causal Sinkhorn loss (an extension: the reference implements bi_causal_modified_cost, gan_utils.py:46-72, and
+ * compute_sinkhorn(..., bi_causal=True), gan_utils.py:124-136, and names the mode in its --bi_causal flag,
+ * kernel_train.py:396, but compute_sinkhorn_loss never passes bi_causal):
+ *   loss = 2 W(x,y) - W(x,x) - W(y,y),   W = compute_sinkhorn(..., bi_causal = True), x = real, y = fake
+ *   C_xy = sc |x_i - y_j|^2 + causal(h_fake, m_real) + causal(h_real, m_fake)
+ *   C_xx = sc |x_i - x_j|^2 + 2 causal(h_real, m_real)
+ *   C_yy = sc |y_i - y_j|^2 + 2 causal(h_fake, m_fake)
+ * with causal(h, M)[i,j] = sc sum_{t<T-1,q} h[i,t,q] (M[j,t+1,q] - M[j,t,q]) (h indexes rows, M columns; the xx / yy
+ * term is added twice in fp32, as the reference does).  Same inputs and argument order as kccot_sinkhorn_loss_*.
+ * Feature gradients, g = d loss / d C3 [xy, xx, yy]:
+ *   dh_fake = g_xy . dm_real + 2 g_yy . dm_fake        dm_real = g_xy with h_fake + 2 g_xx with h_real
+ *   dh_real = g_xy . dm_fake + 2 g_xx . dm_real        dm_fake = g_xy with h_real + 2 g_yy with h_fake
+ * and dfake equal to the one-batch loss's (the squared-distance part is unchanged); real never gets a gradient.
+ *   forward : C3 [3,B,B] (the three bi-causal cost matrices), cost3_out [3], nits_out [6], loss_out [1].  Two modes:
+ *               dC3_unit != NULL (u_hist = v_hist = NULL): the three solves, the combination and the reverse sweep in one
+ *                 launch (eligible when kccot_sinkhorn_fused_eligible(B, L)); dC3_unit [3,B,B] = d loss / d C3 at
+ *                 dLoss = 1;
+ *               dC3_unit == NULL: the solves and the combination; u_hist / v_hist [3,max(L,1),B] receive the dual
+ *                 history for the backward (both NULL: forward only).
+ *             `ticket` = one device int32, zero on entry, left zero.  The cost-ladder options apply as for
+ *             kccot_pairwise_cost3_f32; the Gram-sum split flags are refused.
+ *   backward: gloss = ONE device float.  After a fused forward dC3_unit (C3 / u_hist / v_hist / nits may be NULL),
+ *             otherwise C3, u_hist, v_hist, nits as written by the forward and dC3_unit = NULL.  dfake [B,K] and the
+ *             four feature gradients [B,T,J] may each be NULL.
+ * One FFI crossing per direction, no host synchronisation (graph-capturable).
+ * Workspace (both directions): kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K). */
+size_t kccot_bicausal_sinkhorn_loss_workspace_bytes(int B, int64_t K);
+int kccot_bicausal_sinkhorn_loss_fwd_f32(const float* real, const float* fake, int B, int64_t K, float sc,
+                                         const float* h_fake, const float* h_real, const float* m_real,
+                                         const float* m_fake, int T, int J, float eps, int L, int Lmin, float thresh,
+                                         unsigned flags, float* C3, float* u_hist, float* v_hist, float* dC3_unit,
+                                         float* cost3_out, int32_t* nits_out, float* loss_out, int32_t* ticket,
+                                         void* ws, size_t ws_bytes, kccot_stream_t stream);
+int kccot_bicausal_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const float* fake, int B, int64_t K,
+                                         float sc, const float* h_fake, const float* h_real, const float* m_real,
+                                         const float* m_fake, int T, int J, float eps, int L, const float* C3,
+                                         const float* u_hist, const float* v_hist, const int32_t* nits,
+                                         const float* dC3_unit, float* dfake, float* dh_fake, float* dh_real,
+                                         float* dm_real, float* dm_fake, void* ws, size_t ws_bytes,
+                                         kccot_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Martingale penalty.  Replaces scale_invariante_martingale_regularization (gan_utils.py:179-201):
  *   pM = lam * sc * sum_{t<T-1,q} | (1/B) sum_b (M[b,t+1,q]-M[b,t,q]) / (std_{b,t}(M[:,:,q]) + 1e-6) |

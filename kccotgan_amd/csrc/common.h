@@ -142,4 +142,12 @@ int sinkhorn_fused_weighted(const float* C, int nprob, const float* w, int n, fl
                             float* cost_out, int32_t* nits_out, float* loss_out, int32_t* ticket, float* dC_unit,
                             hipStream_t st);
 
+// cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) with the feature-gradient jobs of the
+// bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake, dh_real = gxy.dm_fake + 2 gxx.dm_real,
+// dm_real = gxy with h_fake + 2 gxx with h_real, dm_fake = gxy with h_real + 2 gyy with h_fake; dfake as the one-batch loss.
+int cost3_bwd_bicausal(const float* g3, const float* gscale, const float* real, const float* fake, int B, int64_t K, float sc,
+                       const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
+                       float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake, void* ws,
+                       size_t ws_bytes, hipStream_t st);
+
 }  // namespace kccot

@@ -136,7 +136,9 @@ __global__ __launch_bounds__(256) void apply_coeffs(const float* __restrict__ Wt
 //   CG_H (dh):  a = i, b = j, G = g[i,j],  X(j,k) = M[j,k+J] - M[j,k]          (0 for k >= (T-1)J)
 //   CG_M (dM):  a = j, b = i, G = g[i,j],  X(i,k) = h[i,k-J][k>=J] - h[i,k][k<(T-1)J]
 // with up to two (g, source) terms summed (h_fake / m_real appear in two cost matrices of the
-// loss).  One launch handles up to four outputs (blockIdx.z); block = 16 (a) x 16 (k) outputs.
+// loss), term `t` weighted by w[t] (the bi-causal loss doubles its xx / yy terms; 1 everywhere else:
+// w * g is exact for w = 1 and 2, so the one-batch loss keeps its bits).  One launch handles up to
+// four outputs (blockIdx.z); block = 16 (a) x 16 (k) outputs.
 enum { CG_H = 0, CG_M = 1 };
 struct CausalGradJob {
     float* out;          // [Ba, T*J]: rows a_begin .. a_begin+Ba-1 of the full problem
@@ -144,6 +146,7 @@ struct CausalGradJob {
     int pitch;           // row pitch (= full column count Bj) of the g matrices
     const float* g[2];   // [Bi, Bj] row-major (Bi = rows of C); null = term absent
     const float* src[2]; // CG_H: M [Bb,T,J];  CG_M: h [Bb,T,J]
+    float w[2] = {1.f, 1.f};
 };
 struct CausalGradBatch { CausalGradJob job[4]; int njobs; };
 
@@ -162,6 +165,7 @@ __device__ __forceinline__ void causal_grads_body(const CausalGradBatch& cb, int
     for (int term = 0; term < 2; ++term) {
         const float* g = jb.g[term];
         const float* src = jb.src[term];
+        const float wg = jb.w[term];
         if (!g) continue;
         for (int b0 = 0; b0 < jb.Bb; b0 += 64) {
             // addresses clamped into range, zeros selected afterwards: the eight to twelve loads of a
@@ -186,7 +190,7 @@ __device__ __forceinline__ void causal_grads_body(const CausalGradBatch& cb, int
             for (int m = 0; m < 4; ++m) {
                 const int e = t + 256 * m;
                 const int ar = (jb.mode == CG_H) ? (e >> 6) : (e & 15), bg = (jb.mode == CG_H) ? (e & 63) : (e >> 4);
-                sg[ar * 65 + bg] = (a0 + ar < jb.Ba && b0 + bg < jb.Bb) ? gv[m] : 0.f;
+                sg[ar * 65 + bg] = (a0 + ar < jb.Ba && b0 + bg < jb.Bb) ? gv[m] * wg : 0.f;
                 const int bb = e >> 4, kk = e & 15, k = k0 + kk;
                 float x = 0.f;
                 if (b0 + bb < jb.Bb && k < TJ) {
@@ -493,7 +497,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3(const unsigned short* __r
 // terms, unconditionally, at clamped addresses: straight-line code, so the compiler's wait in front of `finish` counts only
 // these loads and leaves younger ones in flight), `finish` does the rest.  Bb <= 64 (one b chunk).
 struct WaveTask {
-    float gv[2][4], xa[2][16], xb[2][16];
+    float gv[2][4], xa[2][16], xb[2][16], wg[2];
     int k, a0, ta, tk, mode, Ba, Bb;
     bool use_a, use_b, term[2];
     float* out;
@@ -518,6 +522,7 @@ __device__ __forceinline__ void causal_wave_load(WaveTask& w, const CausalGradBa
 #pragma unroll
     for (int term = 0; term < 2; ++term) {
         w.term[term] = jb.g[term] != nullptr;
+        w.wg[term] = jb.w[term];
         const float* g = jb.g[term] ? jb.g[term] : jb.g[0];           // an absent term: valid addresses, values unused
         const float* src = jb.src[term] ? jb.src[term] : jb.src[0];
 #pragma unroll
@@ -549,7 +554,7 @@ __device__ __forceinline__ void causal_wave_finish(const WaveTask& w, int TJ, fl
         for (int m = 0; m < 4; ++m) {
             const int e = lane + 64 * m;
             const int ar = H ? m : (e & 3), bg = H ? lane : (e >> 2);
-            sg[ar * 65 + bg] = (w.a0 + ar < w.Ba && bg < w.Bb) ? w.gv[term][m] : 0.f;
+            sg[ar * 65 + bg] = (w.a0 + ar < w.Ba && bg < w.Bb) ? w.gv[term][m] * w.wg[term] : 0.f;
         }
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
@@ -1387,7 +1392,7 @@ static int cost3_bwd_rows_impl(const float* g3, const float* gscale, const float
                                const float* m_real, const float* m_fake, int T, int J,
                                int row_begin, int row_count,
                                float* dfake, float* dh_fake, float* dh_real, float* dm_real,
-                               float* dm_fake, void* ws, size_t ws_bytes, kccot_stream_t stream) {
+                               float* dm_fake, void* ws, size_t ws_bytes, kccot_stream_t stream, bool bicausal = false) {
     if (!g3 || !real || !fake) return fail(KCCOT_EINVAL, "pairwise_cost3_bwd: null pointer");
     if (row_begin < 0 || row_count <= 0 || row_begin + row_count > B)
         return fail(KCCOT_EINVAL, "pairwise_cost3_bwd: bad row range [%d, %d) of %d", row_begin, row_begin + row_count, B);
@@ -1402,10 +1407,18 @@ static int cost3_bwd_rows_impl(const float* g3, const float* gscale, const float
     // gan_utils.py:221-223: h_fake rows of xy (cols m_real) and of yy (cols m_fake); h_real rows of xx
     // (cols m_real); m_real cols of xy (rows h_fake) and of xx (rows h_real); m_fake cols of yy (rows h_fake)
     CausalGradBatch cg{};
-    if (dh_fake) cg.job[cg.njobs++] = CausalGradJob{dh_fake, CG_H, row_count, B, row_begin, B, {gxy, gyy}, {m_real, m_fake}};
-    if (dh_real) cg.job[cg.njobs++] = CausalGradJob{dh_real, CG_H, row_count, B, row_begin, B, {gxx, nullptr}, {m_real, nullptr}};
-    if (dm_real) cg.job[cg.njobs++] = CausalGradJob{dm_real, CG_M, row_count, B, row_begin, B, {gxy, gxx}, {h_fake, h_real}};
-    if (dm_fake) cg.job[cg.njobs++] = CausalGradJob{dm_fake, CG_M, row_count, B, row_begin, B, {gyy, nullptr}, {h_fake, nullptr}};
+    if (!bicausal) {
+        if (dh_fake) cg.job[cg.njobs++] = CausalGradJob{dh_fake, CG_H, row_count, B, row_begin, B, {gxy, gyy}, {m_real, m_fake}};
+        if (dh_real) cg.job[cg.njobs++] = CausalGradJob{dh_real, CG_H, row_count, B, row_begin, B, {gxx, nullptr}, {m_real, nullptr}};
+        if (dm_real) cg.job[cg.njobs++] = CausalGradJob{dm_real, CG_M, row_count, B, row_begin, B, {gxy, gxx}, {h_fake, h_real}};
+        if (dm_fake) cg.job[cg.njobs++] = CausalGradJob{dm_fake, CG_M, row_count, B, row_begin, B, {gyy, nullptr}, {h_fake, nullptr}};
+    } else {
+        // bi-causal loss (bicausal.hip): C_xy gains (h_real rows, m_fake cols), C_xx and C_yy carry their term twice
+        if (dh_fake) cg.job[cg.njobs++] = CausalGradJob{dh_fake, CG_H, row_count, B, row_begin, B, {gxy, gyy}, {m_real, m_fake}, {1.f, 2.f}};
+        if (dh_real) cg.job[cg.njobs++] = CausalGradJob{dh_real, CG_H, row_count, B, row_begin, B, {gxy, gxx}, {m_fake, m_real}, {1.f, 2.f}};
+        if (dm_real) cg.job[cg.njobs++] = CausalGradJob{dm_real, CG_M, row_count, B, row_begin, B, {gxy, gxx}, {h_fake, h_real}, {1.f, 2.f}};
+        if (dm_fake) cg.job[cg.njobs++] = CausalGradJob{dm_fake, CG_M, row_count, B, row_begin, B, {gxy, gyy}, {h_real, h_fake}, {1.f, 2.f}};
+    }
     if (!dfake) return launch_causal_grads(cg, T, J, sc, st, gscale);
     const size_t need = kccot_pairwise_cost3_bwd_workspace_bytes(B, K);
     if (!ws || ws_bytes < need)
@@ -1448,6 +1461,16 @@ static int cost3_bwd_rows_impl(const float* g3, const float* gscale, const float
     return launch_apply(Wt + row_begin, B, real, B, fake, B, row_count, K, dfake, st, W3 + (int64_t)row_begin * 2 * B, B, 2 * B,
                         W3, (B % 32 == 0 && row_begin % 32 == 0) ? Wt3 : nullptr);
 }
+
+namespace kccot {
+int cost3_bwd_bicausal(const float* g3, const float* gscale, const float* real, const float* fake, int B, int64_t K, float sc,
+                       const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
+                       float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake, void* ws,
+                       size_t ws_bytes, hipStream_t st) {
+    return cost3_bwd_rows_impl(g3, gscale, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, 0, B, dfake, dh_fake,
+                               dh_real, dm_real, dm_fake, ws, ws_bytes, (kccot_stream_t)st, true);
+}
+}  // namespace kccot
 
 extern "C" int kccot_pairwise_cost3_bwd_rows_f32(const float* g3, const float* real, const float* fake, int B,
                                                  int64_t K, float sc, const float* h_fake, const float* h_real,

@@ -15,7 +15,8 @@ from ._lib import lib, check, ptr, stream_of, workspace
 
 __all__ = ["cost_xy", "modified_cost", "bi_causal_modified_cost", "benchmark_sinkhorn",
            "compute_sinkhorn", "compute_N", "scale_invariante_martingale_regularization",
-           "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
+           "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "compute_bicausal_sinkhorn_loss", "last_info",
+           "raise_if_solver_aborted"]
 
 # executed Sinkhorn iteration counts (device int32 tensors, no host sync) of the latest calls;
 # the reference keeps them in a local (gan_utils.py:148,158) although its docstring promises them
@@ -330,6 +331,79 @@ class _SinkhornLoss(torch.autograd.Function):
         return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
 
 
+class _BicausalSinkhornLoss(torch.autograd.Function):
+    """compute_bicausal_sinkhorn_loss as ONE library call each way (kccot_bicausal_sinkhorn_loss_{fwd,bwd}_f32): the three
+    bi-causal cost matrices, the three solves + 2 W_xy - W_xx - W_yy, and back.  Fused solve + sweep when a gradient is
+    wanted and the shape is eligible, the dual history path otherwise."""
+
+    @staticmethod
+    def forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc, eps, L, Lmin, tag):
+        B, K = real.shape
+        if fake.shape != real.shape:
+            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        for t in (h_fake, h_real, m_real, m_fake):
+            if tuple(t.shape) != (B, T, J):
+                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
+                                      "use compute_sinkhorn for a gradient w.r.t. both operands")
+        dev = real.device
+        keep = any(ctx.needs_input_grad[1:6])
+        Lh = max(int(L), 1)
+        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
+        small = _lib.empty((4,), torch.float32, dev)                                 # cost3 | loss
+        nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
+        ws, wsb = workspace(lib.kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K), real)
+        fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
+        if fused:
+            state = _lib.empty((2 * nc,), torch.float32, dev)                        # C3 | dC3 at dLoss = 1
+            uh = vh = None
+            dCu = state[nc:]
+        else:
+            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # C3 | u_hist | v_hist
+            uh, vh = (state[nc:nc + nh], state[nc + nh:]) if keep else (None, None)
+            dCu = None
+        C3 = state[:nc]
+        check(lib.kccot_bicausal_sinkhorn_loss_fwd_f32(ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real), ptr(m_real),
+                                                       ptr(m_fake), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
+                                                       ptr(C3), ptr(uh), ptr(vh), ptr(dCu), ptr(small), ptr(nits),
+                                                       ptr(small[3:]), ptr(_ticket(dev)), ws, wsb, stream_of(real)),
+              "bicausal_sinkhorn_loss_fwd")
+        last_info[tag], last_info[tag + "_executed"] = nits[:3], nits[3:]
+        last_info[tag + "_costs"] = small[:3]
+        last_info[tag + "_C3"] = C3[:3 * B * B].view(3, B, B)
+        last_info[tag + "_fused_sweep"] = fused
+        if keep:
+            ctx.save_for_backward(real, fake, h_fake, h_real, m_real, m_fake, state, nits)
+        ctx.cfg = (float(sc), float(eps), Lh, fused)
+        return small[3:].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        real, fake, h_fake, h_real, m_real, m_fake, state, nits = ctx.saved_tensors
+        sc, eps, Lh, fused = ctx.cfg
+        B, K = real.shape
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
+        need = ctx.needs_input_grad
+        g = g.reshape(1).contiguous().float()
+        dfake = _lib.empty_like(fake) if need[1] else None
+        feats = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[2:6]) else None
+        dhf, dhr, dmr, dmf = ((feats[i] if need[2 + i] else None) for i in range(4))
+        ws, wsb = workspace(lib.kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K), real)
+        if fused:
+            C3 = uh = vh = nt = None
+            dCu = state[nc:]
+        else:
+            C3, uh, vh, nt, dCu = state[:nc], state[nc:nc + nh], state[nc + nh:], nits, None
+        check(lib.kccot_bicausal_sinkhorn_loss_bwd_f32(ptr(g), ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real),
+                                                       ptr(m_real), ptr(m_fake), T, J, eps, Lh, ptr(C3), ptr(uh), ptr(vh),
+                                                       ptr(nt), ptr(dCu), ptr(dfake), ptr(dhf), ptr(dhr), ptr(dmr), ptr(dmf),
+                                                       ws, wsb, stream_of(real)), "bicausal_sinkhorn_loss_bwd")
+        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
+
+
 class _MixedSinkhornLoss(torch.autograd.Function):
     """compute_mixed_sinkhorn_loss as ONE library call each way (kccot_mixed_sinkhorn_loss_{fwd,bwd}_f32): the stacked cost
     assembly R = [x; x'], F = [y; y'] + the four cost blocks, the four solves + their combination (W1 + W2) - W3 - W4, and
@@ -546,6 +620,31 @@ def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef
     R = torch.cat([vids[0], vids[2]], 0)
     F = torch.cat([vids[1], vids[3]], 0)
     return _MixedSinkhornLoss.apply(R, F, *feats, float(scaling_coef), eps, L, _LMIN, "compute_mixed_sinkhorn_loss")
+
+
+def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
+                                   m_fake, video=True, *, honor_eps_l=False):
+    """Bi-causal Sinkhorn loss, 2 W(x,y) - W(x,x) - W(y,y) with W = compute_sinkhorn(..., bi_causal=True)
+    (gan_utils.py:124-136) and x = real, y = fake:
+
+        W(x,y) = compute_sinkhorn(real, fake, h_fake, m_real, sc, hx=h_real, My=m_fake, bi_causal=True)
+        W(x,x) = compute_sinkhorn(real, real, h_real, m_real, sc, hx=h_real, My=m_real, bi_causal=True)
+        W(y,y) = compute_sinkhorn(fake, fake, h_fake, m_fake, sc, hx=h_fake, My=m_fake, bi_causal=True)
+
+    i.e. C_xy gains the causal term of (h_real rows, m_fake columns) and C_xx / C_yy carry their own causal term twice.
+    EXTENSION: the reference implements the bi-causal cost and names the mode in kernel_train.py's ``--bi_causal`` flag
+    (:396), but its compute_sinkhorn_loss never passes ``bi_causal``.  Same positional arguments as compute_sinkhorn_loss;
+    ``sinkhorn_eps`` / ``sinkhorn_l`` are ignored by default (epsilon = 1, L = 100) for the same reason, and
+    ``honor_eps_l=True`` applies them.  Differentiable w.r.t. the fake videos and all four features; a real video that
+    requires a gradient raises NotImplementedError.  Records last_info["compute_bicausal_sinkhorn_loss"] (the three
+    reference-equivalent iteration counts), ``..._executed``, ``..._costs`` [3], ``..._C3`` [3,B,B] and
+    ``..._fused_sweep``.
+    """
+    del video  # both layouts flatten to [B, K]
+    eps, L = (float(sinkhorn_eps), int(sinkhorn_l)) if honor_eps_l else (1.0, 100)
+    real, fake = _flat2(f_real), _flat2(f_fake)
+    return _BicausalSinkhornLoss.apply(real, fake, _feat(h_fake), _feat(h_real), _feat(m_real), _feat(m_fake),
+                                       float(scaling_coef), eps, L, _LMIN, "compute_bicausal_sinkhorn_loss")
 
 
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):

@@ -87,14 +87,22 @@ class KCCOTTrainer:
     def __init__(self, batch_size, total_time_steps=15, int_time_steps=5, x_height=64, x_width=64, channels=3,
                  g_state_size=8, d_state_size=8, g_filter_size=8, d_filter_size=8, z_channels=128, bn=True,
                  lr=5e-4, warmup=10000, sinkhorn_eps=0.8, sinkhorn_l=100, scaling_coef=15.0, reg_penalty=1.0,
-                 kernel="none", device="cuda", seed=1, group=None, mixed_sinkhorn=False):
+                 kernel="none", device="cuda", seed=1, group=None, mixed_sinkhorn=False,
+                 bi_causal=False):
         # defaults = kernel_train.py:363-409
         # mixed_sinkhorn=True: the loss is COT-GAN's mixed Sinkhorn divergence over two minibatches
         # (gan_utils.compute_mixed_sinkhorn_loss) -- what the reference's --mixed_sinkhorn flag (:393) names but never runs
         data_parallel = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        # bi_causal=True: the loss is 2 W(x,y) - W(x,x) - W(y,y) with the bi-causal cost (gan_utils.compute_bicausal_sinkhorn_loss)
+        # -- the reference's --bi_causal flag (:396) only renames its output files
+        if mixed_sinkhorn and bi_causal:
+            raise ValueError("mixed_sinkhorn=True and bi_causal=True are exclusive loss modes (kernel_train.py:179-184)")
         if mixed_sinkhorn and data_parallel:
             raise NotImplementedError("mixed_sinkhorn=True has no batch-sharded (data-parallel) form")
+        if bi_causal and data_parallel:
+            raise NotImplementedError("bi_causal=True has no batch-sharded (data-parallel) form")
         self.mixed_sinkhorn = bool(mixed_sinkhorn)
+        self.bi_causal = bool(bi_causal)
         torch.manual_seed(seed)
         self.batch_size, self.device, self.group = batch_size, torch.device(device), group
         self.int_time_steps = int_time_steps
@@ -156,7 +164,10 @@ class KCCOTTrainer:
         h_real = self.discriminator_h(real)
         m_real = self.discriminator_m(real)
         m_fake = self.discriminator_m(fake)
-        if self._world() > 1:
+        if self.bi_causal:
+            loss = gan_utils.compute_bicausal_sinkhorn_loss(real.detach(), fake, self.scaling_coef, self.sinkhorn_eps,
+                                                            self.sinkhorn_l, h_fake, m_real, h_real, m_fake, video=True)
+        elif self._world() > 1:
             from . import dist as kd
             loss = kd.sharded_sinkhorn_loss(real.detach(), fake, self.scaling_coef, h_fake, m_real, h_real, m_fake,
                                             group=self.group)
@@ -198,6 +209,12 @@ class KCCOTTrainer:
         if real_in_p is None or real_pred_p is None:
             raise ValueError("mixed_sinkhorn=True needs the second real minibatch (real_in_p, real_pred_p)")
         return self._forward_mixed(real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad)
+
+    def _loss_tag(self):
+        """the gan_utils.last_info tag of the loss this trainer evaluates"""
+        if self.mixed_sinkhorn:
+            return "compute_mixed_sinkhorn_loss"
+        return "compute_bicausal_sinkhorn_loss" if self.bi_causal else "compute_sinkhorn_loss"
 
     def _world(self):
         return dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -307,8 +324,7 @@ class KCCOTTrainer:
                 log("Sinkhorn Loss", loss, it_counts)
             if not math.isfinite(loss):                                          # :323
                 # an aborted multi-CU solve is an error, not an exploded loss
-                gan_utils.raise_if_solver_aborted(("compute_mixed_sinkhorn_loss",) if self.mixed_sinkhorn
-                                                  else ("compute_sinkhorn_loss",))
+                gan_utils.raise_if_solver_aborted((self._loss_tag(),))
                 exploded = True
                 break
             if test_x is not None and (it_counts % save_freq == 0 or it_counts == 1) and log is not None:   # :331
