@@ -76,7 +76,8 @@ const char* kccot_last_error(void);
  *   apply_m256                1        0: the video gradient of B % 256 == 0 in 64-row blocks instead of 256-row tiles
  *   apply_one_launch          1        0: the loss's video gradient at B <= 64 as coefficient build + apply (two launches);
  *                                      1: one launch -- the apply kernel's consumer waves form their coefficient fragments from dC
- *                                      themselves, the feature gradients run in its spare workgroups
+ *                                      themselves, its producer waves run the feature gradients ahead of their tile loads (taken
+ *                                      when real, fake and dC are 16-byte aligned; otherwise the two-launch form)
  *   apply_q256                1        0: the video gradient of B % 256 == 0 on 256 x 64 / 128 tiles with the coefficient fragments
  *                                      streamed from L2; 1: from 512 tiles on, 256 x 256 output tiles with the coefficient panel
  *                                      staged through LDS (csrc/cost_bwd_q256.hip; bit-identical, 13.7 -> 11.1 ms at configs[4])

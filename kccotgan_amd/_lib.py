@@ -247,10 +247,15 @@ def workspace(nbytes, ref):
         return None, 0
     key = (ref.device, stream_of(ref))
     buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        if _CANARY:   # float32 view so that the guard sentinel is exact
+    if _CANARY:
+        # a buffer of exactly the requested size (float32 view so that the guard sentinel is exact), so that the guard
+        # zone starts at nbytes: a cached larger buffer would hide an overrun into its slack.  The previous one stays
+        # referenced by _guards until it is verified.  nbytes is a multiple of 4 for every workspace query.
+        if buf is None or buf.numel() * 4 != (int(nbytes) + 3) // 4 * 4:
             buf = empty(((int(nbytes) + 3) // 4,), torch.float32, ref.device)
-        else:
-            buf = torch.empty(int(nbytes), dtype=torch.uint8, device=ref.device)
+            _ws_cache[key] = buf
+        return buf.data_ptr(), int(nbytes)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(int(nbytes), dtype=torch.uint8, device=ref.device)
         _ws_cache[key] = buf
-    return buf.data_ptr(), int(nbytes) if _CANARY else buf.numel()
+    return buf.data_ptr(), buf.numel()

@@ -1423,9 +1423,10 @@ static int cost3_bwd_rows_impl(const float* g3, const float* gscale, const float
     const size_t need = kccot_pairwise_cost3_bwd_workspace_bytes(B, K);
     if (!ws || ws_bytes < need)
         return fail(KCCOT_EWORKSPACE, "pairwise_cost3_bwd: workspace %zu < required %zu", ws_bytes, need);
-    // B <= 64, whole batch, aligned rows: ONE launch (W built by the consumer waves, feature gradients in spare workgroups)
+    // B <= 64, whole batch, aligned rows: ONE launch (W built by the consumer waves from gxy / gyy, read with 16-byte loads;
+    // the feature gradients run as tasks of the producer waves, ahead of their tile loads)
     if (B <= 64 && B % 8 == 0 && row_begin == 0 && row_count == B && K % 4 == 0 && (uintptr_t)real % 16 == 0 &&
-        (uintptr_t)fake % 16 == 0 && !opt(OPT_APPLY_F32) && opt(OPT_APPLY_ONE_LAUNCH)) {
+        (uintptr_t)fake % 16 == 0 && (uintptr_t)g3 % 16 == 0 && !opt(OPT_APPLY_F32) && opt(OPT_APPLY_ONE_LAUNCH)) {
         Loss3Apply la{};
         la.gxy = gxy; la.gyy = gyy; la.gscale = gscale; la.real = real; la.fake = fake; la.out = dfake;
         la.B = B; la.sc = sc; la.K = K; la.ntiles = (K + AM_COLS - 1) / AM_COLS;

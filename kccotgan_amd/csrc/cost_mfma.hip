@@ -571,6 +571,14 @@ __global__ __launch_bounds__(512) void gram128_partial_x3ws(GramArgs ga) {
 
 enum { GRAM_SPLIT_NONE = 0, GRAM_SPLIT_89 = 1 };
 
+// the causal tiles alone, one per workgroup: the finalize-only call (KCCOT_COST_FROM_GRAM_SUMS) forms them from the features it
+// is given -- the hand-over between the two calls is the reported span of Gram sums and nothing else in the workspace
+__global__ __launch_bounds__(256) void causal_pre_only(CausalPre cp) {
+    __shared__ __attribute__((aligned(16))) float csh[CAUSAL_TILE * CAUSAL_PITCH];
+    __shared__ __attribute__((aligned(16))) float csm[CAUSAL_TILE * CAUSAL_PITCH];
+    causal_pre_tile(cp, blockIdx.x, csh, csm, threadIdx.x);
+}
+
 __global__ __launch_bounds__(1024) void gram_reduce(const float* __restrict__ gpart, int nchunk, unsigned mask, int split_mode,
                                                     double* __restrict__ gsum, CausalPre cp) {
     __shared__ double part[16][64];
@@ -846,6 +854,11 @@ int run_gram(const CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J,
     const bool compact = ga.mask == 0x3FFu && gram_use_x3();   // gram128_partial_x3ws writes compact records
     gf.compact = compact ? 1 : 0;
     if (stage == 2) {
+        if (ncausal > 0) {
+            hipLaunchKernelGGL(causal_pre_only, dim3(ncausal), dim3(256), 0, st, cp);
+            const int rcc = launch_status("causal_pre_only");
+            if (rcc) return rcc;
+        }
         gf.gsum = gsum; gf.caus = cp.caus; gf.mode = mode; gf.sc = sc; gf.T = T; gf.J = J;
         hipLaunchKernelGGL(gram_finalize, dim3((gf.B2 + CAUSAL_TILE - 1) / CAUSAL_TILE, (gf.B1 + CAUSAL_TILE - 1) / CAUSAL_TILE, nout),
                            dim3(256), 0, st, gf);

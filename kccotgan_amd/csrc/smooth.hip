@@ -360,6 +360,15 @@ enum { WALK_MAX = 0, WALK_WRITE = 1, WALK_RAW = 2, WALK_ADJ = 3, WALK_ADJX = 4, 
 constexpr int SMOOTH_MAX_TIES = 32;    // arg-max elements the sparse fix-up handles; more -> the dense fallback (on the device)
 constexpr int TIE_PER_WG = 4;
 struct TieRec { double dot; long long idx[TIE_PER_WG]; int ties; int pad; };
+// Workspace behind the tensor-sized buffer (kccot_smooth_workspace_bytes): two per-block arrays (forward: block maxima;
+// backward without the fold: the partial sums of the normalisation adjoint), 256 bytes of scalars, a record area.  Only the
+// folded backward writes TieRecs, and it gathers its sums itself: it lays the records over the per-block arrays AND the
+// record area and puts the scalars behind them.  tie_rec_capacity = the records that fit there.  Every launch that writes
+// TieRecs checks its grid against it on the host: it depends on the shape only, never on the options, so a caller that
+// sized the workspace and then changed an option still gets a launch that fits.
+static inline size_t smooth_blk_bytes(int64_t n) { return align_up((size_t)((n + 255) / 256) * sizeof(float), 256); }
+static inline size_t smooth_rec_bytes(int64_t n) { return align_up((size_t)(n / 1024 + 2) * sizeof(TieRec), 256); }
+static inline int64_t tie_rec_capacity(int64_t n) { return (int64_t)((2 * smooth_blk_bytes(n) + smooth_rec_bytes(n)) / sizeof(TieRec)); }
 
 struct TieNote {                       // LDS side of one workgroup's record (workgroups of 256 threads)
     double part[4]; long long idx[TIE_PER_WG]; int n;
@@ -1245,7 +1254,8 @@ struct Fused3Plan { int wt, hseg, ni, nt; size_t lds; int64_t grid; bool ok; };
 
 // tile choice: the cheapest (column halo) x (plane halo) overhead among the power-of-two cuts of W and H that still fills the
 // CUs; NI = float4 items per thread <= 4 at <= 512 threads
-static Fused3Plan fused3_plan(int B, int H, int T, int W, int C, int radius, const void* p0, const void* p1, bool adj = false) {
+static Fused3Plan fused3_plan(int B, int H, int T, int W, int C, int radius, const void* p0, const void* p1, bool adj = false,
+                              bool ties = false) {
     Fused3Plan best{};
     const int mode = opt(OPT_SMOOTH_FUSED3);
     if (!mode || !(radius == 3 || radius == 4) || !(C == 1 || C == 3)) return best;
@@ -1290,7 +1300,10 @@ static Fused3Plan fused3_plan(int B, int H, int T, int W, int C, int radius, con
             // below one full round the chip idles: price that as if the work were spread over the workgroups there are
             double cost = over * (waves >= 1.0 ? 1.0 : 1.0 / waves);
             if (force_hs) cost = hs == force_hs ? 0.0 : 1e29;
-            if (cost < best_cost && grid <= 0x7fffffff) { best_cost = cost; best = Fused3Plan{wt, hs, ni, nt, lds, grid, true}; }
+            // ties: the adjoint writes one TieRec per workgroup -- a tiling with more workgroups than the workspace has records is
+            // not a candidate (one tile per sample at least, so many tiny frames may find no plan and take the chain)
+            const bool fits = !ties || grid <= tie_rec_capacity(numel);
+            if (cost < best_cost && grid <= 0x7fffffff && fits) { best_cost = cost; best = Fused3Plan{wt, hs, ni, nt, lds, grid, true}; }
             if (hs == 8) break;
         }
     }
@@ -1909,11 +1922,10 @@ using namespace kccot;
 extern "C" size_t kccot_smooth_workspace_bytes(int B, int H, int T, int W, int C) {
     if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return 0;
     const size_t n = (size_t)B * H * T * W * C;
-    const size_t nb = (n + 255) / 256;
     // one tensor-sized ping-pong buffer + two per-block reduction arrays + scalars + the backward's per-workgroup tie
-    // records (a line kernel's workgroup covers >= 256 lines of >= 4 elements)
-    return align_up(n * sizeof(float), 256) + 2 * align_up(nb * sizeof(float), 256) + 256 +
-           align_up((n / 1024 + 2) * sizeof(TieRec), 256);
+    // records (a line kernel's workgroup covers >= 256 lines of >= 4 elements; the folded backward also lays records over
+    // the per-block arrays: tie_rec_capacity)
+    return align_up(n * sizeof(float), 256) + 2 * smooth_blk_bytes((int64_t)n) + 256 + smooth_rec_bytes((int64_t)n);
 }
 
 static int smooth_check(const char* who, const void* a, const void* b, int B, int H, int T, int W, int C, float sigma,
@@ -2151,8 +2163,12 @@ static int smooth_bwd_impl(const float* gout, const float* out, const float* max
     // Round 4: with the three adjoint stages in ONE pass (smooth_fused3_adj, which gathers the sums itself) folding pays from
     // 3.5 M elements on for the 3-D call -- the plan decides.
     Fused3Plan fpa{};
-    if (chain && three && (stats_in || fold_opt != 0) && ((uintptr_t)out & 15) == 0) fpa = fused3_plan(B, H, T, W, C, radius, gout, din, true);
+    if (chain && three && (stats_in || fold_opt != 0) && ((uintptr_t)out & 15) == 0) fpa = fused3_plan(B, H, T, W, C, radius, gout, din, true, !stats_in);
     const bool fold = chain && !stats_in && (fold_opt == 2 || fpa.ok || (fold_opt == 1 && n >= (three ? (int64_t)1 << 25 : (int64_t)1 << 22)));
+    if (fold) {     // no per-block partial sums: the records start at the per-block arrays, the scalars sit behind the records
+        recs = reinterpret_cast<TieRec*>(p);
+        scal = res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n) + smooth_rec_bytes(n));
+    }
     if (stats_in && fpa.ok) {       // the batch-sharded caller: sums handed in, correction applied at the loads, nothing to fix up
         Fused3AdjArgs fa{};
         fa.gout = gout; fa.out_fwd = out; fa.din = din; fa.mx = max_in; fa.res = stats_ext;
@@ -2210,6 +2226,8 @@ static int smooth_bwd_impl(const float* gout, const float* out, const float* max
                 if ((rc2 = launch_axis(WALK_ADJ, wd, radius, n, pt, st))) return rc2;
                 return 0;
             };
+            if (fold && nrec > tie_rec_capacity(n))
+                return fail(KCCOT_EUNSUPPORTED, "smooth_bwd: %d tie records > %lld in the workspace", nrec, (long long)tie_rec_capacity(n));
             if (!three) {
                 wa.in = gout; wa.out = din; wa.L = T; wa.S = WC;
                 if ((rc = launch_axis(first, wa, radius, n, pt, st))) return rc;
@@ -2218,6 +2236,9 @@ static int smooth_bwd_impl(const float* gout, const float* out, const float* max
             {               // all three adjoint stages in one pass (smooth_fused3_adj), the statistics gathered on the way
                 const Fused3Plan& fp = fpa;
                 if (fp.ok) {
+                    if (fp.grid > tie_rec_capacity(n))      // (fused3_plan never returns such a plan; checked where the records are written)
+                        return fail(KCCOT_EUNSUPPORTED, "smooth_bwd: %lld tie records > %lld in the workspace", (long long)fp.grid,
+                                    (long long)tie_rec_capacity(n));
                     Fused3AdjArgs fa{};
                     fa.gout = gout; fa.out_fwd = out; fa.din = din; fa.mx = max_in; fa.ties = recs;
                     fa.H = H; fa.T = T; fa.W = W; fa.wt = fp.wt; fa.ntw = W / fp.wt; fa.hseg = fp.hseg;

@@ -252,3 +252,38 @@ def test_isa_of_the_three_cost_hand_off_to_the_combining_workgroup(tmp_path):
             first_load = ahead.index(loads[0])
             assert wait and wait[0] < first_load, name             # the add has returned before the first load issues
     assert seen >= 6, seen                                         # register forward kernels + fused kernels, every instantiation
+
+
+def test_every_entry_point_that_writes_device_memory_has_bounds_coverage():
+    """Every function of include/kccot.h that takes a workspace (`void* ws`) or a non-const pointer output appears in the
+    entry-point table of tests/abi_guard.py, with the same output parameter names, a workspace query that the header
+    declares, and a bounds test that exists in tests/test_gpu_abi_bounds.py -- a new entry point without guard-zone
+    coverage fails here, on the CPU."""
+    import abi_guard
+    text = open(os.path.join(ROOT, "include", "kccot.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    decls = dict((m.group(1), m.group(2)) for m in re.finditer(r"\b(kccot_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text))
+    assert sorted(decls) == header_symbols()
+    writers = {}
+    for name, args in decls.items():
+        outs = []
+        for a in args.split(","):
+            a = a.strip()
+            if "*" in a and not a.startswith("const"):
+                outs.append(a.split()[-1].lstrip("*"))
+        if outs:
+            writers[name] = outs
+    host = abi_guard.HOST_OUTPUTS
+    assert sorted(set(writers) - set(abi_guard.ENTRIES)) == sorted(host), "entry points without bounds coverage"
+    for name, outs in host.items():
+        assert writers[name] == outs
+    bounds = open(os.path.join(ROOT, "tests", "test_gpu_abi_bounds.py")).read()
+    for name, e in abi_guard.ENTRIES.items():
+        assert name in decls, name
+        want = [o for o in writers[name] if o != "ws"]
+        assert sorted(e["outputs"]) == sorted(want), (name, want)
+        assert ("ws" in writers[name]) == (e["ws"] is not None), name
+        if e["ws"]:
+            assert e["ws"] in decls, (name, e["ws"])
+        assert re.search(r"^def %s\(" % e["test"], bounds, flags=re.M), (name, e["test"])
+        assert '"%s"' % name in bounds, "%s is not called by %s" % (name, e["test"])

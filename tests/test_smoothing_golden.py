@@ -426,11 +426,14 @@ def test_fused_3d_adjoint_equals_the_chain(shape, ties):
     wsb = int(lib.kccot_smooth_workspace_bytes(B, H, T, W, C))
 
     def bwd():
+        import abi_guard
         din = torch.full(shape, float("nan"), device="cuda")
-        buf = torch.empty(wsb // 4 + 64, device="cuda")
+        ws = abi_guard.guarded(wsb, "workspace", "workspace")          # exactly the queried size, guard zones either side
+        buf = ws.payload().view(torch.float32)
         buf[:n] = -7.0
-        check(lib.kccot_smooth_bwd_f32(ptr(g), ptr(o), ptr(mx), B, H, T, W, C, 2.1, 3, axes, ptr(din), buf.data_ptr(), wsb, None), "bwd")
+        check(lib.kccot_smooth_bwd_f32(ptr(g), ptr(o), ptr(mx), B, H, T, W, C, 2.1, 3, axes, ptr(din), ws.ptr, wsb, None), "bwd")
         torch.cuda.synchronize()
+        assert ws.verify() is None, ws.verify()
         return din, bool((buf[:n] != -7.0).any())
 
     with _lib.options(smooth_bwd_fold=2, smooth_fused3=2):
