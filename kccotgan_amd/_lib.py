@@ -240,12 +240,12 @@ def stream_of(t):
 _ws_cache = {}
 
 
-def workspace(nbytes, ref):
+def workspace(nbytes, ref, stream=None):
     """A per-(device, stream) scratch buffer, grown on demand.  Calls issued on one stream are
-    ordered, so successive kernels may reuse it."""
+    ordered, so successive kernels may reuse it.  ``stream``: stream_of(ref), if the caller has it."""
     if nbytes <= 0:
         return None, 0
-    key = (ref.device, stream_of(ref))
+    key = (ref.device, stream_of(ref) if stream is None else stream)
     buf = _ws_cache.get(key)
     if _CANARY:
         # a buffer of exactly the requested size (float32 view so that the guard sentinel is exact), so that the guard

@@ -16,6 +16,7 @@
 //             term of each matrix added in place) -> the three solves + combination (fused solve + sweep, or history)
 //   backward: [history path: reverse sweep] -> the one-batch cost backward with the bi-causal feature-gradient job table
 //             (cost_bwd.hip: per-term weights 1, 2); dfake is the one-batch loss's (the distance part is unchanged).
+// The entry points kccot_bicausal_sinkhorn_loss_* run the one-batch loss's host sequence (loss.hip) with these two changes.
 #include "common.h"
 
 namespace kccot {
@@ -89,88 +90,12 @@ __global__ __launch_bounds__(256) void bicausal_cost_add(float* __restrict__ C3,
     }
 }
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-}  // namespace kccot
-using namespace kccot;
-
-extern "C" size_t kccot_bicausal_sinkhorn_loss_workspace_bytes(int B, int64_t K) {
-    // the one-batch loss's layout: dC3 [3,B,B] + 3 floats of the history backward, then one stage at a time
-    return kccot_sinkhorn_loss_workspace_bytes(B, K);
-}
-
-extern "C" int kccot_bicausal_sinkhorn_loss_fwd_f32(const float* real, const float* fake, int B, int64_t K, float sc,
-                                                    const float* h_fake, const float* h_real, const float* m_real,
-                                                    const float* m_fake, int T, int J, float eps, int L, int Lmin,
-                                                    float thresh, unsigned flags, float* C3, float* u_hist, float* v_hist,
-                                                    float* dC3_unit, float* cost3_out, int32_t* nits_out, float* loss_out,
-                                                    int32_t* ticket, void* ws, size_t ws_bytes, kccot_stream_t stream) {
-    if (!real || !fake || !h_fake || !h_real || !m_real || !m_fake)
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: null input pointer");
-    if (!C3 || !cost3_out || !nits_out || !loss_out || !ticket)
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: null output pointer");
-    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: bad arguments B=%d K=%lld T=%d J=%d L=%d eps=%g", B,
-                    (long long)K, T, J, L, (double)eps);
-    if ((u_hist == nullptr) != (v_hist == nullptr) || (dC3_unit && u_hist))
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: give u_hist and v_hist together, or dC3_unit, not both");
-    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS))
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: the Gram-sum split flags do not apply");
-    if (!ws || ws_bytes < kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K))
-        return fail(KCCOT_EWORKSPACE, "bicausal_sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
-                    kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K));
-    hipStream_t st = (hipStream_t)stream;
-    int rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes,
-                                      stream);
-    if (rc) return rc;
+int launch_bicausal_cost_add(float* C3, int B, const float* h_fake, const float* h_real, const float* m_real,
+                             const float* m_fake, int T, int J, float sc, hipStream_t st) {
     const unsigned tiles = (unsigned)((B + BC_TILE - 1) / BC_TILE);
     hipLaunchKernelGGL(bicausal_cost_add, dim3(tiles, tiles, 3), dim3(256), 0, st, C3,
                        BicausalAdd{{h_real, h_real, h_fake}, {m_fake, m_real, m_fake}}, B, T, J, sc);
-    if ((rc = launch_status("bicausal_cost_add"))) return rc;
-    if (dC3_unit)
-        return kccot_sinkhorn_divergence_fused_f32(C3, B, eps, L, Lmin, thresh, cost3_out, nits_out, loss_out, ticket,
-                                                   dC3_unit, stream);
-    return kccot_sinkhorn_divergence_fwd_f32(C3, B, eps, L, Lmin, thresh, u_hist, v_hist, cost3_out, nits_out, loss_out,
-                                             ticket, ws, ws_bytes, stream);
+    return launch_status("bicausal_cost_add");
 }
 
-extern "C" int kccot_bicausal_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const float* fake, int B,
-                                                    int64_t K, float sc, const float* h_fake, const float* h_real,
-                                                    const float* m_real, const float* m_fake, int T, int J, float eps,
-                                                    int L, const float* C3, const float* u_hist, const float* v_hist,
-                                                    const int32_t* nits, const float* dC3_unit, float* dfake,
-                                                    float* dh_fake, float* dh_real, float* dm_real, float* dm_fake,
-                                                    void* ws, size_t ws_bytes, kccot_stream_t stream) {
-    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake)
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_bwd: null input pointer");
-    if (!dC3_unit && (!C3 || !u_hist || !v_hist || !nits))
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_bwd: give dC3_unit (fused forward) or C3, u_hist, v_hist, nits");
-    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
-        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_bwd: bad arguments B=%d K=%lld T=%d J=%d", B, (long long)K, T, J);
-    if (!ws || ws_bytes < kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K))
-        return fail(KCCOT_EWORKSPACE, "bicausal_sinkhorn_loss_bwd: workspace %zu < %zu bytes", ws_bytes,
-                    kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K));
-    hipStream_t st = (hipStream_t)stream;
-    if (dC3_unit)
-        return cost3_bwd_bicausal(dC3_unit, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake,
-                                  dh_real, dm_real, dm_fake, ws, ws_bytes, st);
-    // history path, laid out as kccot_sinkhorn_loss_bwd_f32: dC3 [3,B,B] | 3 floats | stage
-    char* base = static_cast<char*>(ws);
-    float* dC3 = reinterpret_cast<float*>(base);
-    const size_t off_gc = up256((size_t)3 * B * B * sizeof(float));
-    float* gc = reinterpret_cast<float*>(base + off_gc);
-    void* stage = base + off_gc + 256;
-    const size_t stage_bytes = ws_bytes - off_gc - 256;
-    int rc;
-    if (kccot_sinkhorn_workspace_bytes(3, B) > 0) {
-        // streaming solver (n > 128): weights {2,-1,-1} * gloss first, then the generic reverse sweep
-        rc = kccot_mixed_divergence_bwd_f32(gloss, gc, stream);
-        if (rc) return rc;
-        rc = kccot_sinkhorn_bwd_f32(C3, u_hist, v_hist, nits, 3, B, eps, L, gc, dC3, stage, stage_bytes, stream);
-    } else {
-        rc = kccot_sinkhorn_divergence_bwd_f32(C3, u_hist, v_hist, nits, B, eps, L, gloss, dC3, stage, stage_bytes, stream);
-    }
-    if (rc) return rc;
-    return cost3_bwd_bicausal(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake,
-                              dh_real, dm_real, dm_fake, stage, stage_bytes, st);
-}
+}  // namespace kccot

@@ -32,6 +32,7 @@ inline int launch_status(const char* what) {
 }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- wave-level reductions (64-wide wavefront; xor butterflies leave the result in every lane)
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory
@@ -142,12 +143,17 @@ int sinkhorn_fused_weighted(const float* C, int nprob, const float* w, int n, fl
                             float* cost_out, int32_t* nits_out, float* loss_out, int32_t* ticket, float* dC_unit,
                             hipStream_t st);
 
-// cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) with the feature-gradient jobs of the
-// bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake, dh_real = gxy.dm_fake + 2 gxx.dm_real,
-// dm_real = gxy with h_fake + 2 gxx with h_real, dm_fake = gxy with h_real + 2 gyy with h_fake; dfake as the one-batch loss.
-int cost3_bwd_bicausal(const float* g3, const float* gscale, const float* real, const float* fake, int B, int64_t K, float sc,
-                       const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
-                       float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake, void* ws,
-                       size_t ws_bytes, hipStream_t st);
+// cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) over the whole batch.  bicausal selects the
+// feature-gradient jobs of the bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake,
+// dh_real = gxy.dm_fake + 2 gxx.dm_real, dm_real = gxy with h_fake + 2 gxx with h_real, dm_fake = gxy with h_real +
+// 2 gyy with h_fake; dfake as the one-batch loss.
+int cost3_bwd_loss(const float* g3, const float* gscale, const float* real, const float* fake, int B, int64_t K, float sc,
+                   const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
+                   float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake, void* ws, size_t ws_bytes,
+                   hipStream_t st, bool bicausal);
+
+// bicausal.hip: C3 [3,B,B] += the second causal term of each bi-causal cost matrix, in place
+int launch_bicausal_cost_add(float* C3, int B, const float* h_fake, const float* h_real, const float* m_real,
+                             const float* m_fake, int T, int J, float sc, hipStream_t st);
 
 }  // namespace kccot

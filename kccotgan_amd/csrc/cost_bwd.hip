@@ -1464,12 +1464,12 @@ static int cost3_bwd_rows_impl(const float* g3, const float* gscale, const float
 }
 
 namespace kccot {
-int cost3_bwd_bicausal(const float* g3, const float* gscale, const float* real, const float* fake, int B, int64_t K, float sc,
-                       const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
-                       float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake, void* ws,
-                       size_t ws_bytes, hipStream_t st) {
+int cost3_bwd_loss(const float* g3, const float* gscale, const float* real, const float* fake, int B, int64_t K, float sc,
+                   const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
+                   float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake, void* ws, size_t ws_bytes,
+                   hipStream_t st, bool bicausal) {
     return cost3_bwd_rows_impl(g3, gscale, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, 0, B, dfake, dh_fake,
-                               dh_real, dm_real, dm_fake, ws, ws_bytes, (kccot_stream_t)st, true);
+                               dh_real, dm_real, dm_fake, ws, ws_bytes, (kccot_stream_t)st, bicausal);
 }
 }  // namespace kccot
 

@@ -2,11 +2,62 @@
 // cost assembly -> three Sinkhorn solves + combination (forward) and reverse sweep -> cost backward
 // (backward) is issued from C, so a caller pays one FFI crossing and one workspace per direction
 // instead of one per stage.  No new kernels: these entry points only sequence the stage functions.
+// The bi-causal loss (bicausal.hip) runs the same sequence with one launch more in the forward (its second causal terms)
+// and its own feature-gradient jobs in the cost backward.
 #include "common.h"
 
 namespace kccot {
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 static size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
+
+// cost assembly [-> bi-causal terms] -> the three solves + combination: ONE launch with the reverse sweep at dLoss = 1 when
+// dC3_unit is given (C3 is then scratch for the caller), the dual history (u_hist / v_hist, both may be null) otherwise
+static int loss3_fwd(bool bicausal, const float* real, const float* fake, int B, int64_t K, float sc, const float* h_fake,
+                     const float* h_real, const float* m_real, const float* m_fake, int T, int J, float eps, int L, int Lmin,
+                     float thresh, unsigned flags, float* C3, float* u_hist, float* v_hist, float* dC3_unit,
+                     float* cost3_out, int32_t* nits_out, float* loss_out, int32_t* ticket, void* ws, size_t ws_bytes,
+                     kccot_stream_t stream) {
+    int rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes,
+                                      stream);
+    if (rc) return rc;
+    if (bicausal && (rc = launch_bicausal_cost_add(C3, B, h_fake, h_real, m_real, m_fake, T, J, sc, (hipStream_t)stream)))
+        return rc;
+    if (dC3_unit)
+        return kccot_sinkhorn_divergence_fused_f32(C3, B, eps, L, Lmin, thresh, cost3_out, nits_out, loss_out, ticket,
+                                                   dC3_unit, stream);
+    return kccot_sinkhorn_divergence_fwd_f32(C3, B, eps, L, Lmin, thresh, u_hist, v_hist, cost3_out, nits_out, loss_out,
+                                             ticket, ws, ws_bytes, stream);
+}
+
+// after the fused forward: coefficient build (dC3_unit x gloss) -> video gradient; after the history forward: reverse sweep
+// into the workspace, laid out dC3 [3,B,B] | 3 floats | stage, then the cost backward in the stage
+static int loss3_bwd(bool bicausal, const float* gloss, const float* real, const float* fake, int B, int64_t K, float sc,
+                     const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
+                     float eps, int L, const float* C3, const float* u_hist, const float* v_hist, const int32_t* nits,
+                     const float* dC3_unit, float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake,
+                     void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (dC3_unit)
+        return cost3_bwd_loss(dC3_unit, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake,
+                              dh_real, dm_real, dm_fake, ws, ws_bytes, st, bicausal);
+    char* base = static_cast<char*>(ws);
+    float* dC3 = reinterpret_cast<float*>(base);
+    const size_t off_gc = up256((size_t)3 * B * B * sizeof(float));
+    float* gc = reinterpret_cast<float*>(base + off_gc);
+    void* stage = base + off_gc + 256;
+    const size_t stage_bytes = ws_bytes - off_gc - 256;
+    int rc;
+    if (kccot_sinkhorn_workspace_bytes(3, B) > 0) {
+        // streaming solver (n > 128): weights {2,-1,-1} * gloss first, then the generic reverse sweep
+        rc = kccot_mixed_divergence_bwd_f32(gloss, gc, stream);
+        if (rc) return rc;
+        rc = kccot_sinkhorn_bwd_f32(C3, u_hist, v_hist, nits, 3, B, eps, L, gc, dC3, stage, stage_bytes, stream);
+    } else {
+        rc = kccot_sinkhorn_divergence_bwd_f32(C3, u_hist, v_hist, nits, B, eps, L, gloss, dC3, stage, stage_bytes, stream);
+    }
+    if (rc) return rc;
+    return cost3_bwd_loss(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake, dh_real,
+                          dm_real, dm_fake, stage, stage_bytes, st, bicausal);
+}
 }  // namespace kccot
 using namespace kccot;
 
@@ -29,11 +80,8 @@ extern "C" int kccot_sinkhorn_loss_fwd_f32(const float* real, const float* fake,
     if (ws_bytes < kccot_sinkhorn_loss_workspace_bytes(B, K) || (!ws && ws_bytes))
         return fail(KCCOT_EWORKSPACE, "sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
                     kccot_sinkhorn_loss_workspace_bytes(B, K));
-    int rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes,
-                                      stream);
-    if (rc) return rc;
-    return kccot_sinkhorn_divergence_fwd_f32(C3, B, eps, L, Lmin, thresh, u_hist, v_hist, cost3_out, nits_out, loss_out,
-                                             ticket, ws, ws_bytes, stream);
+    return loss3_fwd(false, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, Lmin, thresh, flags, C3,
+                     u_hist, v_hist, nullptr, cost3_out, nits_out, loss_out, ticket, ws, ws_bytes, stream);
 }
 
 extern "C" int kccot_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const float* fake, int B, int64_t K,
@@ -46,24 +94,8 @@ extern "C" int kccot_sinkhorn_loss_bwd_f32(const float* gloss, const float* real
     if (!ws || ws_bytes < kccot_sinkhorn_loss_workspace_bytes(B, K))
         return fail(KCCOT_EWORKSPACE, "sinkhorn_loss_bwd: workspace %zu < %zu bytes", ws_bytes,
                     kccot_sinkhorn_loss_workspace_bytes(B, K));
-    char* base = static_cast<char*>(ws);
-    float* dC3 = reinterpret_cast<float*>(base);
-    const size_t off_gc = up256((size_t)3 * B * B * sizeof(float));
-    float* gc = reinterpret_cast<float*>(base + off_gc);
-    void* stage = base + off_gc + 256;
-    const size_t stage_bytes = ws_bytes - off_gc - 256;
-    int rc;
-    if (kccot_sinkhorn_workspace_bytes(3, B) > 0) {
-        // streaming solver (n > 128): weights {2,-1,-1} * gloss first, then the generic reverse sweep
-        rc = kccot_mixed_divergence_bwd_f32(gloss, gc, stream);
-        if (rc) return rc;
-        rc = kccot_sinkhorn_bwd_f32(C3, u_hist, v_hist, nits, 3, B, eps, L, gc, dC3, stage, stage_bytes, stream);
-    } else {
-        rc = kccot_sinkhorn_divergence_bwd_f32(C3, u_hist, v_hist, nits, B, eps, L, gloss, dC3, stage, stage_bytes, stream);
-    }
-    if (rc) return rc;
-    return kccot_pairwise_cost3_bwd_f32(dC3, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake,
-                                        dh_real, dm_real, dm_fake, stage, stage_bytes, stream);
+    return loss3_bwd(false, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, C3, u_hist, v_hist,
+                     nits, nullptr, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream);
 }
 
 // ---- the same with the fused solve + sweep (kccot_sinkhorn_divergence_fused_f32) ----------------------------------
@@ -80,11 +112,8 @@ extern "C" int kccot_sinkhorn_loss_fused_fwd_f32(const float* real, const float*
     if (ws_bytes < kccot_sinkhorn_loss_workspace_bytes(B, K) || (!ws && ws_bytes))
         return fail(KCCOT_EWORKSPACE, "sinkhorn_loss_fused_fwd: workspace %zu < %zu bytes", ws_bytes,
                     kccot_sinkhorn_loss_workspace_bytes(B, K));
-    int rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes,
-                                      stream);
-    if (rc) return rc;
-    return kccot_sinkhorn_divergence_fused_f32(C3, B, eps, L, Lmin, thresh, cost3_out, nits_out, loss_out, ticket, dC3_unit,
-                                               stream);
+    return loss3_fwd(false, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, Lmin, thresh, flags, C3,
+                     nullptr, nullptr, dC3_unit, cost3_out, nits_out, loss_out, ticket, ws, ws_bytes, stream);
 }
 
 extern "C" int kccot_sinkhorn_loss_fused_bwd_f32(const float* gloss, const float* dC3_unit, const float* real,
@@ -93,6 +122,56 @@ extern "C" int kccot_sinkhorn_loss_fused_bwd_f32(const float* gloss, const float
                                                  float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake,
                                                  void* ws, size_t ws_bytes, kccot_stream_t stream) {
     if (!gloss || !dC3_unit) return fail(KCCOT_EINVAL, "sinkhorn_loss_fused_bwd: null pointer");
-    return kccot_pairwise_cost3_bwd_scaled_f32(dC3_unit, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J,
-                                               dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream);
+    return loss3_bwd(false, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, 0.f, 0, nullptr, nullptr,
+                     nullptr, nullptr, dC3_unit, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream);
+}
+
+// ---- the bi-causal loss (bicausal.hip) -------------------------------------------------------------------------------
+extern "C" size_t kccot_bicausal_sinkhorn_loss_workspace_bytes(int B, int64_t K) {
+    // the one-batch loss's layout: dC3 [3,B,B] + 3 floats of the history backward, then one stage at a time
+    return kccot_sinkhorn_loss_workspace_bytes(B, K);
+}
+
+extern "C" int kccot_bicausal_sinkhorn_loss_fwd_f32(const float* real, const float* fake, int B, int64_t K, float sc,
+                                                    const float* h_fake, const float* h_real, const float* m_real,
+                                                    const float* m_fake, int T, int J, float eps, int L, int Lmin,
+                                                    float thresh, unsigned flags, float* C3, float* u_hist, float* v_hist,
+                                                    float* dC3_unit, float* cost3_out, int32_t* nits_out, float* loss_out,
+                                                    int32_t* ticket, void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    if (!real || !fake || !h_fake || !h_real || !m_real || !m_fake)
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: null input pointer");
+    if (!C3 || !cost3_out || !nits_out || !loss_out || !ticket)
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: null output pointer");
+    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: bad arguments B=%d K=%lld T=%d J=%d L=%d eps=%g", B,
+                    (long long)K, T, J, L, (double)eps);
+    if ((u_hist == nullptr) != (v_hist == nullptr) || (dC3_unit && u_hist))
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: give u_hist and v_hist together, or dC3_unit, not both");
+    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS))
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_fwd: the Gram-sum split flags do not apply");
+    if (!ws || ws_bytes < kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K))
+        return fail(KCCOT_EWORKSPACE, "bicausal_sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
+                    kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K));
+    return loss3_fwd(true, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, Lmin, thresh, flags, C3,
+                     u_hist, v_hist, dC3_unit, cost3_out, nits_out, loss_out, ticket, ws, ws_bytes, stream);
+}
+
+extern "C" int kccot_bicausal_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const float* fake, int B,
+                                                    int64_t K, float sc, const float* h_fake, const float* h_real,
+                                                    const float* m_real, const float* m_fake, int T, int J, float eps,
+                                                    int L, const float* C3, const float* u_hist, const float* v_hist,
+                                                    const int32_t* nits, const float* dC3_unit, float* dfake,
+                                                    float* dh_fake, float* dh_real, float* dm_real, float* dm_fake,
+                                                    void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake)
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_bwd: null input pointer");
+    if (!dC3_unit && (!C3 || !u_hist || !v_hist || !nits))
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_bwd: give dC3_unit (fused forward) or C3, u_hist, v_hist, nits");
+    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
+        return fail(KCCOT_EINVAL, "bicausal_sinkhorn_loss_bwd: bad arguments B=%d K=%lld T=%d J=%d", B, (long long)K, T, J);
+    if (!ws || ws_bytes < kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K))
+        return fail(KCCOT_EWORKSPACE, "bicausal_sinkhorn_loss_bwd: workspace %zu < %zu bytes", ws_bytes,
+                    kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K));
+    return loss3_bwd(true, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, C3, u_hist, v_hist,
+                     nits, dC3_unit, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream);
 }

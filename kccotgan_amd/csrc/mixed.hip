@@ -143,8 +143,6 @@ __global__ void mixed_sinkhorn_combine_bwd(const float* __restrict__ gloss, floa
     }
 }
 
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static bool mix_shape_ok(int B, int64_t K, int T, int J) {
     return B > 0 && K > 0 && T >= 1 && J >= 1 && (int64_t)B * 2 <= (1 << 20);
 }

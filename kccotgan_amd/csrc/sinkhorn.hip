@@ -856,11 +856,6 @@ using namespace kccot;
 // option "sinkhorn_shortcut" = 0: always execute every iteration (bench headline, bitwise-equality tests)
 static int sink_shortcut_enabled() { return opt(OPT_SK_SHORTCUT); }
 
-// set by the *_divergence_* entry points around their call into the base functions
-static thread_local float* g_div_loss = nullptr;
-static thread_local int* g_div_ticket = nullptr;
-static thread_local int g_div_weights = 0;
-
 extern "C" size_t kccot_sinkhorn_workspace_bytes(int nprob, int n) {
     if (nprob <= 0 || n <= SK_MAXN) return 0;   // the register-resident kernels need none
     return sinkhorn_gen_workspace_bytes(nprob, n);
@@ -885,10 +880,11 @@ extern "C" size_t kccot_sinkhorn_workspace_bytes(int nprob, int n) {
         }                                                                                      \
     }
 
-extern "C" int kccot_sinkhorn_fwd_f32(const float* C, int nprob, int n, float eps, int L, int Lmin,
-                                      float thresh, int stop_mode, float* u_hist, float* v_hist,
-                                      float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
-                                      size_t ws_bytes, kccot_stream_t stream) {
+// div_loss / div_ticket: the loss and the arrival counter of the divergence forward's in-kernel combine
+// (kccot_sinkhorn_divergence_fwd_f32); null for the plain solves
+static int sinkhorn_fwd(const float* C, int nprob, int n, float eps, int L, int Lmin, float thresh, int stop_mode,
+                        float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
+                        size_t ws_bytes, kccot_stream_t stream, float* div_loss, int* div_ticket) {
     if (!C || !cost_out || !nits_out) return fail(KCCOT_EINVAL, "sinkhorn_fwd: null pointer");
     if (nprob <= 0 || n <= 0 || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "sinkhorn_fwd: bad arguments nprob=%d n=%d L=%d eps=%g", nprob, n, L, (double)eps);
@@ -901,7 +897,7 @@ extern "C" int kccot_sinkhorn_fwd_f32(const float* C, int nprob, int n, float ep
                                        pi_out, ws, ws_bytes, (hipStream_t)stream);
     SinkGeom g = sink_geom(n, true);
     SinkArgs a{C, n, L, Lmin, stop_mode, eps, (float)(1.0 / (double)eps), thresh, u_hist, v_hist, cost_out, nits_out, pi_out,
-               nullptr, g_div_loss, g_div_ticket, sink_shortcut_enabled()};
+               nullptr, div_loss, div_ticket, sink_shortcut_enabled()};
 #ifdef KCCOT_DIAG
     a.diag = static_cast<unsigned long long*>(ws);   // diagnostic build: ws carries the stamp buffer
 #endif
@@ -912,6 +908,14 @@ extern "C" int kccot_sinkhorn_fwd_f32(const float* C, int nprob, int n, float ep
         KCCOT_SK_DISPATCH(sinkhorn_fwd_reg_full, a, g, nprob, st)
     }
     return launch_status("sinkhorn_fwd_reg");
+}
+
+extern "C" int kccot_sinkhorn_fwd_f32(const float* C, int nprob, int n, float eps, int L, int Lmin,
+                                      float thresh, int stop_mode, float* u_hist, float* v_hist,
+                                      float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
+                                      size_t ws_bytes, kccot_stream_t stream) {
+    return sinkhorn_fwd(C, nprob, n, eps, L, Lmin, thresh, stop_mode, u_hist, v_hist, cost_out, nits_out, pi_out, ws,
+                        ws_bytes, stream, nullptr, nullptr);
 }
 
 extern "C" int kccot_sinkhorn_status(const int32_t* nits, int nprob, kccot_stream_t stream) {
@@ -928,10 +932,11 @@ extern "C" int kccot_sinkhorn_status(const int32_t* nits, int nprob, kccot_strea
     return 0;
 }
 
-extern "C" int kccot_sinkhorn_bwd_f32(const float* C, const float* u_hist, const float* v_hist,
-                                      const int32_t* nits, int nprob, int n, float eps, int L,
-                                      const float* gcost, float* dC_out, void* ws, size_t ws_bytes,
-                                      kccot_stream_t stream) {
+// div_weights = 1: gcost is ONE float dLoss/dloss and the sweep applies the weights {2,-1,-1} of the divergence
+// (kccot_sinkhorn_divergence_bwd_f32); 0: gcost holds one float per problem
+static int sinkhorn_bwd(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
+                        float eps, int L, const float* gcost, float* dC_out, void* ws, size_t ws_bytes,
+                        kccot_stream_t stream, int div_weights) {
     if (!C || !u_hist || !v_hist || !nits || !gcost || !dC_out)
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: null pointer");
     if (nprob <= 0 || n <= 0 || L < 0 || !(eps > 0.f))
@@ -940,10 +945,17 @@ extern "C" int kccot_sinkhorn_bwd_f32(const float* C, const float* u_hist, const
         return launch_sinkhorn_bwd_gen(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes,
                                        (hipStream_t)stream);
     SinkGeom g = sink_geom(n, false);
-    SinkBwdArgs a{C, u_hist, v_hist, nits, gcost, dC_out, n, L, eps, (float)(1.0 / (double)eps), g_div_weights};
+    SinkBwdArgs a{C, u_hist, v_hist, nits, gcost, dC_out, n, L, eps, (float)(1.0 / (double)eps), div_weights};
     hipStream_t st = (hipStream_t)stream;
     KCCOT_SK_DISPATCH(sinkhorn_bwd_reg, a, g, nprob, st)
     return launch_status("sinkhorn_bwd_reg");
+}
+
+extern "C" int kccot_sinkhorn_bwd_f32(const float* C, const float* u_hist, const float* v_hist,
+                                      const int32_t* nits, int nprob, int n, float eps, int L,
+                                      const float* gcost, float* dC_out, void* ws, size_t ws_bytes,
+                                      kccot_stream_t stream) {
+    return sinkhorn_bwd(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes, stream, 0);
 }
 
 extern "C" int kccot_mixed_divergence_fwd_f32(const float* cost3, float* loss_out, kccot_stream_t stream) {
@@ -1048,11 +1060,8 @@ extern "C" int kccot_sinkhorn_divergence_fwd_f32(const float* C3, int n, float e
         if (rc) return rc;
         return kccot_mixed_divergence_fwd_f32(cost3_out, loss_out, stream);
     }
-    g_div_loss = loss_out; g_div_ticket = reinterpret_cast<int*>(ticket);
-    int rc = kccot_sinkhorn_fwd_f32(C3, 3, n, eps, L, Lmin, thresh, KCCOT_STOP_COUNT, u_hist, v_hist, cost3_out, nits_out,
-                                    nullptr, ws, ws_bytes, stream);
-    g_div_loss = nullptr; g_div_ticket = nullptr;
-    return rc;
+    return sinkhorn_fwd(C3, 3, n, eps, L, Lmin, thresh, KCCOT_STOP_COUNT, u_hist, v_hist, cost3_out, nits_out, nullptr, ws,
+                        ws_bytes, stream, loss_out, reinterpret_cast<int*>(ticket));
 }
 
 // gloss: ONE device float dLoss/dloss; dC3_out = d loss / d C3 scaled by it.
@@ -1061,8 +1070,5 @@ extern "C" int kccot_sinkhorn_divergence_bwd_f32(const float* C3, const float* u
                                                  float* dC3_out, void* ws, size_t ws_bytes, kccot_stream_t stream) {
     if (!gloss) return fail(KCCOT_EINVAL, "sinkhorn_divergence_bwd: null pointer");
     if (n > SK_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_divergence_bwd: use mixed_divergence_bwd + sinkhorn_bwd for n > %d", SK_MAXN);
-    g_div_weights = 1;
-    int rc = kccot_sinkhorn_bwd_f32(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3_out, ws, ws_bytes, stream);
-    g_div_weights = 0;
-    return rc;
+    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3_out, ws, ws_bytes, stream, 1);
 }

@@ -195,36 +195,12 @@ class HipOps:
     @staticmethod
     def divergence_fwd(C3, eps, L):
         """The three solves AND 2 xy - xx - yy in one launch (n <= 128; larger n: two launches inside the library)."""
-        from .gan_utils import _ticket
-        _, n, _ = C3.shape
-        dev = C3.device
-        Lh = max(int(L), 1)
-        u_hist = _lib.empty((3, Lh, n), torch.float32, dev)
-        v_hist = _lib.empty((3, Lh, n), torch.float32, dev)
-        small = _lib.empty((4,), torch.float32, dev)             # cost3 | loss
-        nits = _lib.empty((6,), torch.int32, dev)
-        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(3, n), C3)
-        check(lib.kccot_sinkhorn_divergence_fwd_f32(ptr(C3), n, float(eps), int(L), _LMIN, _THRESH, ptr(u_hist), ptr(v_hist),
-                                                    ptr(small), ptr(nits), ptr(small[3:]), ptr(_ticket(dev)), ws, wsb,
-                                                    stream_of(C3)), "sinkhorn_divergence_fwd")
-        return small[3:].reshape(()), (C3, u_hist, v_hist, nits, float(eps), Lh)
+        small, _, saved = gan_utils._divergence_fwd(C3, eps, L, _LMIN)
+        return small[3:].reshape(()), saved
 
     @staticmethod
     def divergence_bwd(saved, g):
-        C3, u_hist, v_hist, nits, eps, Lh = saved
-        _, n, _ = C3.shape
-        g = g.reshape(1).contiguous().float()
-        dC3 = _lib.empty_like(C3)
-        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(3, n), C3)
-        if n > 128:      # streaming / cooperative solvers: weights first, then the generic reverse sweep
-            gc = _lib.empty((3,), torch.float32, g.device)
-            check(lib.kccot_mixed_divergence_bwd_f32(ptr(g), ptr(gc), stream_of(g)), "mixed_divergence_bwd")
-            check(lib.kccot_sinkhorn_bwd_f32(ptr(C3), ptr(u_hist), ptr(v_hist), ptr(nits), 3, n, eps, Lh, ptr(gc), ptr(dC3),
-                                             ws, wsb, stream_of(C3)), "sinkhorn_bwd")
-        else:
-            check(lib.kccot_sinkhorn_divergence_bwd_f32(ptr(C3), ptr(u_hist), ptr(v_hist), ptr(nits), n, eps, Lh, ptr(g),
-                                                        ptr(dC3), ws, wsb, stream_of(C3)), "sinkhorn_divergence_bwd")
-        return dC3
+        return gan_utils._divergence_bwd(saved, g)
 
     @staticmethod
     def cost3_bwd_rows(dC3, real, fake, h_fake, h_real, m_real, m_fake, sc, row_begin, row_count):

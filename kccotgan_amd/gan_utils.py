@@ -8,6 +8,8 @@ unrolled Sinkhorn loop with tf.GradientTape, kernel_train.py:221,252,262,289).
 
 There is no CPU path: tensors must live on the GPU and the library must be built.
 """
+import collections
+
 import torch
 
 from . import _lib
@@ -206,278 +208,181 @@ def _ticket(device):
     return t
 
 
+def _divergence_fwd(C3, eps, L, Lmin):
+    """The three solves of C3 [3,n,n] AND 2 xy - xx - yy (gan_utils.py:221-225): one launch at n <= 128, two inside the
+    library above.  Returns (cost3 | loss, nits, what _divergence_bwd needs)."""
+    _, n, _ = C3.shape
+    dev = C3.device
+    Lh = max(int(L), 1)
+    u_hist = _lib.empty((3, Lh, n), torch.float32, dev)
+    v_hist = _lib.empty((3, Lh, n), torch.float32, dev)
+    small = _lib.empty((4,), torch.float32, dev)                                     # cost3 | loss
+    nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
+    ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(3, n), C3)
+    check(lib.kccot_sinkhorn_divergence_fwd_f32(ptr(C3), n, float(eps), int(L), int(Lmin), _THRESH, ptr(u_hist),
+                                                ptr(v_hist), ptr(small), ptr(nits), ptr(small[3:]), ptr(_ticket(dev)),
+                                                ws, wsb, stream_of(C3)), "sinkhorn_divergence_fwd")
+    return small, nits, (C3, u_hist, v_hist, nits, float(eps), Lh)
+
+
+def _divergence_bwd(saved, g):
+    """d loss / d C3 scaled by the upstream scalar g, from what _divergence_fwd saved."""
+    C3, u_hist, v_hist, nits, eps, Lh = saved
+    _, n, _ = C3.shape
+    g = g.reshape(1).contiguous().float()
+    dC3 = _lib.empty_like(C3)
+    ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(3, n), C3)
+    if n > 128:   # streaming / cooperative solvers: weights first, then the generic reverse sweep
+        gc = _lib.empty((3,), torch.float32, g.device)
+        check(lib.kccot_mixed_divergence_bwd_f32(ptr(g), ptr(gc), stream_of(g)), "mixed_divergence_bwd")
+        check(lib.kccot_sinkhorn_bwd_f32(ptr(C3), ptr(u_hist), ptr(v_hist), ptr(nits), 3, n, eps, Lh, ptr(gc), ptr(dC3),
+                                         ws, wsb, stream_of(C3)), "sinkhorn_bwd")
+    else:
+        check(lib.kccot_sinkhorn_divergence_bwd_f32(ptr(C3), ptr(u_hist), ptr(v_hist), ptr(nits), n, eps, Lh, ptr(g),
+                                                    ptr(dC3), ws, wsb, stream_of(C3)), "sinkhorn_divergence_bwd")
+    return dC3
+
+
 class _SinkhornDivergence(torch.autograd.Function):
     """loss = 2 W(C3[0]) - W(C3[1]) - W(C3[2]) in one launch each way (gan_utils.py:221-225)."""
 
     @staticmethod
     def forward(ctx, C3, eps, L, Lmin, tag):
-        _, n, _ = C3.shape
-        C3 = C3.contiguous()
-        dev = C3.device
-        Lh = max(int(L), 1)
-        u_hist = _lib.empty((3, Lh, n), torch.float32, dev)
-        v_hist = _lib.empty((3, Lh, n), torch.float32, dev)
-        cost = _lib.empty((3,), torch.float32, dev)
-        nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
-        loss = _lib.empty((1,), torch.float32, dev)
-        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(3, n), C3)
-        check(lib.kccot_sinkhorn_divergence_fwd_f32(ptr(C3), n, float(eps), int(L), int(Lmin), _THRESH, ptr(u_hist),
-                                                    ptr(v_hist), ptr(cost), ptr(nits), ptr(loss), ptr(_ticket(dev)),
-                                                    ws, wsb, stream_of(C3)), "sinkhorn_divergence_fwd")
+        small, nits, saved = _divergence_fwd(C3.contiguous(), eps, L, Lmin)
         last_info[tag], last_info[tag + "_executed"] = nits[:3], nits[3:]
-        last_info[tag + "_costs"] = cost
-        ctx.save_for_backward(C3, u_hist, v_hist, nits)
-        ctx.eps, ctx.Lh = float(eps), Lh
-        return loss.reshape(())
+        last_info[tag + "_costs"] = small[:3]
+        ctx.save_for_backward(*saved[:4])
+        ctx.eps, ctx.Lh = saved[4:]
+        return small[3:].reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        C3, u_hist, v_hist, nits = ctx.saved_tensors
-        _, n, _ = C3.shape
-        g = g.reshape(1).contiguous().float()
-        dC = _lib.empty_like(C3)
-        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(3, n), C3)
-        if n > 128:   # streaming solver: separate combine
-            gc = _lib.empty((3,), torch.float32, g.device)
-            check(lib.kccot_mixed_divergence_bwd_f32(ptr(g), ptr(gc), stream_of(g)), "mixed_divergence_bwd")
-            check(lib.kccot_sinkhorn_bwd_f32(ptr(C3), ptr(u_hist), ptr(v_hist), ptr(nits), 3, n, ctx.eps, ctx.Lh,
-                                             ptr(gc), ptr(dC), ws, wsb, stream_of(C3)), "sinkhorn_bwd")
-        else:
-            check(lib.kccot_sinkhorn_divergence_bwd_f32(ptr(C3), ptr(u_hist), ptr(v_hist), ptr(nits), n, ctx.eps, ctx.Lh,
-                                                        ptr(g), ptr(dC), ws, wsb, stream_of(C3)), "sinkhorn_divergence_bwd")
-        return dC, None, None, None, None
+        return _divergence_bwd((*ctx.saved_tensors, ctx.eps, ctx.Lh), g), None, None, None, None
 
 
 def _pad64(n):
     return (n + 63) & ~63
 
 
+# The loss entry points of one loss, called with the pointer arguments _SinkhornLoss assembles:
+#   fwd(head, u_hist, v_hist, dC_unit, tail)
+#       head = (real, fake, B, K, sc, *features, T, J, eps, L, Lmin, thresh, flags, C)
+#       tail = (costs, nits, loss, ticket, ws, ws_bytes, stream)
+#   bwd(gloss, inputs, hist, dC_unit, outs)
+#       inputs = (real, fake, B, K, sc, *features, T, J), hist = (eps, L, C, u_hist, v_hist, nits),
+#       outs = (dfake, *dfeatures, ws, ws_bytes, stream)
+# The fused path (solves + reverse sweep in one launch) passes dC_unit and null history; the history path the reverse.
+# P problems, stack videos per operand ([x; x'] for the mixed loss), key: the last_info name of the matrices.
+_LossSpec = collections.namedtuple("_LossSpec", "P stack ws_bytes fwd bwd key shape_error")
+
+
+def _one_fwd(head, uh, vh, dCu, tail):
+    if dCu is not None:
+        check(lib.kccot_sinkhorn_loss_fused_fwd_f32(*head, dCu, *tail), "sinkhorn_loss_fused_fwd")
+    else:
+        check(lib.kccot_sinkhorn_loss_fwd_f32(*head, uh, vh, *tail), "sinkhorn_loss_fwd")
+
+
+def _one_bwd(g, inputs, hist, dCu, outs):
+    if dCu is not None:
+        check(lib.kccot_sinkhorn_loss_fused_bwd_f32(g, dCu, *inputs, *outs), "sinkhorn_loss_fused_bwd")
+    else:
+        check(lib.kccot_sinkhorn_loss_bwd_f32(g, *inputs, *hist, *outs), "sinkhorn_loss_bwd")
+
+
+_ONE_BATCH = _LossSpec(3, 1, lib.kccot_sinkhorn_loss_workspace_bytes, _one_fwd, _one_bwd, "_C3",
+                       "real and fake must have the same shape: {} vs {}")
+_BICAUSAL = _LossSpec(
+    3, 1, lib.kccot_bicausal_sinkhorn_loss_workspace_bytes,
+    lambda head, uh, vh, dCu, tail: check(lib.kccot_bicausal_sinkhorn_loss_fwd_f32(*head, uh, vh, dCu, *tail),
+                                          "bicausal_sinkhorn_loss_fwd"),
+    lambda g, inputs, hist, dCu, outs: check(lib.kccot_bicausal_sinkhorn_loss_bwd_f32(g, *inputs, *hist, dCu, *outs),
+                                             "bicausal_sinkhorn_loss_bwd"),
+    "_C3", "real and fake must have the same shape: {} vs {}")
+_MIXED = _LossSpec(
+    4, 2, lib.kccot_mixed_sinkhorn_loss_workspace_bytes,
+    lambda head, uh, vh, dCu, tail: check(lib.kccot_mixed_sinkhorn_loss_fwd_f32(*head, uh, vh, dCu, *tail),
+                                          "mixed_sinkhorn_loss_fwd"),
+    lambda g, inputs, hist, dCu, outs: check(lib.kccot_mixed_sinkhorn_loss_bwd_f32(g, *inputs, *hist, dCu, *outs),
+                                             "mixed_sinkhorn_loss_bwd"),
+    "_Cmix", "the four videos must have the same shape")
+
+
 class _SinkhornLoss(torch.autograd.Function):
-    """compute_sinkhorn_loss as ONE library call each way (kccot_sinkhorn_loss_{fwd,bwd}_f32): cost
-    assembly + the three solves + their combination; reverse sweep + cost backward.  Same kernels as
-    _Cost3 followed by _SinkhornDivergence, a third of the host work."""
+    """A Sinkhorn loss of ``spec`` (_ONE_BATCH, _BICAUSAL or _MIXED) as ONE library call each way: the cost matrices, the
+    P solves + their combination, and back.  When a gradient is wanted and the dual history fits the CU's LDS
+    (kccot_sinkhorn_fused_eligible: configs[0], configs[1]) the solves and the reverse sweep are ONE launch: no history
+    leaves the CU, the state kept for backward is d loss / d C at dLoss = 1 and backward is coefficient build + video
+    gradient only.  Otherwise the dual history path.  Same kernels as _Cost3 followed by _SinkhornDivergence for the
+    one-batch loss, a third of the host work."""
 
     @staticmethod
-    def forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc, eps, L, Lmin, tag):
-        B, K = real.shape
-        if fake.shape != real.shape:
-            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        for t in (h_fake, h_real, m_real, m_fake):
-            if tuple(t.shape) != (B, T, J):
+    def forward(ctx, spec, tag, sc, eps, L, Lmin, real, fake, *feats):
+        rows, K = real.shape
+        B = rows // spec.stack
+        if fake.shape != real.shape or rows % spec.stack:
+            raise ValueError(spec.shape_error.format(tuple(real.shape), tuple(fake.shape)))
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        for t in feats:
+            if t.shape != (B, T, J):
                 raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        if ctx.needs_input_grad[0]:
+        need = ctx.needs_input_grad[6:]                                             # real, fake, *feats
+        if need[0]:
             raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
                                       "use compute_sinkhorn for a gradient w.r.t. both operands")
-        dev = real.device
-        keep = any(ctx.needs_input_grad[1:6])
+        P, dev = spec.P, real.device
+        keep = any(need[1:])
         Lh = max(int(L), 1)
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
-        small = _lib.empty((4,), torch.float32, dev)                                 # cost3 | loss
-        nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
-        ws, wsb = workspace(lib.kccot_sinkhorn_loss_workspace_bytes(B, K), real)
-        # With a gradient wanted and the dual history small enough for the CU's LDS (configs[0], configs[1]) the solves
-        # and the reverse sweep are ONE launch: no history leaves the CU, the state kept for backward is d loss / d C3
-        # at dLoss = 1 (12 B^2 bytes) and backward is coefficient build + video gradient only.
+        nc, nh = _pad64(P * B * B), _pad64(P * Lh * B)
+        small = _lib.empty((P + 1,), torch.float32, dev)                             # costs | loss
+        nits = _lib.empty((2 * P,), torch.int32, dev)       # [reference-equivalent counts | iterations executed]
+        st = stream_of(real)
+        ws, wsb = workspace(spec.ws_bytes(B, K), real, st)
         fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
         if fused:
-            state = _lib.empty((2 * nc,), torch.float32, dev)                        # C3 | dC3 at dLoss = 1
-            C3 = state[:nc]
-            check(lib.kccot_sinkhorn_loss_fused_fwd_f32(ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real),
-                                                        ptr(m_real), ptr(m_fake), T, J, float(eps), int(L), int(Lmin),
-                                                        _THRESH, cost_flags, ptr(C3), ptr(state[nc:]), ptr(small),
-                                                        ptr(nits), ptr(small[3:]), ptr(_ticket(dev)), ws, wsb,
-                                                        stream_of(real)), "sinkhorn_loss_fused_fwd")
-        else:
-            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # C3 | u_hist | v_hist
-            C3 = state[:nc]
-            uh, vh = (state[nc:nc + nh], state[nc + nh:]) if keep else (None, None)
-            check(lib.kccot_sinkhorn_loss_fwd_f32(ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real), ptr(m_real),
-                                                  ptr(m_fake), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
-                                                  ptr(C3), ptr(uh), ptr(vh), ptr(small), ptr(nits), ptr(small[3:]),
-                                                  ptr(_ticket(dev)), ws, wsb, stream_of(real)), "sinkhorn_loss_fwd")
-        last_info[tag], last_info[tag + "_executed"] = nits[:3], nits[3:]
-        last_info[tag + "_costs"] = small[:3]
-        last_info[tag + "_C3"] = C3[:3 * B * B].view(3, B, B)
-        last_info[tag + "_fused_sweep"] = fused
-        if keep:
-            ctx.save_for_backward(real, fake, h_fake, h_real, m_real, m_fake, state, nits)
-        ctx.cfg = (float(sc), float(eps), Lh, fused)
-        return small[3:].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        real, fake, h_fake, h_real, m_real, m_fake, state, nits = ctx.saved_tensors
-        sc, eps, Lh, fused = ctx.cfg
-        B, K = real.shape
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
-        need = ctx.needs_input_grad
-        g = g.reshape(1).contiguous().float()
-        dfake = _lib.empty_like(fake) if need[1] else None
-        feats = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[2:6]) else None
-        dhf, dhr, dmr, dmf = ((feats[i] if need[2 + i] else None) for i in range(4))
-        ws, wsb = workspace(lib.kccot_sinkhorn_loss_workspace_bytes(B, K), real)
-        if fused:
-            check(lib.kccot_sinkhorn_loss_fused_bwd_f32(ptr(g), ptr(state[nc:]), ptr(real), ptr(fake), B, K, sc, ptr(h_fake),
-                                                        ptr(h_real), ptr(m_real), ptr(m_fake), T, J, ptr(dfake), ptr(dhf),
-                                                        ptr(dhr), ptr(dmr), ptr(dmf), ws, wsb, stream_of(real)),
-                  "sinkhorn_loss_fused_bwd")
-        else:
-            check(lib.kccot_sinkhorn_loss_bwd_f32(ptr(g), ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real), ptr(m_real),
-                                                  ptr(m_fake), T, J, eps, Lh, ptr(state[:nc]), ptr(state[nc:nc + nh]),
-                                                  ptr(state[nc + nh:]), ptr(nits), ptr(dfake), ptr(dhf), ptr(dhr), ptr(dmr),
-                                                  ptr(dmf), ws, wsb, stream_of(real)), "sinkhorn_loss_bwd")
-        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
-
-
-class _BicausalSinkhornLoss(torch.autograd.Function):
-    """compute_bicausal_sinkhorn_loss as ONE library call each way (kccot_bicausal_sinkhorn_loss_{fwd,bwd}_f32): the three
-    bi-causal cost matrices, the three solves + 2 W_xy - W_xx - W_yy, and back.  Fused solve + sweep when a gradient is
-    wanted and the shape is eligible, the dual history path otherwise."""
-
-    @staticmethod
-    def forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc, eps, L, Lmin, tag):
-        B, K = real.shape
-        if fake.shape != real.shape:
-            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        for t in (h_fake, h_real, m_real, m_fake):
-            if tuple(t.shape) != (B, T, J):
-                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
-                                      "use compute_sinkhorn for a gradient w.r.t. both operands")
-        dev = real.device
-        keep = any(ctx.needs_input_grad[1:6])
-        Lh = max(int(L), 1)
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
-        small = _lib.empty((4,), torch.float32, dev)                                 # cost3 | loss
-        nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
-        ws, wsb = workspace(lib.kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K), real)
-        fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
-        if fused:
-            state = _lib.empty((2 * nc,), torch.float32, dev)                        # C3 | dC3 at dLoss = 1
+            state = _lib.empty((2 * nc,), torch.float32, dev)                        # C | dC at dLoss = 1
             uh = vh = None
-            dCu = state[nc:]
+            dCu = ptr(state[nc:])
         else:
-            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # C3 | u_hist | v_hist
-            uh, vh = (state[nc:nc + nh], state[nc + nh:]) if keep else (None, None)
+            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # C | u_hist | v_hist
+            uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
             dCu = None
-        C3 = state[:nc]
-        check(lib.kccot_bicausal_sinkhorn_loss_fwd_f32(ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real), ptr(m_real),
-                                                       ptr(m_fake), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
-                                                       ptr(C3), ptr(uh), ptr(vh), ptr(dCu), ptr(small), ptr(nits),
-                                                       ptr(small[3:]), ptr(_ticket(dev)), ws, wsb, stream_of(real)),
-              "bicausal_sinkhorn_loss_fwd")
-        last_info[tag], last_info[tag + "_executed"] = nits[:3], nits[3:]
-        last_info[tag + "_costs"] = small[:3]
-        last_info[tag + "_C3"] = C3[:3 * B * B].view(3, B, B)
+        loss = small[P:]
+        spec.fwd((ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH,
+                  cost_flags, ptr(state)), uh, vh, dCu,
+                 (ptr(small), ptr(nits), ptr(loss), ptr(_ticket(dev)), ws, wsb, st))
+        last_info[tag], last_info[tag + "_executed"] = nits[:P], nits[P:]
+        last_info[tag + "_costs"] = small[:P]
+        last_info[tag + spec.key] = state[:P * B * B].view(P, B, B)
         last_info[tag + "_fused_sweep"] = fused
         if keep:
-            ctx.save_for_backward(real, fake, h_fake, h_real, m_real, m_fake, state, nits)
-        ctx.cfg = (float(sc), float(eps), Lh, fused)
-        return small[3:].reshape(())
+            ctx.save_for_backward(real, fake, *feats, state, nits)
+        ctx.spec, ctx.cfg = spec, (float(sc), float(eps), Lh, fused)
+        return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        real, fake, h_fake, h_real, m_real, m_fake, state, nits = ctx.saved_tensors
-        sc, eps, Lh, fused = ctx.cfg
-        B, K = real.shape
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
-        need = ctx.needs_input_grad
+        real, fake, *feats, state, nits = ctx.saved_tensors
+        spec, (sc, eps, Lh, fused) = ctx.spec, ctx.cfg
+        P, nf = spec.P, len(feats)
+        rows, K = real.shape
+        B = rows // spec.stack
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        nc, nh = _pad64(P * B * B), _pad64(P * Lh * B)
+        need = ctx.needs_input_grad[7:]                                             # fake, *feats
         g = g.reshape(1).contiguous().float()
-        dfake = _lib.empty_like(fake) if need[1] else None
-        feats = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[2:6]) else None
-        dhf, dhr, dmr, dmf = ((feats[i] if need[2 + i] else None) for i in range(4))
-        ws, wsb = workspace(lib.kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K), real)
+        dfake = _lib.empty_like(fake) if need[0] else None
+        df = _lib.empty((nf, B, T, J), torch.float32, real.device) if any(need[1:]) else None
+        dfeats = [(df[i] if need[1 + i] else None) for i in range(nf)]
+        st = stream_of(real)
+        ws, wsb = workspace(spec.ws_bytes(B, K), real, st)
         if fused:
-            C3 = uh = vh = nt = None
-            dCu = state[nc:]
+            hist, dCu = (eps, Lh, None, None, None, None), ptr(state[nc:])
         else:
-            C3, uh, vh, nt, dCu = state[:nc], state[nc:nc + nh], state[nc + nh:], nits, None
-        check(lib.kccot_bicausal_sinkhorn_loss_bwd_f32(ptr(g), ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real),
-                                                       ptr(m_real), ptr(m_fake), T, J, eps, Lh, ptr(C3), ptr(uh), ptr(vh),
-                                                       ptr(nt), ptr(dCu), ptr(dfake), ptr(dhf), ptr(dhr), ptr(dmr), ptr(dmf),
-                                                       ws, wsb, stream_of(real)), "bicausal_sinkhorn_loss_bwd")
-        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
-
-
-class _MixedSinkhornLoss(torch.autograd.Function):
-    """compute_mixed_sinkhorn_loss as ONE library call each way (kccot_mixed_sinkhorn_loss_{fwd,bwd}_f32): the stacked cost
-    assembly R = [x; x'], F = [y; y'] + the four cost blocks, the four solves + their combination (W1 + W2) - W3 - W4, and
-    back.  Fused solve + sweep when a gradient is wanted and the shape is eligible, the dual history path otherwise."""
-
-    @staticmethod
-    def forward(ctx, R, F, h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, sc, eps, L, Lmin, tag):
-        B2, K = R.shape
-        B = B2 // 2
-        if F.shape != R.shape or B2 % 2:
-            raise ValueError("the four videos must have the same shape")
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        for t in (h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p):
-            if tuple(t.shape) != (B, T, J):
-                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
-                                      "use compute_sinkhorn for a gradient w.r.t. both operands")
-        dev = R.device
-        keep = any(ctx.needs_input_grad[1:8])
-        Lh = max(int(L), 1)
-        nc, nh = _pad64(4 * B * B), _pad64(4 * Lh * B)
-        small = _lib.empty((5,), torch.float32, dev)                                 # cost4 | loss
-        nits = _lib.empty((8,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
-        ws, wsb = workspace(lib.kccot_mixed_sinkhorn_loss_workspace_bytes(B, K), R)
-        fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
-        if fused:
-            state = _lib.empty((2 * nc,), torch.float32, dev)                        # Cmix | dCmix at dLoss = 1
-            uh = vh = None
-            dCu = state[nc:]
-        else:
-            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # Cmix | u_hist | v_hist
-            uh, vh = (state[nc:nc + nh], state[nc + nh:]) if keep else (None, None)
-            dCu = None
-        Cmix = state[:nc]
-        check(lib.kccot_mixed_sinkhorn_loss_fwd_f32(ptr(R), ptr(F), B, K, sc, ptr(h_fake), ptr(m_real), ptr(h_real_p),
-                                                    ptr(m_fake), ptr(h_fake_p), ptr(m_real_p), T, J, float(eps), int(L),
-                                                    int(Lmin), _THRESH, cost_flags, ptr(Cmix), ptr(uh), ptr(vh), ptr(dCu),
-                                                    ptr(small), ptr(nits), ptr(small[4:]), ptr(_ticket(dev)), ws, wsb,
-                                                    stream_of(R)), "mixed_sinkhorn_loss_fwd")
-        last_info[tag], last_info[tag + "_executed"] = nits[:4], nits[4:]
-        last_info[tag + "_costs"] = small[:4]
-        last_info[tag + "_Cmix"] = Cmix[:4 * B * B].view(4, B, B)
-        last_info[tag + "_fused_sweep"] = fused
-        if keep:
-            ctx.save_for_backward(R, F, h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, state, nits)
-        ctx.cfg = (float(sc), float(eps), Lh, fused)
-        return small[4:].reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        R, F, h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p, state, nits = ctx.saved_tensors
-        sc, eps, Lh, fused = ctx.cfg
-        B2, K = R.shape
-        B = B2 // 2
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        nc, nh = _pad64(4 * B * B), _pad64(4 * Lh * B)
-        need = ctx.needs_input_grad
-        g = g.reshape(1).contiguous().float()
-        dF = _lib.empty_like(F) if need[1] else None
-        feats = _lib.empty((6, B, T, J), torch.float32, R.device) if any(need[2:8]) else None
-        df = [(feats[i] if need[2 + i] else None) for i in range(6)]
-        ws, wsb = workspace(lib.kccot_mixed_sinkhorn_loss_workspace_bytes(B, K), R)
-        if fused:
-            Cmix = uh = vh = nt = None
-            dCu = state[nc:]
-        else:
-            Cmix, uh, vh, nt, dCu = state[:nc], state[nc:nc + nh], state[nc + nh:], nits, None
-        check(lib.kccot_mixed_sinkhorn_loss_bwd_f32(ptr(g), ptr(R), ptr(F), B, K, sc, ptr(h_fake), ptr(m_real),
-                                                    ptr(h_real_p), ptr(m_fake), ptr(h_fake_p), ptr(m_real_p), T, J, eps,
-                                                    Lh, ptr(Cmix), ptr(uh), ptr(vh), ptr(nt), ptr(dCu), ptr(dF),
-                                                    *[ptr(d) for d in df], ws, wsb, stream_of(R)),
-              "mixed_sinkhorn_loss_bwd")
-        return (None, dF, *df, None, None, None, None, None)
+            hist, dCu = (eps, Lh, ptr(state), ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits)), None
+        spec.bwd(ptr(g), (ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J), hist, dCu,
+                 (ptr(dfake), *map(ptr, dfeats), ws, wsb, st))
+        return (None,) * 7 + (dfake, *dfeats)
 
 
 class _MixedDivergence(torch.autograd.Function):
@@ -569,6 +474,13 @@ def scale_invariante_martingale_regularization(M, reg_lam, scaling_coef):
     return _Martingale.apply(_feat(M), float(reg_lam), float(scaling_coef))
 
 
+def _loss_inputs(videos, feats, sinkhorn_eps, sinkhorn_l, honor_eps_l):
+    """Prologue of the compute_*_loss functions: the videos as [B, K] (``video=True`` or not, both layouts flatten the
+    same way), the features as fp32 [B, T, J], and (epsilon, L) = (1.0, 100) unless honor_eps_l (compute_sinkhorn_loss)."""
+    eps, L = (float(sinkhorn_eps), int(sinkhorn_l)) if honor_eps_l else (1.0, 100)
+    return [_flat2(v) for v in videos], [_feat(t) for t in feats], eps, L
+
+
 def compute_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
                           m_fake, video=True, *, honor_eps_l=False):
     """gan_utils.py:204-227: 2*W(real,fake) - W(real,real) - W(fake,fake).
@@ -582,12 +494,10 @@ def compute_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l
     ``video=True`` inputs are [B,H,T,W,C]; the reference's transpose(0,2,1,3,4)+reshape
     (gan_utils.py:217-220) does not change a sum over all of (T,H,W,C), so the buffer is read as is.
     """
-    del video  # both layouts flatten to [B, K]
-    eps, L = (float(sinkhorn_eps), int(sinkhorn_l)) if honor_eps_l else (1.0, 100)
-    real, fake = _flat2(f_real), _flat2(f_fake)
+    vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l,
+                                       honor_eps_l)
     # one library call each way; equivalent to _Cost3 (C3 = [xy, xx, yy]) followed by _SinkhornDivergence
-    return _SinkhornLoss.apply(real, fake, _feat(h_fake), _feat(h_real), _feat(m_real), _feat(m_fake),
-                               float(scaling_coef), eps, L, _LMIN, "compute_sinkhorn_loss")
+    return _SinkhornLoss.apply(_ONE_BATCH, "compute_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats)
 
 
 def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef, sinkhorn_eps, sinkhorn_l,
@@ -608,18 +518,17 @@ def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef
     requires a gradient raises NotImplementedError.  Records last_info["compute_mixed_sinkhorn_loss"] (the four
     reference-equivalent iteration counts), ``..._executed``, ``..._costs`` [4] and ``..._Cmix`` [4,B,B].
     """
-    del video  # both layouts flatten to [B, K]
-    eps, L = (float(sinkhorn_eps), int(sinkhorn_l)) if honor_eps_l else (1.0, 100)
-    vids = [_flat2(v) for v in (f_real, f_fake, f_real_p, f_fake_p)]
+    vids, feats, eps, L = _loss_inputs((f_real, f_fake, f_real_p, f_fake_p),
+                                       (h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p), sinkhorn_eps, sinkhorn_l,
+                                       honor_eps_l)
     if any(v.shape != vids[0].shape for v in vids[1:]):
         raise ValueError("the four videos must have the same shape: %s" % ([tuple(v.shape) for v in vids],))
-    feats = [_feat(t) for t in (h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p)]
     if any(t.shape != feats[0].shape for t in feats[1:]) or feats[0].shape[0] != vids[0].shape[0]:
         raise ValueError("the six features must all be [B,T,J] with the videos' B; got %s" % ([tuple(t.shape) for t in feats],))
     # stacked minibatches (2 B K floats copied); cat's backward hands d[y; y'] back to y and y' as two views
     R = torch.cat([vids[0], vids[2]], 0)
     F = torch.cat([vids[1], vids[3]], 0)
-    return _MixedSinkhornLoss.apply(R, F, *feats, float(scaling_coef), eps, L, _LMIN, "compute_mixed_sinkhorn_loss")
+    return _SinkhornLoss.apply(_MIXED, "compute_mixed_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, R, F, *feats)
 
 
 def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
@@ -640,11 +549,10 @@ def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
     reference-equivalent iteration counts), ``..._executed``, ``..._costs`` [3], ``..._C3`` [3,B,B] and
     ``..._fused_sweep``.
     """
-    del video  # both layouts flatten to [B, K]
-    eps, L = (float(sinkhorn_eps), int(sinkhorn_l)) if honor_eps_l else (1.0, 100)
-    real, fake = _flat2(f_real), _flat2(f_fake)
-    return _BicausalSinkhornLoss.apply(real, fake, _feat(h_fake), _feat(h_real), _feat(m_real), _feat(m_fake),
-                                       float(scaling_coef), eps, L, _LMIN, "compute_bicausal_sinkhorn_loss")
+    vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l,
+                                       honor_eps_l)
+    return _SinkhornLoss.apply(_BICAUSAL, "compute_bicausal_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids,
+                               *feats)
 
 
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):

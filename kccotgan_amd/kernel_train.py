@@ -151,15 +151,7 @@ class KCCOTTrainer:
             fake_pred = self.decoder(preds_features, hidden_z)                   # :224
         real = torch.cat((real_in, real_pred), dim=2)                            # :226
         fake = torch.cat((real_in, fake_pred), dim=2)                            # :227
-        if self.kernel_choice == "1d":                                           # :229-239
-            real = self.gaussian_kernel.temporal_convolution(real, sigma)
-            fake = self.gaussian_kernel.temporal_convolution(fake, sigma)
-        elif self.kernel_choice == "2d":
-            real = self.gaussian_kernel.spatial_convolution(real, sigma)
-            fake = self.gaussian_kernel.spatial_convolution(fake, sigma)
-        elif self.kernel_choice == "3d":
-            real = self.gaussian_kernel.gaussian_convolution3D(real, sigma)
-            fake = self.gaussian_kernel.gaussian_convolution3D(fake, sigma)
+        real, fake = self._smooth(real, sigma), self._smooth(fake, sigma)        # :229-239
         h_fake = self.discriminator_h(fake)                                      # :241-245
         h_real = self.discriminator_h(real)
         m_real = self.discriminator_m(real)
