@@ -47,6 +47,8 @@ extern "C" {
                                       /* are in the workspace -- nothing is written to C3                               */
 #define KCCOT_COST_FROM_GRAM_SUMS 32u /* kccot_pairwise_cost3_f32: only the finalize step, from the sums left in the    */
                                       /* SAME workspace by a GRAM_SUMS_ONLY call (real / fake are not read)             */
+#define KCCOT_COST_BICAUSAL_TERM_ONLY 64u /* kccot_pairwise_cost3_f32: C3 is input AND output -- add the second causal  */
+                                          /* term of the bi-causal loss in place (see below); nothing else is computed  */
 
 /* Sinkhorn stop modes */
 #define KCCOT_STOP_COUNT 0         /* compute_sinkhorn: stop when err<thresh && nits >= Lmin  */
@@ -149,6 +151,18 @@ int kccot_pairwise_cost3_f32(const float* real, const float* fake, int B, int64_
  * kccot_pairwise_cost3_gram_sums_span reports where the sums sit in the workspace (byte offset, number of doubles);
  * 0 doubles = this (B, K) has no Gram path (use the other protocol).  Both calls must use the same B, K, workspace. */
 int kccot_pairwise_cost3_gram_sums_span(int B, int64_t K, size_t* byte_offset, size_t* n_doubles);
+
+/* KCCOT_COST_BICAUSAL_TERM_ONLY turns a one-batch C3 [3,B,B], however it was assembled (one call, the Gram-sum split, the
+ * gathered row blocks of a batch-sharded caller), into the three cost matrices of the bi-causal loss
+ * (kccot_bicausal_sinkhorn_loss_*): in place,
+ *   C3[0] (xy) += causal(h_real, m_fake),   C3[1] (xx) += causal(h_real, m_real),   C3[2] (yy) += causal(h_fake, m_fake)
+ * with causal(h, M)[i,j] = sc sum_{t<T-1,q} h[i,t,q] (M[j,t+1,q] - M[j,t,q]).  xx and yy then carry their causal term
+ * twice (two fp32 additions of the same value, as the reference's bi_causal_modified_cost, gan_utils.py:46-72, adds it).
+ * The launch, its k-chunk order and the order of its partial sums are those of kccot_bicausal_sinkhorn_loss_fwd_f32, so a
+ * C3 assembled by any route receives exactly the fp32 additions the one-call loss applies.  real, fake, K and the
+ * workspace are not read (they may be NULL / 0); the four features are required.  The flag takes no other flag:
+ * combined with SAME, FORCE_*, PARTIAL_ONLY, GRAM_SUMS_ONLY or FROM_GRAM_SUMS the call returns KCCOT_EINVAL, and so do the
+ * loss entry points (kccot_*sinkhorn_loss_fwd_f32) when given it. */
 
 /* Row blocks [row_count, B] of the same three matrices for the batch-sharded caller (kccotgan_amd/dist.py: rank g
  * owns samples [row_begin, row_begin+row_count) of the gathered batch): one launch of the exact direct-difference

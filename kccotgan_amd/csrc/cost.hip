@@ -394,6 +394,18 @@ extern "C" int kccot_pairwise_cost3_f32(const float* real, const float* fake, in
                                         const float* h_fake, const float* h_real, const float* m_real,
                                         const float* m_fake, int T, int J, unsigned flags, float* C3,
                                         void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    if (flags & KCCOT_COST_BICAUSAL_TERM_ONLY) {
+        // the bi-causal loss's second causal terms added to a finished C3 (bicausal.hip): videos and workspace unused
+        if (flags != KCCOT_COST_BICAUSAL_TERM_ONLY)
+            return fail(KCCOT_EINVAL, "pairwise_cost3: BICAUSAL_TERM_ONLY takes no other flag (flags=%u)", flags);
+        if (!C3 || !h_fake || !h_real || !m_real || !m_fake)
+            return fail(KCCOT_EINVAL, "pairwise_cost3: BICAUSAL_TERM_ONLY needs C3 and all four feature tensors");
+        if (B <= 0 || T < 1 || J < 1)
+            return fail(KCCOT_EINVAL, "pairwise_cost3: bad shape B=%d T=%d J=%d", B, T, J);
+        if ((B + 7) / 8 > 65535)     // 8 x 8 output tiles on the y / x grid axes (the y axis caps at 65535)
+            return fail(KCCOT_EUNSUPPORTED, "pairwise_cost3: BICAUSAL_TERM_ONLY supports B <= %d (got %d)", 65535 * 8, B);
+        return launch_bicausal_cost_add(C3, B, h_fake, h_real, m_real, m_fake, T, J, sc, (hipStream_t)stream);
+    }
     if (!real || !fake || !C3) return fail(KCCOT_EINVAL, "pairwise_cost3: null pointer");
     const int nfeat = (h_fake != nullptr) + (h_real != nullptr) + (m_real != nullptr) + (m_fake != nullptr);
     if (nfeat != 0 && nfeat != 4)   // all four (the loss) or none (plain squared distances, e.g. for the RBF kernel)

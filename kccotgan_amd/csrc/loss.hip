@@ -16,6 +16,8 @@ static int loss3_fwd(bool bicausal, const float* real, const float* fake, int B,
                      float thresh, unsigned flags, float* C3, float* u_hist, float* v_hist, float* dC3_unit,
                      float* cost3_out, int32_t* nits_out, float* loss_out, int32_t* ticket, void* ws, size_t ws_bytes,
                      kccot_stream_t stream) {
+    if (flags & KCCOT_COST_BICAUSAL_TERM_ONLY)      // a step of the sharded caller's assembly, not a cost-ladder option
+        return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_BICAUSAL_TERM_ONLY does not apply to a loss call");
     int rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes,
                                       stream);
     if (rc) return rc;

@@ -201,8 +201,8 @@ extern "C" int kccot_mixed_sinkhorn_loss_fwd_f32(const float* R, const float* F,
     if ((u_hist == nullptr) != (v_hist == nullptr) || (dCmix_unit && u_hist))
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: give u_hist and v_hist together, or dCmix_unit, not both");
     if (dCmix_unit && !ticket) return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the fused path needs the ticket");
-    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS))
-        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split flags do not apply");
+    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS | KCCOT_COST_BICAUSAL_TERM_ONLY))
+        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only flags do not apply");
     if (!ws || ws_bytes < kccot_mixed_sinkhorn_loss_workspace_bytes(B, K))
         return fail(KCCOT_EWORKSPACE, "mixed_sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
                     kccot_mixed_sinkhorn_loss_workspace_bytes(B, K));

@@ -13,6 +13,10 @@ GPU, torch.distributed over RCCL/xGMI).  The reference has no distributed code a
   6. rank g forms the gradients of ITS samples from the replicated dLoss/dC and the gathered
      videos (kccot_pairwise_cost3_bwd_rows_f32): NO reduce-scatter of video-sized gradients.
 
+sharded_bicausal_sinkhorn_loss is the same for the bi-causal loss (gan_utils.compute_bicausal_sinkhorn_loss): after step 4
+(or the ksplit finalize) every rank adds the second causal term of each matrix to its replicated C3 (one launch,
+KCCOT_COST_BICAUSAL_TERM_ONLY); step 6 keeps the video gradient and forms the feature gradients with the bi-causal table.
+
 The returned loss is the GLOBAL-batch loss (identical on every rank).  Parameter gradients that
 flow back through a rank's local samples are therefore partial sums: combine them with an
 all-reduce SUM (not the mean DistributedDataParallel applies by default).
@@ -216,6 +220,87 @@ class HipOps:
               "pairwise_cost3_bwd_rows")
         return dfake, dhf, dhr, dmr, dmf
 
+    # ---- the bi-causal loss (gan_utils.compute_bicausal_sinkhorn_loss) ----
+    @staticmethod
+    def dfake_rows(dC3, real, fake, sc, row_begin, row_count):
+        """The video gradient of this rank's rows alone (kccot_pairwise_cost3_bwd_rows_f32, feature pointers NULL): the
+        bi-causal loss changes only the causal terms, so its distance part -- and this gradient -- is the one-batch loss's."""
+        B, K = real.shape
+        dfake = _lib.empty((row_count, K), torch.float32, real.device)
+        ws, wsb = workspace(lib.kccot_pairwise_cost3_bwd_workspace_bytes(B, K), real)
+        check(lib.kccot_pairwise_cost3_bwd_rows_f32(ptr(dC3), ptr(real), ptr(fake), B, K, sc, None, None, None, None, 1, 1,
+                                                    row_begin, row_count, ptr(dfake), None, None, None, None, ws, wsb,
+                                                    stream_of(real)), "pairwise_cost3_bwd_rows")
+        return dfake
+
+    @staticmethod
+    def bicausal_term(C3, h_fake, h_real, m_real, m_fake, sc):
+        """The replicated one-batch C3 [3,B,B] -> the bi-causal cost matrices, in place: the second causal term of each
+        matrix (KCCOT_COST_BICAUSAL_TERM_ONLY: the launch and summation order of the single-GPU loss)."""
+        B = C3.shape[1]
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        check(lib.kccot_pairwise_cost3_f32(None, None, B, 0, sc, ptr(h_fake), ptr(h_real), ptr(m_real), ptr(m_fake), T, J,
+                                           _lib.COST_BICAUSAL_TERM_ONLY, ptr(C3), None, 0, stream_of(C3)),
+              "pairwise_cost3(bi-causal term)")
+        return C3
+
+    @staticmethod
+    def bicausal_feature_grads(dC3, real, fake, h_fake, h_real, m_real, m_fake, sc, row_begin, row_count, whole=False):
+        """dh_fake, dh_real, dm_real, dm_fake of this rank's rows under the bi-causal job table (include/kccot.h).  They are
+        products of the replicated dC3 with the gathered features, formed for all B samples and sliced.
+        whole=True (replicated assembly, B <= 64): ONE launch, the single-GPU loss's backward with dC3 as its unit gradient
+        and no video gradient (its workspace, of the size the replicated cost assembly already holds).  Otherwise one
+        kccot_pairwise_cost_bwd_f32 per causal term with dx = dy = NULL (no workspace at all; the weight 2 of the xx / yy
+        terms folded into sc), and the two terms of each gradient added: the row-block and ksplit paths allocate nothing
+        that grows with K."""
+        B, K = real.shape
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        dev, st = real.device, stream_of(real)
+        feats = (ptr(h_fake), ptr(h_real), ptr(m_real), ptr(m_fake))
+        if whole:
+            df = _lib.empty((4, B, T, J), torch.float32, dev)
+            ws, wsb = workspace(lib.kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K), real)
+            # eps / L are only checked on this path: the solves' state is not read after a fused forward
+            check(lib.kccot_bicausal_sinkhorn_loss_bwd_f32(ptr(_one(dev)), ptr(real), ptr(fake), B, K, sc, *feats, T, J, 1.0, 0,
+                                                           None, None, None, None, ptr(dC3), None, *(ptr(d) for d in df),
+                                                           ws, wsb, st), "bicausal_sinkhorn_loss_bwd(feature gradients)")
+        else:
+            part = _lib.empty((2, 4, B, T, J), torch.float32, dev)     # [term][dh_fake, dh_real, dm_real, dm_fake]
+            #        g    rows h  cols M  weight  dh slot    dM slot
+            for p, h, M, w, sh, sm in ((0, h_fake, m_real, 1.0, (0, 0), (0, 2)), (0, h_real, m_fake, 1.0, (0, 1), (0, 3)),
+                                       (1, h_real, m_real, 2.0, (1, 1), (1, 2)), (2, h_fake, m_fake, 2.0, (1, 0), (1, 3))):
+                check(lib.kccot_pairwise_cost_bwd_f32(ptr(dC3[p]), ptr(real), ptr(fake), B, B, K, sc * w, ptr(h), ptr(M), T, J, 0,
+                                                      None, None, ptr(part[sh]), ptr(part[sm]), None, 0, st),
+                      "pairwise_cost_bwd(bi-causal term)")
+            df = part[0] + part[1]
+        return tuple(df[i, row_begin:row_begin + row_count] for i in range(4))
+
+
+_ones = {}
+
+
+def _one(device):
+    """One device float 1.0 per device (the upstream scalar of a library backward)."""
+    t = _ones.get(device)
+    if t is None:
+        t = torch.ones((1,), dtype=torch.float32, device=device)
+        _ones[device] = t
+    return t
+
+
+def _record(ops, bicausal, saved, C3):
+    """Iteration counts of the latest sharded evaluation, where raise_if_solver_aborted() looks for them."""
+    if ops is not HipOps:
+        return
+    nits, executed = saved[3][:3], saved[3][3:]
+    last_info["nits"], last_info["nits_executed"] = nits, executed
+    if bicausal:
+        tag = "compute_bicausal_sinkhorn_loss"
+        gan_utils.last_info[tag], gan_utils.last_info[tag + "_executed"] = nits, executed
+        last_info["C3"] = C3               # the replicated bi-causal cost matrices
+    else:
+        gan_utils.last_info["compute_sinkhorn_loss"] = nits    # raise_if_solver_aborted() covers the sharded loss too
+
 
 # ---- contraction-sharded protocol ("ksplit") ------------------------------------------------------------------
 # Instead of gathering the whole batch on every rank, the [B/G, K] shards are all-to-all'ed into [B, K/G] slices:
@@ -280,7 +365,7 @@ def _all_reduce_sum(t, group):
 
 class _KSplitLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, real_l, fake_l, h_fake_l, h_real_l, m_real_l, m_fake_l, sc, eps, L, group):
+    def forward(ctx, real_l, fake_l, h_fake_l, h_real_l, m_real_l, m_fake_l, sc, eps, L, group, bicausal):
         import ctypes
         rank, world = dist.get_rank(group), dist.get_world_size(group)
         Bl = real_l.shape[0]
@@ -312,18 +397,20 @@ class _KSplitLoss(torch.autograd.Function):
         check(lib.kccot_pairwise_cost3_f32(*args, _lib.COST_FROM_GRAM_SUMS, ptr(C3), ws.data_ptr(), wsb, stream_of(real_s)),
               "pairwise_cost3(from gram sums)")
         _mark("cost_finalize")
+        if bicausal:
+            HipOps.bicausal_term(C3, h_fake, h_real, m_real, m_fake, sc)
+            _mark("bicausal_term")
         loss, saved = HipOps.divergence_fwd(C3, eps, L)
         _mark("sinkhorn_fwd")
-        last_info["nits"], last_info["nits_executed"] = saved[3][:3], saved[3][3:]
-        gan_utils.last_info["compute_sinkhorn_loss"] = saved[3][:3]      # raise_if_solver_aborted() covers the sharded loss too
+        _record(HipOps, bicausal, saved, C3)
         ctx.saved_state = (saved, real_s, fake_s, h_fake, h_real, m_real, m_fake)
-        ctx.cfg = (sc, rank * Bl, Bl, group)
+        ctx.cfg = (sc, rank * Bl, Bl, group, bicausal)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         saved, real_s, fake_s, h_fake, h_real, m_real, m_fake = ctx.saved_state
-        sc, row_begin, Bl, group = ctx.cfg
+        sc, row_begin, Bl, group, bicausal = ctx.cfg
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
         _mark("between_fwd_and_bwd")
@@ -341,12 +428,16 @@ class _KSplitLoss(torch.autograd.Function):
         dfake = all_to_all_rows(dfake_s, group)
         _mark("exchange_gradient")
         # feature gradients of this rank's samples (KB-sized products of dC3 with the gathered features)
-        dhf, dhr, dmr, dmf = (_lib.empty((Bl, T, J), torch.float32, real_s.device) for _ in range(4))
-        check(lib.kccot_pairwise_cost3_bwd_rows_f32(ptr(dC3), ptr(real_s), ptr(fake_s), B, Ks, sc, ptr(h_fake), ptr(h_real),
-                                                    ptr(m_real), ptr(m_fake), T, J, row_begin, Bl, None, ptr(dhf), ptr(dhr),
-                                                    ptr(dmr), ptr(dmf), None, 0, stream_of(real_s)), "pairwise_cost3_bwd_rows")
+        if bicausal:
+            dhf, dhr, dmr, dmf = HipOps.bicausal_feature_grads(dC3, real_s, fake_s, h_fake, h_real, m_real, m_fake, sc,
+                                                               row_begin, Bl)
+        else:
+            dhf, dhr, dmr, dmf = (_lib.empty((Bl, T, J), torch.float32, real_s.device) for _ in range(4))
+            check(lib.kccot_pairwise_cost3_bwd_rows_f32(ptr(dC3), ptr(real_s), ptr(fake_s), B, Ks, sc, ptr(h_fake), ptr(h_real),
+                                                        ptr(m_real), ptr(m_fake), T, J, row_begin, Bl, None, ptr(dhf), ptr(dhr),
+                                                        ptr(dmr), ptr(dmf), None, 0, stream_of(real_s)), "pairwise_cost3_bwd_rows")
         _mark("gradient")
-        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None
+        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
 
 
 def all_gather_cat(t, group=None):
@@ -427,7 +518,7 @@ def all_gather_local_grad(t, group=None):
 
 class _ShardedLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, real_l, fake_l, h_fake_l, h_real_l, m_real_l, m_fake_l, sc, eps, L, group, ops):
+    def forward(ctx, real_l, fake_l, h_fake_l, h_real_l, m_real_l, m_fake_l, sc, eps, L, group, ops, bicausal):
         rank, world = dist.get_rank(group), dist.get_world_size(group)
         Bl = real_l.shape[0]
         _mark("start")
@@ -444,6 +535,7 @@ class _ShardedLoss(torch.autograd.Function):
         chunked = norms is not None and nchunks > 1 and hasattr(ops, "rows_gram_sums")
         bounds = gather_chunk_bounds(real_l.shape[1], nchunks) if chunked else None
         chunked = chunked and len(bounds) > 1
+        whole = False                # the whole C3 assembled on every rank (no row blocks)
         if chunked:
             pieces_r = _gather_columns_async(real_l, bounds, group)
             pieces_f = _gather_columns_async(fake_l, bounds, group)
@@ -472,6 +564,7 @@ class _ShardedLoss(torch.autograd.Function):
             _mark("exchange_costs")
         elif hasattr(ops, "cost3_full") and ops.replicate_costs(real.shape[0], real.shape[1]):
             C3 = ops.cost3_full(real, fake, h_fake, h_real, m_real, m_fake, sc)     # small batch: replicated assembly
+            whole = True
             _mark("cost_replicated")
         else:
             # row blocks of the three cost matrices (gan_utils.py:221-223)
@@ -486,23 +579,24 @@ class _ShardedLoss(torch.autograd.Function):
             _mark("cost_rows")
             C3 = all_gather_cat(blk.transpose(0, 1).contiguous(), group).transpose(0, 1).contiguous()  # [3,B,B]
             _mark("exchange_costs")
+        if bicausal:                             # every rank adds the second causal terms to its replicated C3
+            C3 = ops.bicausal_term(C3, h_fake, h_real, m_real, m_fake, sc)
+            _mark("bicausal_term")
         if hasattr(ops, "divergence_fwd"):       # solves + combination in one launch
             loss, saved = ops.divergence_fwd(C3, eps, L)
         else:
             cost3, saved = ops.sinkhorn3_fwd(C3, eps, L)
             loss = (2.0 * cost3[0] - cost3[1]) - cost3[2]       # gan_utils.py:225
         _mark("sinkhorn_fwd")
-        if ops is HipOps:
-            last_info["nits"], last_info["nits_executed"] = saved[3][:3], saved[3][3:]
-            gan_utils.last_info["compute_sinkhorn_loss"] = saved[3][:3]  # raise_if_solver_aborted() covers the sharded loss too
+        _record(ops, bicausal, saved, C3)
         ctx.saved_state = (saved, real, fake, h_fake, h_real, m_real, m_fake)
-        ctx.cfg = (sc, rank * Bl, Bl, ops)
+        ctx.cfg = (sc, rank * Bl, Bl, ops, bicausal, whole)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         saved, real, fake, h_fake, h_real, m_real, m_fake = ctx.saved_state
-        sc, row_begin, Bl, ops = ctx.cfg
+        sc, row_begin, Bl, ops, bicausal, whole = ctx.cfg
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
         g = g.reshape(())
@@ -513,7 +607,16 @@ class _ShardedLoss(torch.autograd.Function):
             gcost3 = torch.stack([2.0 * g, -g, -g])             # d(2 xy - xx - yy)
             dC3 = ops.sinkhorn3_bwd(saved, gcost3)
         _mark("sinkhorn_bwd")
-        if isinstance(real, list):       # chunked gather: the video gradient is separable in the columns, range by range
+        if bicausal:
+            # the video gradient is the one-batch loss's (range by range after a chunked gather); the feature gradients
+            # follow the bi-causal job table
+            reals, fakes = (real, fake) if isinstance(real, list) else ([real], [fake])
+            parts = [_dfake_rows(ops, dC3, r_c, f_c, h_fake, h_real, m_real, m_fake, sc, row_begin, Bl)
+                     for r_c, f_c in zip(reals, fakes)]
+            dfake = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+            dhf, dhr, dmr, dmf = ops.bicausal_feature_grads(dC3, reals[0], fakes[0], h_fake, h_real, m_real, m_fake, sc,
+                                                            row_begin, Bl, whole)
+        elif isinstance(real, list):     # chunked gather: the video gradient is separable in the columns, range by range
             parts = [ops.cost3_bwd_rows(dC3, r_c, f_c, h_fake, h_real, m_real, m_fake, sc, row_begin, Bl)
                      for r_c, f_c in zip(real, fake)]
             dfake = torch.cat([p[0] for p in parts], dim=1)
@@ -521,7 +624,13 @@ class _ShardedLoss(torch.autograd.Function):
         else:
             dfake, dhf, dhr, dmr, dmf = ops.cost3_bwd_rows(dC3, real, fake, h_fake, h_real, m_real, m_fake, sc, row_begin, Bl)
         _mark("gradient")
-        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None
+        return None, dfake, dhf, dhr, dmr, dmf, None, None, None, None, None, None
+
+
+def _dfake_rows(ops, dC3, real, fake, h_fake, h_real, m_real, m_fake, sc, row_begin, row_count):
+    if hasattr(ops, "dfake_rows"):
+        return ops.dfake_rows(dC3, real, fake, sc, row_begin, row_count)
+    return ops.cost3_bwd_rows(dC3, real, fake, h_fake, h_real, m_real, m_fake, sc, row_begin, row_count)[0]
 
 
 def sharded_sinkhorn_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, h_real_l, m_fake_l, group=None,
@@ -529,6 +638,30 @@ def sharded_sinkhorn_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, 
     """compute_sinkhorn_loss (gan_utils.py:204-227) of the GLOBAL batch from per-rank shards.
     Arguments are this rank's [B/G, ...] slices, in the reference's order h_fake, m_real, h_real,
     m_fake.  epsilon / L default to what the reference effectively runs (1.0, 100)."""
+    return _sharded_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, h_real_l, m_fake_l, group, ops, epsilon, L,
+                         protocol, False)
+
+
+def sharded_bicausal_sinkhorn_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, h_real_l, m_fake_l, group=None,
+                                   ops=None, epsilon=1.0, L=100, protocol=None):
+    """gan_utils.compute_bicausal_sinkhorn_loss, 2 W(x,y) - W(x,x) - W(y,y) with the bi-causal cost, of the GLOBAL batch
+    from per-rank shards: the same arguments, order and protocols as sharded_sinkhorn_loss, and the same result on every
+    rank.  Each protocol assembles the one-batch C3 exactly as sharded_sinkhorn_loss does (replicated at B <= 64; row
+    blocks all-gathered; ksplit: all-reduced Gram sums), then every rank adds the second causal term of each matrix to its
+    replicated C3 (KCCOT_COST_BICAUSAL_TERM_ONLY, the single-GPU loss's launch).  Backward: the video gradient rows are the
+    one-batch loss's; the feature gradients follow the bi-causal job table.  Records
+    gan_utils.last_info["compute_bicausal_sinkhorn_loss"] (and dist.last_info["C3"]).  Injected ``ops`` must provide
+    ``bicausal_term`` and ``bicausal_feature_grads``."""
+    ops = ops or HipOps
+    missing = [n for n in ("bicausal_term", "bicausal_feature_grads") if not hasattr(ops, n)]
+    if missing:
+        raise NotImplementedError("sharded bi-causal loss: the ops %r lack %s" % (getattr(ops, "__name__", ops), ", ".join(missing)))
+    return _sharded_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, h_real_l, m_fake_l, group, ops, epsilon, L,
+                         protocol, True)
+
+
+def _sharded_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, h_real_l, m_fake_l, group, ops, epsilon, L, protocol,
+                  bicausal):
     ops = ops or HipOps
     Bl = f_real_l.shape[0]
     cast = (lambda v: v.float()) if ops is HipOps else (lambda v: v)   # the HIP kernels are fp32
@@ -554,9 +687,9 @@ def sharded_sinkhorn_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, 
         if not ksplit_supported(Bl * world, K, world):
             raise NotImplementedError("ksplit protocol: unsupported shape B=%d K=%d on %d ranks" % (Bl * world, K, world))
         return _KSplitLoss.apply(flat(f_real_l), flat(f_fake_l), feat(h_fake_l), feat(h_real_l), feat(m_real_l),
-                                 feat(m_fake_l), float(scaling_coef), float(epsilon), int(L), group).reshape(())
+                                 feat(m_fake_l), float(scaling_coef), float(epsilon), int(L), group, bicausal).reshape(())
     return _ShardedLoss.apply(flat(f_real_l), flat(f_fake_l), feat(h_fake_l), feat(h_real_l), feat(m_real_l),
-                              feat(m_fake_l), float(scaling_coef), float(epsilon), int(L), group, ops).reshape(())
+                              feat(m_fake_l), float(scaling_coef), float(epsilon), int(L), group, ops, bicausal).reshape(())
 
 
 # ---- helpers used by bench.py ---------------------------------------------------------------------
@@ -572,8 +705,9 @@ def shard_batch(t, rank, world):
     return out
 
 
-def sharded_loss_step(shard, sc, group=None, epsilon=1.0, L=100, protocol=None):
-    loss = sharded_sinkhorn_loss(shard["real"], shard["fake"], sc, shard["h_fake"], shard["m_real"], shard["h_real"],
-                                 shard["m_fake"], group, epsilon=epsilon, L=L, protocol=protocol)
+def sharded_loss_step(shard, sc, group=None, epsilon=1.0, L=100, protocol=None, bi_causal=False):
+    fn = sharded_bicausal_sinkhorn_loss if bi_causal else sharded_sinkhorn_loss
+    loss = fn(shard["real"], shard["fake"], sc, shard["h_fake"], shard["m_real"], shard["h_real"], shard["m_fake"], group,
+              epsilon=epsilon, L=L, protocol=protocol)
     grads = torch.autograd.grad(loss, [shard[k] for k in ("fake", "h_fake", "h_real", "m_real", "m_fake")])
     return loss, grads

@@ -102,12 +102,16 @@ class GraphedShardedStep:
     the reverse sweep, the gradients of this rank's rows); for batches of at most 64 (``HipOps.replicate_costs``) the
     costs are assembled whole on every rank and everything after the input gathers is ONE graph.  Same kernels, arguments and order as the eager path
     (``dist._ShardedLoss``): bit-identical results (tests/test_dist_gloo.py).  ``step(fake=..., h_fake=...)`` copies the
-    given LOCAL shards ([B/G, ...]) into the static buffers first; returns (loss, grads) as static tensors."""
+    given LOCAL shards ([B/G, ...]) into the static buffers first; returns (loss, grads) as static tensors.
+    ``bi_causal=True``: ``dist.sharded_bicausal_sinkhorn_loss`` -- the second causal terms added to the replicated C3 in
+    front of the solves, the video gradient rows alone from the cost backward, the bi-causal feature gradients after it
+    (the eager path's kernels and order)."""
 
-    def __init__(self, shard, scaling_coef, group=None, epsilon=1.0, L=100, warmup=2):
+    def __init__(self, shard, scaling_coef, group=None, epsilon=1.0, L=100, warmup=2, bi_causal=False):
         import torch.distributed as dist
         from . import dist as kd
         self._kd, self._dist, self.group = kd, dist, group
+        self.bi_causal = bool(bi_causal)
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         self._nccl = dist.get_backend(group) == "nccl"
         Bl = shard["real"].shape[0]
@@ -190,6 +194,8 @@ class GraphedShardedStep:
             self._f[i].copy_(self.full["feats"][:, i])
         if self.replicated:
             self._C3 = self._kd.HipOps.cost3_full(self.full["real"], self.full["fake"], *self._f, sc)
+            if self.bi_causal:
+                self._kd.HipOps.bicausal_term(self._C3, *self._f, sc)
             return
         blk = self._kd.HipOps.cost3_rows(self.full["real"], self.full["fake"], *self._f, sc, row_begin, Bl,
                                          self.full["norms"] if self.use_norms else None)
@@ -199,9 +205,16 @@ class GraphedShardedStep:
         sc, eps, L, row_begin, Bl = self._cfg
         H = self._kd.HipOps
         C3 = self._C3 if self.replicated else self._C3g.transpose(0, 1).contiguous()
+        if self.bi_causal and not self.replicated:
+            H.bicausal_term(C3, *self._f, sc)
         loss, saved = H.divergence_fwd(C3, eps, L)
         dC3 = H.divergence_bwd(saved, self._one)
-        g = H.cost3_bwd_rows(dC3, self.full["real"], self.full["fake"], *self._f, sc, row_begin, Bl)
+        if self.bi_causal:
+            real, fake = self.full["real"], self.full["fake"]
+            g = (H.dfake_rows(dC3, real, fake, sc, row_begin, Bl),) + \
+                H.bicausal_feature_grads(dC3, real, fake, *self._f, sc, row_begin, Bl, self.replicated)
+        else:
+            g = H.cost3_bwd_rows(dC3, self.full["real"], self.full["fake"], *self._f, sc, row_begin, Bl)
         names = ("fake",) + _FEATS
         return loss, {k: v.reshape(self._shapes[k]) for k, v in zip(names, g)}, saved[3]
 
@@ -224,15 +237,17 @@ class GraphedKSplitStep:
     """Forward + backward of the contraction-sharded protocol (``dist._KSplitLoss``) at dLoss = 1 for one rank:
     all-to-all x2 + all-gather (features) -> graph A (fp64 Gram sums of the rank's K-slice) -> all-reduce(SUM) of the
     sums -> graph B (finalize, solves, reverse sweep, video gradient of ALL samples on the slice, feature gradients
-    of the rank's samples) -> all-to-all back.  Same calls and order as the eager Function: bit-identical results."""
+    of the rank's samples) -> all-to-all back.  Same calls and order as the eager Function: bit-identical results.
+    ``bi_causal=True``: the bi-causal loss (the second causal terms after the finalize, the bi-causal feature gradients)."""
 
-    def __init__(self, shard, scaling_coef, group=None, epsilon=1.0, L=100, warmup=2):
+    def __init__(self, shard, scaling_coef, group=None, epsilon=1.0, L=100, warmup=2, bi_causal=False):
         import ctypes
         import torch.distributed as dist
         from . import dist as kd
         from . import _lib
         from ._lib import lib, check
         self._kd, self._dist, self.group = kd, dist, group
+        self.bi_causal = bool(bi_causal)
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         Bl = shard["real"].shape[0]
         dev = shard["real"].device
@@ -307,12 +322,17 @@ class GraphedKSplitStep:
         sc, eps, L, row_begin, Bl, B, Ks, T, J = self._cfg
         H = self._kd.HipOps
         self._cost3(_lib.COST_FROM_GRAM_SUMS)
+        if self.bi_causal:
+            H.bicausal_term(self._C3, *self._f, sc)
         loss, saved = H.divergence_fwd(self._C3, eps, L)
         dC3 = H.divergence_bwd(saved, self._one)
         ws, wsb = workspace(lib.kccot_pairwise_cost3_bwd_workspace_bytes(B, Ks), self._real_s)
         check(lib.kccot_pairwise_cost3_bwd_f32(ptr(dC3), ptr(self._real_s), ptr(self._fake_s), B, Ks, sc, None, None, None, None,
                                                1, 1, ptr(self._dfake_s), None, None, None, None, ws, wsb,
                                                stream_of(self._real_s)), "pairwise_cost3_bwd")
+        if self.bi_causal:         # the static homes of the feature gradients are the capture's outputs
+            self._fg = list(H.bicausal_feature_grads(dC3, self._real_s, self._fake_s, *self._f, sc, row_begin, Bl))
+            return loss, saved[3]
         check(lib.kccot_pairwise_cost3_bwd_rows_f32(ptr(dC3), ptr(self._real_s), ptr(self._fake_s), B, Ks, sc, ptr(self._f[0]),
                                                     ptr(self._f[1]), ptr(self._f[2]), ptr(self._f[3]), T, J, row_begin, Bl, None,
                                                     ptr(self._fg[0]), ptr(self._fg[1]), ptr(self._fg[2]), ptr(self._fg[3]),

@@ -12,7 +12,8 @@ staircase ExponentialDecay schedule (:54-59, data_utils.py:589-621).
 Data-parallel use (one process per GPU, torch.distributed over RCCL): pass ``group``; each rank
 feeds its shard of the batch, the loss is the GLOBAL-batch divergence assembled by
 ``kccotgan_amd.dist`` and parameter gradients are all-reduced with SUM (the loss is replicated,
-each rank holds the partial derivative through its own samples).
+each rank holds the partial derivative through its own samples).  ``bi_causal=True`` runs there too
+(``dist.sharded_bicausal_sinkhorn_loss``, GPU devices only); ``mixed_sinkhorn=True`` has no sharded form.
 
 ``sample`` is the test-time autoregressive loop (kernel_train.py:340-347), ``fit`` the loop body around the two
 steps (:295-330): per-iteration sigma (annealed or fixed, :308-311), the scalar log ``pM`` / ``Sinkhorn Loss``
@@ -99,8 +100,10 @@ class KCCOTTrainer:
             raise ValueError("mixed_sinkhorn=True and bi_causal=True are exclusive loss modes (kernel_train.py:179-184)")
         if mixed_sinkhorn and data_parallel:
             raise NotImplementedError("mixed_sinkhorn=True has no batch-sharded (data-parallel) form")
-        if bi_causal and data_parallel:
-            raise NotImplementedError("bi_causal=True has no batch-sharded (data-parallel) form")
+        if bi_causal and data_parallel and torch.device(device).type != "cuda":
+            # the batch-sharded bi-causal loss (dist.sharded_bicausal_sinkhorn_loss) runs on the HIP library only
+            raise NotImplementedError("bi_causal=True with data parallelism: the sharded bi-causal loss runs on the GPU only "
+                                      "(device %r)" % (device,))
         self.mixed_sinkhorn = bool(mixed_sinkhorn)
         self.bi_causal = bool(bi_causal)
         torch.manual_seed(seed)
@@ -156,7 +159,11 @@ class KCCOTTrainer:
         h_real = self.discriminator_h(real)
         m_real = self.discriminator_m(real)
         m_fake = self.discriminator_m(fake)
-        if self.bi_causal:
+        if self.bi_causal and self._world() > 1:
+            from . import dist as kd
+            loss = kd.sharded_bicausal_sinkhorn_loss(real.detach(), fake, self.scaling_coef, h_fake, m_real, h_real, m_fake,
+                                                     group=self.group)
+        elif self.bi_causal:
             loss = gan_utils.compute_bicausal_sinkhorn_loss(real.detach(), fake, self.scaling_coef, self.sinkhorn_eps,
                                                             self.sinkhorn_l, h_fake, m_real, h_real, m_fake, video=True)
         elif self._world() > 1:
