@@ -9,10 +9,13 @@ Workload = BASELINE.json configs[1]: Moving-MNIST shape [B=64, H=64, T=30, W=64,
 scaling_coef=1/15, epsilon=1, 100 Sinkhorn iterations (the as-called behaviour of the
 reference: gan_utils.py:221-223).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+headline keys.  The other blocks -- those listed below from `event_timing` to `cpu_baseline`, and `with_exact_shortcut`,
+`eager_launches_ms_per_step`, `box_probe`, `kernel_smoothing`, `train_steps_per_sec_data_parallel` -- are measured only
+with --full, after the timed region; --no-cpu-baseline / --no-train / --no-configs / --no-pmc leave parts of them out.
   value / ms_per_step  loss evaluations per second / the BASELINE "Sinkhorn-loss ms/iter": EXACTLY K steps between
                        two barriers, one wall-clock interval, max over ranks (the driver's contract).
   event_timing         the same step replayed >= 100 more times with a HIP event between consecutive replays (on the
@@ -677,11 +680,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the train-steps/sec child process")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs[2..4] block")
-    ap.add_argument("--no-pmc", action="store_true", help="do not re-measure roofline.traffic (two rocprofv3 counter passes "
-                                                          "over a child process); report the committed figure")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also record everything else: event timing, the exact-shortcut and eager "
+                         "timings, roofline, Sinkhorn kernels, configs[2..4], kernel smoothing, train-steps/sec, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the train-steps/sec child process")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the configs[2..4] block")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not re-measure roofline.traffic (two rocprofv3 counter "
+                                                          "passes over a child process); report the committed figure")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the loss and gradients of the last timed step to DIR/<name>.npy (N > 1: <name>.rank<r>.npy, "
                          "each rank its shard)")
@@ -830,6 +836,17 @@ def main():
     }
     if dumped:
         out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()          # rank 0 may have measured the roofline block after the timed region: leave together
+            dist.destroy_process_group()
+
+    if not args.full:               # a plain run: the headline is all it measures
+        finish()
+        return
     # ---- per-step distribution with HIP events (all ranks replay -- the sharded step has collectives; rank 0 reports)
     try:
         reps = max(100, args.steps)
@@ -1009,11 +1026,7 @@ def main():
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
       except Exception as e:
         sys.stderr.write("bench: cpu_baseline failed: %r\n" % (e,))
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()          # rank 0 measured the roofline block after the timed region: leave together
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

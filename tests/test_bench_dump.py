@@ -44,3 +44,23 @@ def test_bench_steps_and_dumped_outputs(tmp_path):
         ref = g.cpu().numpy()
         assert d.dtype == np.float32 and d.shape == inp[k].shape, k
         np.testing.assert_allclose(d, ref, rtol=1e-5, atol=1e-6 * float(np.abs(ref).max()), err_msg=k)
+
+
+# what only `bench.py --full` measures: a plain run prints the headline and nothing of this
+FULL_ONLY = ("event_timing", "with_exact_shortcut", "eager_launches_ms_per_step", "roofline", "sinkhorn", "configs",
+             "box_probe", "kernel_smoothing", "train_steps_per_sec", "train_steps_per_sec_data_parallel", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_holds_the_headline_only():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["metric"] == "sinkhorn_loss_evals_per_sec" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert res["unit"] == "loss-evals/s (fwd+bwd)" and res["steps"] == 3 and res["warmup"] == 1
+    assert res["ms_per_step"] > 0 and abs(res["value"] * res["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert res["config"]["sinkhorn_iters_executed"] == [100, 100, 100]
+    assert not [k for k in FULL_ONLY if k in res] and "dumped_outputs" not in res

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 export KCCOT_BENCH_BACKEND=gloo
 for n in 2 4; do
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus $n --steps 5 --warmup 2 $([ $n -gt 2 ] && echo --no-train) > "$OUT/bench_n$n.log" 2>&1 || { echo "N=$n failed"; tail -30 "$OUT/bench_n$n.log"; exit 1; }
+      bench.py --gpus $n --steps 5 --warmup 2 --full $([ $n -gt 2 ] && echo --no-train) > "$OUT/bench_n$n.log" 2>&1 || { echo "N=$n failed"; tail -30 "$OUT/bench_n$n.log"; exit 1; }
   grep '^{' "$OUT/bench_n$n.log" | tail -1 > "$OUT/bench_n$n.json"
   python3 - "$OUT/bench_n$n.json" <<'PY'
 import json, sys

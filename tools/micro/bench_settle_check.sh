@@ -1,4 +1,4 @@
-for i in 1 2 3; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train --no-configs --no-pmc 2>/dev/null | python3 -c "
+for i in 1 2 3; do python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-train --no-configs --no-pmc 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
