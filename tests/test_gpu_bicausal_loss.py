@@ -64,14 +64,14 @@ def call(G, t, case=None, **kw):
                                             t["m_fake"], **kw)
 
 
-def oracle(d, eps=1.0, L=100, chunk=None, video=True):
+def oracle(d, eps=1.0, L=100, chunk=None, video=True, sc=cases.SC):
     """torch composition of the reference's compute_sinkhorn(..., bi_causal=True) over the three terms; returns
     (loss, {tag: W}, {tag: C})."""
     fl = ot.flatten_video if video else (lambda v: v)
     v = dict(d, real=fl(d["real"]), fake=fl(d["fake"]))
     w, C = {}, {}
     for tag, a, b, hy, mx, hx, my in bicausal_cases.TERMS:
-        C[tag] = ot.bi_causal_modified_cost(v[a], v[b], v[hy], v[mx], v[hx], v[my], cases.SC, chunk)
+        C[tag] = ot.bi_causal_modified_cost(v[a], v[b], v[hy], v[mx], v[hx], v[my], sc, chunk)
         w[tag] = ot.sinkhorn_from_cost(C[tag], eps, L)[0]
     return 2.0 * w["xy"] - w["xx"] - w["yy"], w, C
 
@@ -313,3 +313,71 @@ def test_bicausal_loss_graph_replay_equals_eager(G, L, fused):
         eager = step()
         for a, b in zip(out, eager):
             assert torch.equal(a, b)
+
+
+def _check_against_oracle(G, inp, wrt, sc, gtol, loss_abs=0.0, tag=None):
+    """The loss with gradients of `wrt` against the fp64 oracle: C3 at 1e-5 of max|C|, costs 1e-4 relative (+ 1e-5 of
+    max|C|), loss per loss_tol (+ loss_abs), gradients gtol of max|grad| (exactly zero where the oracle's are)."""
+    t = {k: torch.from_numpy(v).to(DEV) for k, v in inp.items()}
+    for k in wrt:
+        t[k].requires_grad_(True)
+    loss = G.compute_bicausal_sinkhorn_loss(t["real"], t["fake"], sc, 0.8, 100, t["h_fake"], t["m_real"], t["h_real"],
+                                            t["m_fake"])
+    G.raise_if_solver_aborted((TAG,))
+    got = dict(zip(wrt, (x.cpu().numpy() for x in torch.autograd.grad(loss, [t[k] for k in wrt], retain_graph=True))))
+    d = {k: torch.from_numpy(v).double() for k, v in inp.items()}
+    for k in wrt:
+        d[k].requires_grad_(True)
+    ref_val, ref_w, refC = oracle(d, chunk=16, video=False, sc=sc)
+    ref = dict(zip(wrt, (x.numpy() for x in torch.autograd.grad(ref_val, [d[k] for k in wrt]))))
+    C3 = G.last_info[TAG + "_C3"].cpu().numpy()
+    costs = G.last_info[TAG + "_costs"].cpu().numpy()
+    for k, name in enumerate(("xy", "xx", "yy")):
+        C = refC[name].detach().numpy()
+        np.testing.assert_allclose(C3[k], C, rtol=0, atol=1e-5 * np.abs(C).max(), err_msg=str((tag, "C_" + name)))
+        w = float(ref_w[name])
+        assert abs(costs[k] - w) <= 1e-4 * abs(w) + 1e-5 * np.abs(C).max(), (tag, name, costs[k], w)
+    assert abs(float(loss) - float(ref_val)) <= loss_tol(ref_val, ref_w.values()) + loss_abs, (tag, float(loss),
+                                                                                                 float(ref_val))
+    for k in wrt:
+        scale = np.abs(ref[k]).max()
+        if scale == 0:
+            assert np.abs(got[k]).max() == 0, (tag, k)
+            continue
+        np.testing.assert_allclose(got[k], ref[k], rtol=0, atol=gtol * scale, err_msg=str((tag, k)))
+    return loss
+
+
+def test_bicausal_loss_on_random_ragged_shapes(G):
+    """20 seeded configurations in the style of test_gpu_parity.py::test_loss_and_gradients_on_random_ragged_shapes: B from
+    1 to 70, T = 1 (no causal term: the four feature gradients are exactly zero) to 6, J = 1 .. 5, K not a multiple of 4,
+    sc in {1/15, 1, 0.01}, near and far regimes -- against the fp64 oracle (loss per loss_tol, gradients at the floor /
+    4 x the far-regime gap)."""
+    rng = np.random.default_rng(20264)
+    for trial in range(20):
+        B = int(rng.choice([1, 2, 3, 5, 7, 11, 17, 23, 31, 33, 48, 63, 65, 70]))
+        T, J = int(rng.integers(1, 7)), int(rng.integers(1, 6))
+        K = 4 * int(rng.integers(1, 40)) + int(rng.integers(1, 4))
+        far = bool(rng.integers(0, 2))
+        sc = float(rng.choice([cases.SC, 1.0, 0.01]))
+        inp = _rand_inputs(B, K, T, J, seed=trial)
+        if far:
+            inp["fake"] = np.random.default_rng(trial).random(inp["real"].shape, dtype=np.float32)
+        tol = max(2.5e-5, 4 * 2.5e-4 if far else 0.0) * 4
+        _check_against_oracle(G, inp, WRT, sc, tol, loss_abs=2e-6, tag=(trial, B, T, J, K, far, sc))
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("part", ["features", "videos"])
+def test_bicausal_loss_partial_gradients(G, L, part, fused):
+    """Discriminator step (fake detached: dfake is NULL) and generator step (every feature detached: every feature-gradient
+    pointer NULL): the requested gradients match the fp64 ones; the loss node hands back None for the rest."""
+    L.set_option("sinkhorn_fused", fused)
+    wrt = WRT[1:] if part == "features" else ["fake"]
+    inp = _rand_inputs(48, 258, T=5, J=3, seed=7)
+    loss = _check_against_oracle(G, inp, wrt, cases.SC, 1e-4)
+    assert G.last_info[TAG + "_fused_sweep"] == bool(fused)
+    node = loss.grad_fn.apply(torch.ones((), device=DEV))     # (7 x None, dfake, dh_fake, dh_real, dm_real, dm_fake)
+    assert all(x is None for x in node[:7])
+    for k, x in zip(["fake", "h_fake", "h_real", "m_real", "m_fake"], node[7:]):
+        assert (x is None) == (k not in wrt), k

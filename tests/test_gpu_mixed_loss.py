@@ -247,3 +247,208 @@ def test_mixed_loss_graph_replay_is_bit_identical(G, L, fused):
         eager = step()
         for a, b in zip(out, eager):
             assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------- random decimated inputs: every dispatch path at 2B
+def _oracle_flat(d, sc=cases.SC, eps=1.0, L=100, chunk=16):
+    """The oracle composition of oracle() on [B,1,K] videos (cost_xy sums the last two axes): (loss, [W1..W4], [C1..C4])."""
+    C = [ot.modified_cost(d[a], d[b], d[h], d[m], sc, chunk) for a, b, h, m, _ in mixed_cases.TERMS]
+    w = [ot.sinkhorn_from_cost(c, eps, L)[0] for c in C]
+    return (w[0] + w[1]) - w[2] - w[3], w, C
+
+
+def _rand_inputs(B, K, T=8, J=8, seed=0, far=False):
+    """x, x' uniform; y, y' 0.05 from them ("near": W1, W2 near, W3, W4 pair independent samples) or uniform ("far")."""
+    rng = np.random.default_rng(3000 + B + seed)
+    inp = {}
+    for k in ("real", "real_p"):
+        inp[k] = rng.random((B, 1, K), dtype=np.float32)
+    for k, src in (("fake", "real"), ("fake_p", "real_p")):
+        inp[k] = rng.random((B, 1, K), dtype=np.float32) if far else np.clip(
+            inp[src] + np.float32(0.05) * rng.standard_normal((B, 1, K), dtype=np.float32), 0, 1).astype(np.float32)
+    for k in ("h_fake", "m_real", "h_real_p", "m_fake", "h_fake_p", "m_real_p"):
+        inp[k] = rng.random((B, T, J), dtype=np.float32)
+    return inp
+
+
+def _run(G, inp, wrt=WRT, sc=cases.SC, **kw):
+    """The mixed loss on the GPU with gradients of `wrt`: (loss, {name: grad}, [nits, costs, Cmix], fused_sweep)."""
+    t = {k: torch.from_numpy(v).to(DEV) for k, v in inp.items()}
+    for k in wrt:
+        t[k].requires_grad_(True)
+    loss = G.compute_mixed_sinkhorn_loss(t["real"], t["fake"], t["real_p"], t["fake_p"], sc, 0.8, 100, t["h_fake"],
+                                         t["m_real"], t["h_real_p"], t["m_fake"], t["h_fake_p"], t["m_real_p"], **kw)
+    info = [G.last_info["compute_mixed_sinkhorn_loss" + s].clone() for s in ("", "_costs", "_Cmix")]
+    fused = G.last_info["compute_mixed_sinkhorn_loss_fused_sweep"]
+    G.raise_if_solver_aborted(("compute_mixed_sinkhorn_loss",))
+    grads = dict(zip(wrt, (x.cpu().numpy() for x in torch.autograd.grad(loss, [t[k] for k in wrt])))) if wrt else {}
+    return float(loss), grads, info, fused
+
+
+def _ref(inp, wrt=WRT, sc=cases.SC, **kw):
+    d = {k: torch.from_numpy(v).double() for k, v in inp.items()}
+    for k in wrt:
+        d[k].requires_grad_(True)
+    val, w, C = _oracle_flat(d, sc, **kw)
+    grads = dict(zip(wrt, (x.numpy() for x in torch.autograd.grad(val, [d[k] for k in wrt])))) if wrt else {}
+    return float(val), [float(x) for x in w], [c.detach().numpy() for c in C], grads
+
+
+def _check_mix(got, ref, gtol=1e-4, loss_abs=0.0):
+    """Cost matrices 1e-5 of max|C|, the four costs 1e-4 relative (+ 1e-5 of max|C_k|: W_k averages C_k, whose causal
+    term can cancel its distances), loss 1e-4 of max(|loss|, max_k |W_k|) (+ loss_abs), gradients gtol of max|grad| (a
+    gradient the oracle has as exactly zero -- T = 1 features -- must be exactly zero)."""
+    loss, grads, (nits, costs, Cmix), _ = got
+    ref_val, ref_w, ref_C, ref_g = ref
+    Cmix, costs = Cmix.cpu().numpy(), costs.cpu().numpy()
+    for k in range(4):
+        np.testing.assert_allclose(Cmix[k], ref_C[k], rtol=0, atol=1e-5 * np.abs(ref_C[k]).max(), err_msg="C%d" % (k + 1))
+        assert abs(costs[k] - ref_w[k]) <= 1e-4 * abs(ref_w[k]) + 1e-5 * np.abs(ref_C[k]).max(), (k, costs[k], ref_w[k])
+    assert abs(loss - ref_val) <= 1e-4 * max(abs(ref_val), max(abs(x) for x in ref_w)) + loss_abs, (loss, ref_val)
+    for k, b in ref_g.items():
+        scale = np.abs(b).max()
+        if scale == 0:
+            assert np.abs(grads[k]).max() == 0, k
+            continue
+        np.testing.assert_allclose(grads[k], b, rtol=0, atol=gtol * scale, err_msg=k)
+
+
+def _check_shape(G, L, B, K, opts=(), flags=0):
+    for k, v in opts:
+        L.set_option(k, v)
+    G.cost_flags = flags
+    inp = _rand_inputs(B, K)
+    got = _run(G, inp)
+    _check_mix(got, _ref(inp))
+    return got
+
+
+# 2B = 64 (B = 32), 80 / 74 (direct kernel above 64 rows, K % 4 != 0), 128 (B == 64: one-launch backward), 192 (blocked),
+# 256 (gram_q256; K % 32 != 0: its ragged-K form), 384 (128-row tiles; the four solves at n = 192 on the multi-CU solver)
+@pytest.mark.parametrize("B,K", [(32, 512), (40, 258), (37, 260), (64, 512), (96, 256), (128, 256), (128, 256 + 36),
+                                 (192, 256)],
+                         ids=["b32", "b40_ragged", "b37_odd", "b64", "b96_blocked", "b128_q256", "b128_q256_ragged_k",
+                              "b192_tiled"])
+def test_mixed_loss_on_every_cost_rung(G, L, B, K):
+    got = _check_shape(G, L, B, K)
+    assert got[3] == bool(L.lib.kccot_sinkhorn_fused_eligible(B, 100))
+
+
+@pytest.mark.parametrize("variant", ["direct", "gram_f32", "no_tiles", "apply_m256_0", "apply_one_launch_0"])
+def test_mixed_loss_b64_with_the_ladder_stepped_down(G, L, variant):
+    opts = {"direct": (), "gram_f32": (("gram_f32", 1), ("apply_f32", 1)),
+            "no_tiles": (("cost_tiled", 0), ("cost_tile256", 0), ("cost_blocked", 0)),
+            "apply_m256_0": (("apply_m256", 0),), "apply_one_launch_0": (("apply_one_launch", 0),)}[variant]
+    _check_shape(G, L, 64, 512, opts=opts, flags=L.COST_FORCE_DIRECT if variant == "direct" else 0)
+
+
+def test_mixed_loss_b128_on_the_128_row_tiles(G, L):
+    """2B = 256 with cost_tile256 = 0: the 128-row tiles of cost_tiled.hip instead of gram_q256."""
+    _check_shape(G, L, 128, 256, opts=(("cost_tile256", 0),))
+
+
+def test_mixed_loss_b192_four_problem_solver_forms(G, L):
+    """n = 192 > 128: the four solves on the multi-CU solver.  Without the per-XCD layout (sinkhorn_coop_xcd = 0, the
+    agent-scope exchange) the result is the same bits (include/kccot.h); the streaming solver (sinkhorn_coop = 0) is
+    another kernel and is held to the fp64 oracle."""
+    inp = _rand_inputs(192, 256, seed=1)
+    ref = _ref(inp)
+    base = _run(G, inp)
+    _check_mix(base, ref)
+    with L.options(sinkhorn_coop_xcd=0):
+        agent = _run(G, inp)
+    assert base[0] == agent[0]
+    for a, b in zip(base[2], agent[2]):
+        assert torch.equal(a, b)
+    for k in WRT:
+        np.testing.assert_array_equal(base[1][k], agent[1][k], err_msg=k)
+    with L.options(sinkhorn_coop=0):
+        _check_mix(_run(G, inp), ref)
+
+
+def test_mixed_video_gradient_on_256x256_tiles(G, L):
+    """2B = 256 and K = 131072: 512 column tiles, so the stacked video gradient d[y; y'] runs on the 256 x 256 tiles of
+    cost_bwd_q256.hip (apply_q256 = 1, the default) -- bit-identical to the 256 x 64 / 128 tiles (apply_q256 = 0) and
+    within 1e-4 of max|grad| of the fp64 gradient.  sc is scaled by 512 / K to keep the costs of the decimated shapes
+    (K = 131072 at sc = 1/15 would be a far sharper problem).  The fp64 reference is the oracle's causal term and Sinkhorn
+    solve on cost matrices from an fp64 Gram product, and the closed form of d C / d y (the oracle's broadcast cost_xy
+    would hold [B,B,K] in fp64)."""
+    B, K = 128, 131072
+    sc = cases.SC * 512 / K
+    inp = _rand_inputs(B, K, T=4, J=4, seed=2)
+    wrt = ["fake", "fake_p"]
+    out = {}
+    for mode in (1, 0):
+        with L.options(apply_q256=mode):
+            out[mode] = _run(G, inp, wrt, sc=sc)
+    for k in wrt:
+        np.testing.assert_array_equal(out[1][1][k], out[0][1][k], err_msg=k)
+    d = {k: torch.from_numpy(v.reshape(v.shape[0], -1)).double() for k, v in inp.items()}
+
+    def sqd(a, b):
+        return ((a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2.0 * a @ b.t()) * sc
+
+    C = []
+    for a, b, h, m, _ in mixed_cases.TERMS:
+        c = (sqd(d[a], d[b]) + ot.causal_term(d[h].reshape(B, 4, 4), d[m].reshape(B, 4, 4), sc)).requires_grad_(True)
+        C.append(c)
+    w = [ot.sinkhorn_from_cost(c, 1.0, 100)[0] for c in C]
+    ref_val = (w[0] + w[1]) - w[2] - w[3]
+    dC1, dC2, _, dC4 = torch.autograd.grad(ref_val, C)
+    x, y, x_p, y_p = d["real"], d["fake"], d["real_p"], d["fake_p"]
+    # C1 = sc |x_i - y_j|^2, C2 = sc |x'_i - y'_j|^2, C4 = sc |y_i - y'_j|^2
+    dy = 2 * sc * (dC1.sum(0)[:, None] * y - dC1.t() @ x + dC4.sum(1)[:, None] * y - dC4 @ y_p)
+    dy_p = 2 * sc * (dC2.sum(0)[:, None] * y_p - dC2.t() @ x_p + dC4.sum(0)[:, None] * y_p - dC4.t() @ y)
+    assert abs(out[1][0] - float(ref_val)) <= 1e-4 * max(abs(float(ref_val)), max(abs(float(v)) for v in w))
+    for k, ref in (("fake", dy.numpy()), ("fake_p", dy_p.numpy())):
+        np.testing.assert_allclose(out[1][1][k].reshape(B, K), ref, rtol=0, atol=1e-4 * np.abs(ref).max(), err_msg=k)
+
+
+def test_mixed_loss_on_random_ragged_shapes(G):
+    """20 seeded configurations in the style of test_gpu_parity.py::test_loss_and_gradients_on_random_ragged_shapes: B from
+    1 to 70 (odd, prime, one sample, just above 64, not a multiple of 16), T = 1 (no causal term: the six feature
+    gradients are exactly zero) to 6, J = 1 .. 5, K not a multiple of 4, sc in {1/15, 1, 0.01}, near and far regimes --
+    against the fp64 oracle (loss at 1e-4 of max(|loss|, max |W_k|), gradients at the floor / 4 x the far-regime gap)."""
+    rng = np.random.default_rng(20263)
+    for trial in range(20):
+        B = int(rng.choice([1, 2, 3, 5, 7, 11, 17, 23, 31, 33, 48, 63, 65, 70]))
+        T, J = int(rng.integers(1, 7)), int(rng.integers(1, 6))
+        K = 4 * int(rng.integers(1, 40)) + int(rng.integers(1, 4))
+        far = bool(rng.integers(0, 2))
+        sc = float(rng.choice([cases.SC, 1.0, 0.01]))
+        inp = _rand_inputs(B, K, T, J, seed=trial, far=far)
+        tag = (trial, B, T, J, K, far, sc)
+        got = _run(G, inp, sc=sc)
+        ref = _ref(inp, sc=sc)
+        if T == 1:
+            assert all(np.abs(got[1][k]).max() == 0 for k in WRT[2:]), tag
+        tol = max(2.5e-5, 4 * 2.5e-4 if far else 0.0) * 4
+        try:
+            _check_mix(got, ref, gtol=tol, loss_abs=2e-6)
+        except AssertionError as e:
+            raise AssertionError("%s: %s" % (tag, e))
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("part", ["features", "videos", "fake_p"])
+def test_mixed_loss_partial_gradients(G, L, part, fused):
+    """Discriminator step (videos detached: dF is NULL), generator step (every feature detached: every feature-gradient
+    pointer NULL) and y' alone: the requested gradients match the fp64 ones; the loss node hands back None for the rest."""
+    L.set_option("sinkhorn_fused", fused)
+    wrt = {"features": WRT[2:], "videos": ["fake", "fake_p"], "fake_p": ["fake_p"]}[part]
+    inp = _rand_inputs(48, 258, T=5, J=3, seed=7)
+    t = {k: torch.from_numpy(v).to(DEV) for k, v in inp.items()}
+    for k in wrt:
+        t[k].requires_grad_(True)
+    loss = call(G, t)
+    assert G.last_info["compute_mixed_sinkhorn_loss_fused_sweep"] == bool(fused)
+    node = loss.grad_fn.apply(torch.ones((), device=DEV))          # (7 x None, d[y; y'], six feature gradients)
+    assert all(x is None for x in node[:7])
+    assert (node[7] is None) == (part == "features")
+    feats = ["h_fake", "m_real", "h_real_p", "m_fake", "h_fake_p", "m_real_p"]
+    for k, x in zip(feats, node[8:]):
+        assert (x is None) == (k not in wrt), k
+    grads = dict(zip(wrt, (x.cpu().numpy() for x in torch.autograd.grad(loss, [t[k] for k in wrt]))))
+    ref_val, ref_w, ref_C, ref_g = _ref(inp, wrt)
+    got = (float(loss), grads, [G.last_info["compute_mixed_sinkhorn_loss" + s] for s in ("", "_costs", "_Cmix")], None)
+    _check_mix(got, (ref_val, ref_w, ref_C, ref_g))
