@@ -49,6 +49,10 @@ extern "C" {
                                       /* SAME workspace by a GRAM_SUMS_ONLY call (real / fake are not read)             */
 #define KCCOT_COST_BICAUSAL_TERM_ONLY 64u /* kccot_pairwise_cost3_f32: C3 is input AND output -- add the second causal  */
                                           /* term of the bi-causal loss in place (see below); nothing else is computed  */
+#define KCCOT_COST_CAUSAL_ADD 128u        /* kccot_pairwise_cost_f32: C_out is input AND output -- add one causal term */
+                                          /* in place, in the mixed loss's summation order (see below)                  */
+#define KCCOT_MIXED_CMIX_GIVEN 256u       /* kccot_mixed_sinkhorn_loss_fwd_f32: Cmix is an INPUT -- the cost stage is    */
+                                          /* skipped, the solves run on the given matrices (see below)                  */
 
 /* Sinkhorn stop modes */
 #define KCCOT_STOP_COUNT 0         /* compute_sinkhorn: stop when err<thresh && nits >= Lmin  */
@@ -132,6 +136,16 @@ int kccot_pairwise_cost_f32(const float* x, const float* y, int Bx, int By, int6
                             const float* h1, const float* M1, const float* h2, const float* M2,
                             int T, int J, unsigned flags, float* C_out,
                             void* ws, size_t ws_bytes, kccot_stream_t stream);
+
+/* KCCOT_COST_CAUSAL_ADD adds ONE causal term to a finished block, for a caller that assembles the mixed loss's Cmix from
+ * row blocks of the stacked problem (kccotgan_amd/dist.py, sharded_mixed_sinkhorn_loss):
+ *   C_out[i,j] += sc sum_{t<T-1,q} h1[i,t,q] (M1[j,t+1,q] - M1[j,t,q])          (C_out [Bx,By], h1 [Bx,T,J], M1 [By,T,J])
+ * Each entry is summed as kccot_mixed_sinkhorn_loss_fwd_f32 sums its causal terms: the fp32 difference of M1, the product
+ * (double) h1 * (double) dM accumulated in fp64 in ascending (t, q) order, then ONE fp32 addition of (float)(acc * sc).
+ * Given equal squared distances a block so completed equals the one-call loss's Cmix entry bit for bit.  x, y, K and the
+ * workspace are not read (they may be NULL / 0); h1, M1 and C_out are required, h2 / M2 must be NULL.  Any T >= 1, J >= 1
+ * (T = 1: nothing is added), Bx <= 65535 * 16.  The flag takes no other flag (KCCOT_EINVAL; kccot_last_error() says so);
+ * kccot_pairwise_cost3_f32 and the mixed loss's cost stage refuse it. */
 
 /* The three cost matrices of compute_sinkhorn_loss (gan_utils.py:221-223) in one pass that
  * reads `real` and `fake` once:  C3[0] = xy: modified_cost(real, fake, h_fake, m_real)
@@ -370,7 +384,14 @@ int kccot_mixed_divergence_bwd_f32(const float* gloss, float* gcost3_out, kccot_
  *             dF [2B,K] = d loss / d [y; y'] and the six feature gradients [B,T,J] -- each may be NULL.  Real videos
  *             never receive a gradient (kernel_train.py:252,289).
  * One FFI crossing per direction, no host synchronisation (graph-capturable).
- * Workspace (both directions): kccot_mixed_sinkhorn_loss_workspace_bytes(B, K). */
+ * Workspace (both directions): kccot_mixed_sinkhorn_loss_workspace_bytes(B, K).
+ * KCCOT_MIXED_CMIX_GIVEN (forward only): Cmix [4,B,B] is an INPUT, assembled by the caller (the batch-sharded loss
+ *   gathers it from row blocks, KCCOT_COST_CAUSAL_ADD).  R, F, K, T, J and the six features are not read (they may be
+ *   NULL / 0); the cost stage is skipped and the solves, the combination and, when dCmix_unit is given, the reverse sweep
+ *   run exactly as in the normal call (same outputs, same bits, for the same Cmix).  Workspace: none on the fused path
+ *   (ws may be NULL), kccot_sinkhorn_workspace_bytes(4, B) on the history path -- nothing grows with K.  The flag takes
+ *   no other flag (KCCOT_EINVAL).  The backward is unchanged: after a CMIX_GIVEN forward, call it with dF = NULL (it
+ *   needs R, F and the features of the full call) or form the gradients from d loss / d Cmix yourself. */
 size_t kccot_mixed_sinkhorn_loss_workspace_bytes(int B, int64_t K);
 int kccot_mixed_sinkhorn_loss_fwd_f32(const float* R, const float* F, int B, int64_t K, float sc,
                                       const float* h_fake, const float* m_real, const float* h_real_p,

@@ -156,4 +156,8 @@ int cost3_bwd_loss(const float* g3, const float* gscale, const float* real, cons
 int launch_bicausal_cost_add(float* C3, int B, const float* h_fake, const float* h_real, const float* m_real,
                              const float* m_fake, int T, int J, float sc, hipStream_t st);
 
+// mixed.hip: C [Bx,By] += sc causal(h, M) in place, summed as mixed_cost_finalize sums it (KCCOT_COST_CAUSAL_ADD)
+int launch_mixed_causal_add(float* C, int Bx, int By, const float* h, const float* M, int T, int J, float sc,
+                            hipStream_t st);
+
 }  // namespace kccot

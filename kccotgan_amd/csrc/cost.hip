@@ -353,6 +353,20 @@ extern "C" int kccot_pairwise_cost_f32(const float* x, const float* y, int Bx, i
                                        const float* h1, const float* M1, const float* h2,
                                        const float* M2, int T, int J, unsigned flags, float* C_out,
                                        void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    if (flags & KCCOT_COST_CAUSAL_ADD) {
+        // C_out += sc causal(h1, M1) in place, summed as the mixed loss's finalize sums it (mixed.hip): x, y, K and the
+        // workspace unused
+        if (flags != KCCOT_COST_CAUSAL_ADD)
+            return fail(KCCOT_EINVAL, "pairwise_cost: CAUSAL_ADD takes no other flag (flags=%u)", flags);
+        if (!C_out || !h1 || !M1 || h2 || M2)
+            return fail(KCCOT_EINVAL, "pairwise_cost: CAUSAL_ADD needs C_out, h1 and M1 (and no h2 / M2)");
+        if (Bx <= 0 || By <= 0 || T < 1 || J < 1)
+            return fail(KCCOT_EINVAL, "pairwise_cost: bad shape Bx=%d By=%d T=%d J=%d", Bx, By, T, J);
+        if ((Bx + 15) / 16 > 65535)     // 16 x 16 output tiles; rows on the y grid axis (capped at 65535)
+            return fail(KCCOT_EUNSUPPORTED, "pairwise_cost: CAUSAL_ADD supports Bx <= %d (got %d)", 65535 * 16, Bx);
+        return launch_mixed_causal_add(C_out, Bx, By, h1, M1, T, J, sc, (hipStream_t)stream);
+    }
+    if (flags & KCCOT_MIXED_CMIX_GIVEN) return fail(KCCOT_EINVAL, "pairwise_cost: CMIX_GIVEN does not apply");
     if (!x || !y || !C_out) return fail(KCCOT_EINVAL, "pairwise_cost: null pointer");
     if (Bx <= 0 || By <= 0 || K <= 0)
         return fail(KCCOT_EINVAL, "pairwise_cost: bad shape Bx=%d By=%d K=%lld", Bx, By, (long long)K);
@@ -406,6 +420,8 @@ extern "C" int kccot_pairwise_cost3_f32(const float* real, const float* fake, in
             return fail(KCCOT_EUNSUPPORTED, "pairwise_cost3: BICAUSAL_TERM_ONLY supports B <= %d (got %d)", 65535 * 8, B);
         return launch_bicausal_cost_add(C3, B, h_fake, h_real, m_real, m_fake, T, J, sc, (hipStream_t)stream);
     }
+    if (flags & (KCCOT_COST_CAUSAL_ADD | KCCOT_MIXED_CMIX_GIVEN))
+        return fail(KCCOT_EINVAL, "pairwise_cost3: the CAUSAL_ADD / CMIX_GIVEN flags do not apply (flags=%u)", flags);
     if (!real || !fake || !C3) return fail(KCCOT_EINVAL, "pairwise_cost3: null pointer");
     const int nfeat = (h_fake != nullptr) + (h_real != nullptr) + (m_real != nullptr) + (m_fake != nullptr);
     if (nfeat != 0 && nfeat != 4)   // all four (the loss) or none (plain squared distances, e.g. for the RBF kernel)

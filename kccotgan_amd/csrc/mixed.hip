@@ -52,6 +52,75 @@ __global__ __launch_bounds__(256) void mixed_cost_finalize(const float* __restri
     Cmix[e] = d + (float)(acc * (double)sc);
 }
 
+// KCCOT_COST_CAUSAL_ADD (kccot_pairwise_cost_f32): C[i,j] += sc causal(h, M)[i,j] on a finished block, for a caller that
+// assembles Cmix from row blocks of the stacked problem (kccotgan_amd/dist.py, the batch-sharded mixed loss).  Each entry
+// is summed exactly as mixed_cost_finalize sums it -- the fp32 first difference of M, then (double)h * (double)dM
+// accumulated in fp64 in ascending term order, then ONE (float)(acc * sc) added to C -- so that, given equal distances,
+// the entries equal the single-GPU Cmix bit for bit.  16 x 16 output tiles; a k chunk of CA_KC terms of the 16 h rows and
+// of the 16 first differences of the M rows is staged through LDS (the pattern of causal_tile16, cost_internal.h), all
+// 48 loads of a thread in flight before the one wait; each thread then walks its row and column in order.
+constexpr int CA_TILE = 16;
+constexpr int CA_KC = 256;
+constexpr int CA_PITCH = CA_KC + 4;   // rows 16-byte aligned and 4 banks apart: conflict-free float4 reads
+
+__global__ __launch_bounds__(256) void mixed_causal_add(float* __restrict__ C, const float* __restrict__ h,
+                                                        const float* __restrict__ M, int Bx, int By, int T, int J, float sc) {
+    __shared__ __attribute__((aligned(16))) float sh[CA_TILE * CA_PITCH];
+    __shared__ __attribute__((aligned(16))) float sm[CA_TILE * CA_PITCH];
+    const int i0 = blockIdx.y * CA_TILE, j0 = blockIdx.x * CA_TILE;
+    const int t = threadIdx.x, ti = t >> 4, tj = t & 15;
+    const int KK = (T - 1) * J, TJ = T * J;
+    double acc = 0.0;
+    for (int k0 = 0; k0 < KK; k0 += CA_KC) {
+        // addresses clamped into range (rows to the last one, k to 0): no control dependence on the loads; the selects
+        // below write zeros for the lanes out of range, and a zero term leaves the fp64 sum unchanged
+        const int k = k0 + t;
+        const bool kok = k < KK;
+        const int kc = kok ? k : 0;
+        float hv[CA_TILE], m0[CA_TILE], m1[CA_TILE];
+#pragma unroll
+        for (int r = 0; r < CA_TILE; ++r) {
+            const int ri = (i0 + r < Bx) ? i0 + r : Bx - 1, rj = (j0 + r < By) ? j0 + r : By - 1;
+            hv[r] = h[(int64_t)ri * TJ + kc];
+            const float* mr = M + (int64_t)rj * TJ + kc;
+            m0[r] = mr[0];
+            m1[r] = mr[J];
+        }
+#pragma unroll
+        for (int r = 0; r < CA_TILE; ++r) {
+            sh[r * CA_PITCH + t] = (kok && i0 + r < Bx) ? hv[r] : 0.f;
+            sm[r * CA_PITCH + t] = (kok && j0 + r < By) ? m1[r] - m0[r] : 0.f;
+        }
+        __syncthreads();
+        const int n = KK - k0 < CA_KC ? KK - k0 : CA_KC;
+        const float* hr = sh + ti * CA_PITCH;
+        const float* mr = sm + tj * CA_PITCH;
+#pragma unroll 8
+        for (int kk = 0; kk < n; kk += 4) {
+            const float4 a = *reinterpret_cast<const float4*>(hr + kk);
+            const float4 b = *reinterpret_cast<const float4*>(mr + kk);
+            // the expression of mixed_cost_finalize, term by term
+            acc += (double)a.x * (double)b.x;
+            acc += (double)a.y * (double)b.y;
+            acc += (double)a.z * (double)b.z;
+            acc += (double)a.w * (double)b.w;
+        }
+        __syncthreads();
+    }
+    const int i = i0 + ti, j = j0 + tj;
+    if (i < Bx && j < By) {
+        float* c = C + (int64_t)i * By + j;
+        *c = *c + (float)(acc * (double)sc);
+    }
+}
+
+int launch_mixed_causal_add(float* C, int Bx, int By, const float* h, const float* M, int T, int J, float sc,
+                            hipStream_t st) {
+    hipLaunchKernelGGL(mixed_causal_add, dim3((unsigned)((By + CA_TILE - 1) / CA_TILE), (unsigned)((Bx + CA_TILE - 1) / CA_TILE)),
+                       dim3(256), 0, st, C, h, M, Bx, By, T, J, sc);
+    return launch_status("mixed_causal_add");
+}
+
 struct MixBwdArgs {
     const float* dC;      // [4,B,B] d loss / d Cmix (at dLoss = 1 when gscale != NULL)
     const float* gscale;  // ONE device float or NULL (= 1)
@@ -191,35 +260,52 @@ extern "C" int kccot_mixed_sinkhorn_loss_fwd_f32(const float* R, const float* F,
                                                  float* Cmix, float* u_hist, float* v_hist, float* dCmix_unit,
                                                  float* cost4_out, int32_t* nits_out, float* loss_out, int32_t* ticket,
                                                  void* ws, size_t ws_bytes, kccot_stream_t stream) {
-    if (!R || !F || !h_fake || !m_real || !h_real_p || !m_fake || !h_fake_p || !m_real_p)
+    // KCCOT_MIXED_CMIX_GIVEN: Cmix is an input (assembled by the caller, e.g. from the gathered row blocks of a
+    // batch-sharded loss); R, F, K and the features are not read and the cost stage is skipped
+    const bool given = (flags & KCCOT_MIXED_CMIX_GIVEN) != 0;
+    if (given && flags != KCCOT_MIXED_CMIX_GIVEN)
+        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: CMIX_GIVEN takes no other flag (flags=%u)", flags);
+    if (!given && (!R || !F || !h_fake || !m_real || !h_real_p || !m_fake || !h_fake_p || !m_real_p))
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: null input pointer");
     if (!Cmix || !cost4_out || !nits_out || !loss_out)
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: null output pointer");
-    if (!mix_shape_ok(B, K, T, J) || L < 0 || !(eps > 0.f))
+    if (!(given ? (B > 0 && (int64_t)B * 2 <= (1 << 20)) : mix_shape_ok(B, K, T, J)) || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: bad arguments B=%d K=%lld T=%d J=%d L=%d eps=%g", B,
                     (long long)K, T, J, L, (double)eps);
     if ((u_hist == nullptr) != (v_hist == nullptr) || (dCmix_unit && u_hist))
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: give u_hist and v_hist together, or dCmix_unit, not both");
     if (dCmix_unit && !ticket) return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the fused path needs the ticket");
-    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS | KCCOT_COST_BICAUSAL_TERM_ONLY))
-        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only flags do not apply");
-    if (!ws || ws_bytes < kccot_mixed_sinkhorn_loss_workspace_bytes(B, K))
-        return fail(KCCOT_EWORKSPACE, "mixed_sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
-                    kccot_mixed_sinkhorn_loss_workspace_bytes(B, K));
+    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS | KCCOT_COST_BICAUSAL_TERM_ONLY | KCCOT_COST_CAUSAL_ADD))
+        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only / causal-add flags do not apply");
     hipStream_t st = (hipStream_t)stream;
-    const MixWs w = mix_ws(ws, ws_bytes, B);
-    int rc = kccot_pairwise_cost3_f32(R, F, 2 * B, K, sc, nullptr, nullptr, nullptr, nullptr, 1, 1, flags, w.D3, w.stage,
+    void* stage = ws;
+    size_t stage_bytes = ws_bytes;
+    int rc;
+    if (given) {
+        // only the history path's solves use a workspace (kccot_sinkhorn_workspace_bytes(4, B): nothing grows with K)
+        const size_t need = dCmix_unit ? 0 : kccot_sinkhorn_workspace_bytes(4, B);
+        if (need && (!ws || ws_bytes < need))
+            return fail(KCCOT_EWORKSPACE, "mixed_sinkhorn_loss_fwd: workspace %zu < %zu bytes (CMIX_GIVEN)", ws_bytes, need);
+    } else {
+        if (!ws || ws_bytes < kccot_mixed_sinkhorn_loss_workspace_bytes(B, K))
+            return fail(KCCOT_EWORKSPACE, "mixed_sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
+                        kccot_mixed_sinkhorn_loss_workspace_bytes(B, K));
+        const MixWs w = mix_ws(ws, ws_bytes, B);
+        rc = kccot_pairwise_cost3_f32(R, F, 2 * B, K, sc, nullptr, nullptr, nullptr, nullptr, 1, 1, flags, w.D3, w.stage,
                                       w.stage_bytes, stream);
-    if (rc) return rc;
-    const int64_t n4 = 4 * (int64_t)B * B;
-    hipLaunchKernelGGL(mixed_cost_finalize, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float*)w.D3,
-                       mix_feats(h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p), B, T, J, sc, Cmix);
-    if ((rc = launch_status("mixed_cost_finalize"))) return rc;
+        if (rc) return rc;
+        const int64_t n4 = 4 * (int64_t)B * B;
+        hipLaunchKernelGGL(mixed_cost_finalize, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, (const float*)w.D3,
+                           mix_feats(h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p), B, T, J, sc, Cmix);
+        if ((rc = launch_status("mixed_cost_finalize"))) return rc;
+        stage = w.stage;
+        stage_bytes = w.stage_bytes;
+    }
     if (dCmix_unit)
         return sinkhorn_fused_weighted(Cmix, 4, kMixW, B, eps, L, Lmin, thresh, cost4_out, nits_out, loss_out, ticket,
                                        dCmix_unit, st);
     rc = kccot_sinkhorn_fwd_f32(Cmix, 4, B, eps, L, Lmin, thresh, KCCOT_STOP_COUNT, u_hist, v_hist, cost4_out, nits_out,
-                                nullptr, w.stage, w.stage_bytes, stream);
+                                nullptr, stage, stage_bytes, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(mixed_sinkhorn_combine_fwd, dim3(1), dim3(64), 0, st, (const float*)cost4_out, loss_out);
     return launch_status("mixed_sinkhorn_combine_fwd");

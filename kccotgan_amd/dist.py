@@ -17,6 +17,12 @@ sharded_bicausal_sinkhorn_loss is the same for the bi-causal loss (gan_utils.com
 (or the ksplit finalize) every rank adds the second causal term of each matrix to its replicated C3 (one launch,
 KCCOT_COST_BICAUSAL_TERM_ONLY); step 6 keeps the video gradient and forms the feature gradients with the bi-causal table.
 
+sharded_mixed_sinkhorn_loss is the mixed divergence over two minibatches (gan_utils.compute_mixed_sinkhorn_loss, DESIGN.md
+section 10.1): the four videos are gathered into the stacked R = [x; x'], F = [y; y'] of the single-GPU loss; at B <= 64
+every rank runs the single-GPU loss call itself, above that rank g builds its rows of the four cost matrices from two
+row-block calls on the stacked problem (rows g B/G and B + g B/G), adds their causal terms (KCCOT_COST_CAUSAL_ADD), and
+the gathered Cmix goes to the solves (KCCOT_MIXED_CMIX_GIVEN).
+
 The returned loss is the GLOBAL-batch loss (identical on every rank).  Parameter gradients that
 flow back through a rank's local samples are therefore partial sums: combine them with an
 all-reduce SUM (not the mean DistributedDataParallel applies by default).
@@ -275,8 +281,153 @@ class HipOps:
             df = part[0] + part[1]
         return tuple(df[i, row_begin:row_begin + row_count] for i in range(4))
 
+    # ---- the mixed divergence over two minibatches (gan_utils.compute_mixed_sinkhorn_loss) ----
+    @staticmethod
+    def _mixed_state(B, L, keep, dev):
+        """Output buffers of one mixed forward: costs | loss, iteration counts, and dCmix_unit (fused solve + sweep) or the
+        dual history -- the single-GPU loss's choice (gan_utils._SinkhornLoss)."""
+        Lh = max(int(L), 1)
+        fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
+        st = {"small": _lib.empty((5,), torch.float32, dev), "nits": _lib.empty((8,), torch.int32, dev), "fused": fused,
+              "Lh": Lh, "dCu": None, "uh": None, "vh": None}
+        if fused:
+            st["dCu"] = _lib.empty((4, B, B), torch.float32, dev)
+        elif keep:
+            st["uh"], st["vh"] = _lib.empty((4, Lh, B), torch.float32, dev), _lib.empty((4, Lh, B), torch.float32, dev)
+        return st
+
+    @staticmethod
+    def _mixed_fwd(R, F, B, K, sc, feats, T, J, eps, L, flags, Cmix, st, ws, wsb):
+        small = st["small"]
+        check(lib.kccot_mixed_sinkhorn_loss_fwd_f32(R, F, B, K, sc, *feats, T, J, float(eps), int(L), _LMIN, _THRESH, flags,
+                                                    ptr(Cmix), ptr(st["uh"]), ptr(st["vh"]), ptr(st["dCu"]), ptr(small),
+                                                    ptr(st["nits"]), ptr(small[4:]), ptr(gan_utils._ticket(Cmix.device)),
+                                                    ws, wsb, stream_of(Cmix)), "mixed_sinkhorn_loss_fwd")
+        st["Cmix"], st["eps"] = Cmix, float(eps)
+        return small[4:].reshape(()), st
+
+    @staticmethod
+    def mixed_loss_full(R, F, feats, sc, eps, L, keep):
+        """Replicated regime: the unchanged single-GPU loss call on the gathered stacked R, F [2B,K] and the six gathered
+        features -- Cmix [4,B,B], the loss and the iteration counts are those of compute_mixed_sinkhorn_loss bit for bit."""
+        B, K = R.shape[0] // 2, R.shape[1]
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        st = HipOps._mixed_state(B, L, keep, R.device)
+        ws, wsb = workspace(lib.kccot_mixed_sinkhorn_loss_workspace_bytes(B, K), R)
+        Cmix = _lib.empty((4, B, B), torch.float32, R.device)
+        loss, st = HipOps._mixed_fwd(ptr(R), ptr(F), B, K, sc, [ptr(f) for f in feats], T, J, eps, L, gan_utils.cost_flags,
+                                     Cmix, st, ws, wsb)
+        return loss, Cmix, st
+
+    @staticmethod
+    def mixed_cost_rows(R, F, sc, row_begin, row_count, norms=None):
+        """Rows [row_begin, row_begin + row_count) of the plain scaled distances of the stacked problem, [3, row_count, 2B]
+        = (RF, RR, FF): on the matrix pipe when the gathered stacked `norms` [2B,3] are given, else on the direct kernel.
+        Both entries demand four feature pointers: one zero [2B,1,1] tensor with T = J = 1 (no causal term; d + 0 is exact)."""
+        zero = _zeros_feat(R.shape[0], R.device)
+        return HipOps.cost3_rows(R, F, zero, zero, zero, zero, sc, row_begin, row_count, norms)
+
+    @staticmethod
+    def causal_add(C, h_rows, M, sc):
+        """C [Bx,By] += sc causal(h_rows, M) in place (KCCOT_COST_CAUSAL_ADD: the single-GPU Cmix's summation order)."""
+        Bx, By = C.shape
+        T, J = h_rows.shape[1], h_rows.shape[2]
+        check(lib.kccot_pairwise_cost_f32(None, None, Bx, By, 0, sc, ptr(h_rows.contiguous()), ptr(M), None, None, T, J,
+                                          _lib.COST_CAUSAL_ADD, ptr(C), None, 0, stream_of(C)), "pairwise_cost(causal add)")
+        return C
+
+    @staticmethod
+    def mixed_loss_given(Cmix, eps, L, keep):
+        """Row-block regime: the four solves, the combination and (fused) the reverse sweep on the gathered Cmix
+        (KCCOT_MIXED_CMIX_GIVEN); n > 128 runs the multi-CU solver inside the library."""
+        B = Cmix.shape[1]
+        st = HipOps._mixed_state(B, L, keep, Cmix.device)
+        ws, wsb = (None, 0) if st["fused"] else workspace(lib.kccot_sinkhorn_workspace_bytes(4, B), Cmix)
+        return HipOps._mixed_fwd(None, None, B, 0, 0.0, [None] * 6, 1, 1, eps, L, _lib.MIXED_CMIX_GIVEN, Cmix, st, ws, wsb)
+
+    @staticmethod
+    def mixed_dcmix(st, g):
+        """d loss / d Cmix at the upstream scalar g: dCmix_unit * g (fused), or the reverse sweep of the four problems with
+        gcost4 = g {1, 1, -1, -1} formed on the device (history)."""
+        g = g.reshape(1).float()
+        if st["fused"]:
+            return st["dCu"] * g
+        Cmix = st["Cmix"]
+        B = Cmix.shape[1]
+        gc = g * _mix_weights(g.device)
+        dC = _lib.empty_like(Cmix)
+        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(4, B), Cmix)
+        check(lib.kccot_sinkhorn_bwd_f32(ptr(Cmix), ptr(st["uh"]), ptr(st["vh"]), ptr(st["nits"]), 4, B, st["eps"], st["Lh"],
+                                         ptr(gc), ptr(dC), ws, wsb, stream_of(Cmix)), "sinkhorn_bwd")
+        return dC
+
+    @staticmethod
+    def mixed_dfake_rows(dCmix, R, F, sc, row_begin, row_count):
+        """The video gradients of this rank's rows of y and y': g3 [3,2B,2B] of the stacked problem from dCmix (the block
+        map of mixed_cost_bwd: dC1 -> RF (0,0), dC2 -> RF (1,1), dC4 -> FF (0,1)), then two row calls of the cost backward."""
+        B = dCmix.shape[1]
+        g3 = torch.zeros((3, 2 * B, 2 * B), dtype=torch.float32, device=dCmix.device)
+        g3[0, :B, :B] = dCmix[0]
+        g3[0, B:, B:] = dCmix[1]
+        g3[2, :B, B:] = dCmix[3]
+        return (HipOps.dfake_rows(g3, R, F, sc, row_begin, row_count),
+                HipOps.dfake_rows(g3, R, F, sc, B + row_begin, row_count))
+
+    @staticmethod
+    def mixed_feature_grads(dCmix, g, st, R, F, feats, sc, row_begin, row_count, whole=False):
+        """The six feature gradients of this rank's rows (h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p), formed for
+        all B samples and sliced.  whole=True (replicated regime): the single-GPU loss's backward with dF = NULL (after a
+        fused forward with its dCmix_unit and g, else with dCmix at g = 1: the single-GPU call's operands and bits).
+        Otherwise one kccot_pairwise_cost_bwd_f32 per block with dx = dy = NULL -- nothing that grows with K:
+        dh_fake <- C1, dm_real <- C1 + C3, dh_real_p <- C3, dm_fake <- C4, dh_fake_p <- C2 + C4, dm_real_p <- C2."""
+        B, K = R.shape[0] // 2, R.shape[1]
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        dev, stm = R.device, stream_of(R)
+        if whole:
+            df = _lib.empty((6, B, T, J), torch.float32, dev)
+            ws, wsb = workspace(lib.kccot_mixed_sinkhorn_loss_workspace_bytes(B, K), R)
+            gl, dCu = (g.reshape(1).float().contiguous(), st["dCu"]) if st["fused"] else (_one(dev), dCmix)
+            check(lib.kccot_mixed_sinkhorn_loss_bwd_f32(ptr(gl), ptr(R), ptr(F), B, K, sc, *(ptr(f) for f in feats), T, J,
+                                                        st["eps"], st["Lh"], None, None, None, None, ptr(dCu), None,
+                                                        *(ptr(d) for d in df), ws, wsb, stm),
+                  "mixed_sinkhorn_loss_bwd(feature gradients)")
+            out = [df[i] for i in range(6)]
+        else:
+            h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p = feats
+            part = _lib.empty((4, 2, B, T, J), torch.float32, dev)            # [block][dh, dM]
+            for k, (h, M) in enumerate(((h_fake, m_real), (h_fake_p, m_real_p), (h_real_p, m_real), (h_fake_p, m_fake))):
+                check(lib.kccot_pairwise_cost_bwd_f32(ptr(dCmix[k]), ptr(R), ptr(F), B, B, K, sc, ptr(h), ptr(M), T, J, 0,
+                                                      None, None, ptr(part[k, 0]), ptr(part[k, 1]), None, 0, stm),
+                      "pairwise_cost_bwd(mixed block)")
+            out = [part[0, 0], part[0, 1] + part[2, 1], part[2, 0], part[3, 1], part[1, 0] + part[3, 0], part[1, 1]]
+        return tuple(d[row_begin:row_begin + row_count] for d in out)
+
+
+# the operations the sharded mixed loss needs of an ops object (an injected one must provide all of them)
+MIXED_OPS = ("replicate_costs", "mixed_loss_full", "mixed_cost_rows", "causal_add", "mixed_loss_given", "mixed_dcmix",
+             "mixed_dfake_rows", "mixed_feature_grads")
 
 _ones = {}
+_zero_feats = {}
+_mix_w = {}
+
+
+def _zeros_feat(n, device):
+    """A zero [n,1,1] feature tensor per (n, device): the four feature pointers of a row-block call without causal terms."""
+    t = _zero_feats.get((n, device))
+    if t is None:
+        t = torch.zeros((n, 1, 1), dtype=torch.float32, device=device)
+        _zero_feats[(n, device)] = t
+    return t
+
+
+def _mix_weights(device):
+    """{1, 1, -1, -1} on the device: d loss / d cost4 of (W1 + W2) - W3 - W4 at g = 1."""
+    t = _mix_w.get(device)
+    if t is None:
+        t = torch.tensor([1.0, 1.0, -1.0, -1.0], dtype=torch.float32, device=device)
+        _mix_w[device] = t
+    return t
 
 
 def _one(device):
@@ -692,6 +843,138 @@ def _sharded_loss(f_real_l, f_fake_l, scaling_coef, h_fake_l, m_real_l, h_real_l
                               feat(m_fake_l), float(scaling_coef), float(epsilon), int(L), group, ops, bicausal).reshape(())
 
 
+# ---- the mixed divergence over two minibatches ----------------------------------------
+def _gather_into(out, t, group):
+    """all-gather the equally shaped [Bl, ...] shards straight into `out` [G Bl, ...] (a contiguous view, e.g. one half of
+    a stacked buffer): RCCL writes it in place (also at world size 1); gloo is staged through the host."""
+    world = dist.get_world_size(group)
+    t = t.contiguous()
+    if dist.get_backend(group) == "nccl":
+        dist.all_gather_into_tensor(out, t, group=group)
+    elif world == 1:
+        out.copy_(t)
+    else:
+        out.copy_(all_gather_cat(t, group))
+
+
+class _ShardedMixedLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_l, y_l, xp_l, yp_l, h_fake_l, m_real_l, h_real_p_l, m_fake_l, h_fake_p_l, m_real_p_l, sc, eps, L,
+                group, ops):
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        Bl, K = x_l.shape
+        B = Bl * world
+        dev, dt = x_l.device, x_l.dtype
+        keep = any(ctx.needs_input_grad[1:10])
+        whole = ops.replicate_costs(B, K)           # the whole Cmix on every rank (B <= 64): the single-GPU loss call
+        _mark("start")
+        # row blocks on the matrix pipe need x.x, e.e, x.e of every sample of the stacked problem: each rank's own rows of
+        # (x, y) and (x', y'), gathered into the two halves of [2B,3] (stacked order)
+        norms = None
+        if (not whole and hasattr(ops, "row_norms") and ops.rows_gram_supported(Bl, 2 * B, K)
+                and os.environ.get("KCCOT_DIST_ROWS") != "direct"):
+            norms = torch.empty((2 * B, 3), dtype=torch.float64, device=dev)
+            _gather_into(norms[:B], ops.row_norms(x_l, y_l), group)
+            _gather_into(norms[B:], ops.row_norms(xp_l, yp_l), group)
+        # the four videos straight into the halves of the stacked R = [x; x'], F = [y; y'] (no torch.cat)
+        R = torch.empty((2 * B, K), dtype=dt, device=dev)
+        F = torch.empty((2 * B, K), dtype=dt, device=dev)
+        for out, t in ((R[:B], x_l), (R[B:], xp_l), (F[:B], y_l), (F[B:], yp_l)):
+            _gather_into(out, t, group)
+        # the six [Bl,T,J] feature shards travel as one message
+        fl = (h_fake_l, m_real_l, h_real_p_l, m_fake_l, h_fake_p_l, m_real_p_l)
+        allf = all_gather_cat(torch.stack(fl, dim=1), group)
+        feats = tuple(allf[:, i].contiguous() for i in range(6))
+        _mark("exchange_inputs")
+        if whole:
+            # one call: the cost stage, the four solves and (fused) the reverse sweep -- the phase holds the solves too
+            loss, Cmix, state = ops.mixed_loss_full(R, F, feats, sc, eps, L, keep)
+            _mark("cost_replicated")
+        else:
+            h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p = feats
+            top = ops.mixed_cost_rows(R, F, sc, rank * Bl, Bl, norms)          # rows I of (RF, RR, FF)
+            bot = ops.mixed_cost_rows(R, F, sc, B + rank * Bl, Bl, norms)      # rows B + I
+            # this rank's rows of C1 = RF[0:B,0:B], C2 = RF[B:,B:], C3 = RR[0:B,B:], C4 = FF[0:B,B:]
+            blk = torch.stack([top[0, :, :B], bot[0, :, B:], top[1, :, B:], top[2, :, B:]])     # [4,Bl,B]
+            _mark("cost_rows")
+            lo = slice(rank * Bl, (rank + 1) * Bl)
+            for k, (h, M) in enumerate(((h_fake, m_real), (h_fake_p, m_real_p), (h_real_p, m_real), (h_fake_p, m_fake))):
+                c = ops.causal_add(blk[k], h[lo], M, sc)
+                if c.data_ptr() != blk[k].data_ptr():
+                    blk[k] = c
+            _mark("causal_add")
+            Cmix = all_gather_cat(blk.transpose(0, 1).contiguous(), group).transpose(0, 1).contiguous()   # [4,B,B]
+            _mark("exchange_costs")
+            loss, state = ops.mixed_loss_given(Cmix, eps, L, keep)
+            _mark("sinkhorn_fwd")
+        if ops is HipOps:
+            nits, executed = state["nits"][:4], state["nits"][4:]
+            last_info["nits"], last_info["nits_executed"] = nits, executed
+            last_info["Cmix"] = Cmix                 # the replicated cost matrices
+            tag = "compute_mixed_sinkhorn_loss"      # raise_if_solver_aborted((tag,)) covers the sharded loss too
+            gan_utils.last_info[tag], gan_utils.last_info[tag + "_executed"] = nits, executed
+        ctx.saved_state = (state, R, F, feats)
+        ctx.cfg = (sc, rank * Bl, Bl, ops, whole)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        state, R, F, feats = ctx.saved_state
+        sc, row_begin, Bl, ops, whole = ctx.cfg
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+        g = g.reshape(())
+        _mark("between_fwd_and_bwd")
+        dCmix = ops.mixed_dcmix(state, g)
+        _mark("sinkhorn_bwd")
+        dy, dyp = ops.mixed_dfake_rows(dCmix, R, F, sc, row_begin, Bl)
+        df = ops.mixed_feature_grads(dCmix, g, state, R, F, feats, sc, row_begin, Bl, whole)
+        _mark("gradient")
+        return (None, dy, None, dyp) + tuple(df) + (None,) * 5
+
+
+def sharded_mixed_sinkhorn_loss(f_real_l, f_fake_l, f_real_p_l, f_fake_p_l, scaling_coef, h_fake_l, m_real_l, h_real_p_l,
+                                m_fake_l, h_fake_p_l, m_real_p_l, group=None, ops=None, epsilon=1.0, L=100, protocol=None):
+    """gan_utils.compute_mixed_sinkhorn_loss, (W(x,y) + W(x',y')) - W(x,x') - W(y,y'), of the GLOBAL batch from per-rank
+    shards: the arguments are this rank's [B/G, ...] slices of x, y, x', y' and of the six features, in the order of the
+    single-GPU function; epsilon / L as sharded_sinkhorn_loss.  Returns the same loss on every rank.  Differentiable
+    w.r.t. both fake shards and all six feature shards; a real shard that requires a gradient raises NotImplementedError.
+
+    The four videos are all-gathered into the stacked R = [x; x'], F = [y; y'] of the single-GPU loss.  B <= 64
+    (``ops.replicate_costs``; KCCOT_DIST_ROW_BLOCKS=1 forces the row blocks): every rank runs the single-GPU loss call on
+    them -- Cmix, loss and iteration counts bit-identical to compute_mixed_sinkhorn_loss.  Above: rank g forms its rows of
+    the four cost matrices from two row-block calls on the stacked problem (rows g B/G and B + g B/G; the matrix pipe when
+    the shape allows it), adds their causal terms in the single-GPU summation order (KCCOT_COST_CAUSAL_ADD), all-gathers
+    them into Cmix [4,B,B], and solves on it (KCCOT_MIXED_CMIX_GIVEN).  Backward: each rank forms the gradient rows of
+    its samples from the replicated d loss / d Cmix, no communication.
+
+    Records gan_utils.last_info["compute_mixed_sinkhorn_loss"] and ``..._executed`` (so raise_if_solver_aborted covers
+    it) and dist.last_info["Cmix"].  protocol: "gather" (default) or "auto" (= "gather"); "ksplit" is not implemented for
+    this loss.  KCCOT_DIST_GATHER_CHUNKS does not apply to it.  Injected ``ops`` must provide MIXED_OPS."""
+    ops = ops or HipOps
+    missing = [n for n in MIXED_OPS if not hasattr(ops, n)]
+    if missing:
+        raise NotImplementedError("sharded mixed loss: the ops %r lack %s" % (getattr(ops, "__name__", ops), ", ".join(missing)))
+    protocol = protocol or os.environ.get("KCCOT_DIST_PROTOCOL", "gather")
+    if protocol == "ksplit":
+        raise NotImplementedError("sharded mixed loss: the ksplit protocol is not implemented for the mixed divergence")
+    if protocol not in ("auto", "gather"):
+        raise ValueError("unknown protocol %r" % (protocol,))
+    if f_real_l.requires_grad or f_real_p_l.requires_grad:
+        raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+    Bl = f_real_l.shape[0]
+    vids = (f_real_l, f_fake_l, f_real_p_l, f_fake_p_l)
+    if any(v.shape != vids[0].shape for v in vids[1:]):
+        raise ValueError("the four video shards must have the same shape: %s" % ([tuple(v.shape) for v in vids],))
+    fl = (h_fake_l, m_real_l, h_real_p_l, m_fake_l, h_fake_p_l, m_real_p_l)
+    if any(t.dim() != 3 or t.shape != fl[0].shape for t in fl) or fl[0].shape[0] != Bl:
+        raise ValueError("the six feature shards must all be [B/G,T,J] with the videos' B/G; got %s" % ([tuple(t.shape) for t in fl],))
+    cast = (lambda v: v.float()) if ops is HipOps else (lambda v: v)   # the HIP kernels are fp32
+    flat = lambda v: cast(v.reshape(Bl, -1)).contiguous()
+    return _ShardedMixedLoss.apply(*(flat(v) for v in vids), *(cast(t).contiguous() for t in fl), float(scaling_coef),
+                                   float(epsilon), int(L), group, ops).reshape(())
+
+
 # ---- helpers used by bench.py ---------------------------------------------------------------------
 def shard_batch(t, rank, world):
     """Slice the leading (batch) axis of every tensor of a dict into this rank's shard."""
@@ -710,4 +993,17 @@ def sharded_loss_step(shard, sc, group=None, epsilon=1.0, L=100, protocol=None, 
     loss = fn(shard["real"], shard["fake"], sc, shard["h_fake"], shard["m_real"], shard["h_real"], shard["m_fake"], group,
               epsilon=epsilon, L=L, protocol=protocol)
     grads = torch.autograd.grad(loss, [shard[k] for k in ("fake", "h_fake", "h_real", "m_real", "m_fake")])
+    return loss, grads
+
+
+_MIXED_WRT = ("fake", "fake_p", "h_fake", "m_real", "h_real_p", "m_fake", "h_fake_p", "m_real_p")
+
+
+def sharded_mixed_loss_step(shard, sc, group=None, epsilon=1.0, L=100):
+    """sharded_mixed_sinkhorn_loss of one rank's shard dict (real, fake, real_p, fake_p and the six features) and its
+    gradients w.r.t. _MIXED_WRT.  Both real videos are detached here, whatever the caller passed."""
+    loss = sharded_mixed_sinkhorn_loss(shard["real"].detach(), shard["fake"], shard["real_p"].detach(), shard["fake_p"], sc,
+                                       shard["h_fake"], shard["m_real"], shard["h_real_p"], shard["m_fake"], shard["h_fake_p"],
+                                       shard["m_real_p"], group, epsilon=epsilon, L=L)
+    grads = torch.autograd.grad(loss, [shard[k] for k in _MIXED_WRT])
     return loss, grads

@@ -19,6 +19,10 @@ bit-identical (tests/test_gpu_parity.py::test_graphed_loss_is_bit_identical).
                         of this rank's rows -- the backward needs no communication) are one graph each.  Issued
                         eagerly from Python the sharded step costs 0.36 ms of host time for 0.22 ms of kernels.
 
+``GraphedShardedMixedStep`` -- the same for ``dist.sharded_mixed_sinkhorn_loss`` (the mixed divergence over two
+                        minibatches): one graph after the input gathers at B <= 64, else graph A (the two stacked row-block
+                        calls + causal adds) -> all-gather -> graph B (solves, sweep, gradients).
+
 All require fixed shapes; inputs are copied into the static buffers on every call unless the
 caller writes into ``.static`` directly.
 """
@@ -355,3 +359,146 @@ class GraphedKSplitStep:
         for k, v in zip(_FEATS, self._fg):
             self.grads[k] = v.reshape(self._shapes[k])
         return self.loss, self.grads
+
+
+_MIXED_FEATS = ("h_fake", "m_real", "h_real_p", "m_fake", "h_fake_p", "m_real_p")
+_MIXED_VIDS = ("real", "fake", "real_p", "fake_p")
+
+
+class GraphedShardedMixedStep:
+    """Forward + backward of ``dist.sharded_mixed_sinkhorn_loss`` at dLoss = 1 for one rank.  ``shard``: this rank's
+    [B/G, ...] slices of real, fake, real_p, fake_p and the six features.  The gathers of the inputs (straight into the
+    halves of the stacked R = [x; x'], F = [y; y']) stay ordinary collectives; for B <= 64 (``HipOps.replicate_costs``)
+    everything after them is ONE graph, above it graph A (the two row-block calls on the stacked problem and the four
+    causal adds) -> all-gather of the row blocks -> graph B (the solves, the reverse sweep, the gradients of this rank's
+    rows).  The eager path's kernels (``dist._ShardedMixedLoss``) in the eager order: bit-identical results.
+    ``step(fake=..., h_fake=...)`` (or calling the object) copies the given LOCAL shards into the static buffers and
+    replays; returns (loss, grads) as static tensors, grads keyed by fake, fake_p and the six feature names."""
+
+    def __init__(self, shard, scaling_coef, group=None, epsilon=1.0, L=100, warmup=2):
+        import torch.distributed as dist
+        from . import dist as kd
+        self._kd, self._dist, self.group = kd, dist, group
+        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+        Bl = shard["real"].shape[0]
+        dev = shard["real"].device
+        flat = lambda v: v.detach().reshape(Bl, -1).float().contiguous().clone()
+        self.local = {k: flat(shard[k]) for k in _MIXED_VIDS}
+        self.local["feats"] = torch.stack([shard[k].detach().float() for k in _MIXED_FEATS], dim=1).contiguous()
+        self._shapes = {k: tuple(shard[k].shape) for k in _MIXED_VIDS + _MIXED_FEATS}
+        B, K = Bl * self.world, self.local["real"].shape[1]
+        T, J = self.local["feats"].shape[2], self.local["feats"].shape[3]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self.R, self.F, self.feats = new(2 * B, K), new(2 * B, K), new(B, 6, T, J)
+        self._f = [new(B, T, J) for _ in range(6)]
+        self._blk_t, self._Cg = new(Bl, 4, B), new(B, 4, B)
+        self._one = torch.ones((), device=dev)
+        self._cfg = (float(scaling_coef), float(epsilon), int(L), self.rank * Bl, Bl, B)
+        self.replicated = kd.HipOps.replicate_costs(B, K)
+        self.use_norms = (not self.replicated and kd.HipOps.rows_gram_supported(Bl, 2 * B, K)
+                          and os.environ.get("KCCOT_DIST_ROWS") != "direct")
+        if self.use_norms:
+            self.norms = torch.zeros((2 * B, 3), dtype=torch.float64, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                        # warm-up off the capture: workspaces, ticket, allocator
+            for _ in range(warmup):
+                self._gather_inputs()
+                self._seg_a()
+                if not self.replicated:
+                    self._gather(self._Cg, self._blk_t)
+                self._seg_b()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph_a = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph_a, capture_error_mode="thread_local"):
+            self._seg_a()
+            if self.replicated:
+                self.loss, self.grads, nits = self._seg_b()
+        if not self.replicated:
+            self.graph_b = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph_b, capture_error_mode="thread_local"):
+                self.loss, self.grads, nits = self._seg_b()
+        self.nits, self.nits_executed = nits[:4], nits[4:]
+
+    def _gather(self, out, local):
+        if self._dist.get_backend(self.group) == "nccl":    # also at world size 1: the same call sequence
+            self._dist.all_gather_into_tensor(out, local, group=self.group)
+        elif self.world == 1:
+            out.copy_(local)
+        else:                                                # gloo rehearsal: staged through the host
+            out.copy_(self._kd.all_gather_cat(local, self.group))
+
+    def _gather_inputs(self):
+        B = self._cfg[5]
+        H = self._kd.HipOps
+        if self.use_norms:
+            self._gather(self.norms[:B], H.row_norms(self.local["real"], self.local["fake"]))
+            self._gather(self.norms[B:], H.row_norms(self.local["real_p"], self.local["fake_p"]))
+        pairs = ((self.R[:B], "real"), (self.R[B:], "real_p"), (self.F[:B], "fake"), (self.F[B:], "fake_p"),
+                 (self.feats, "feats"))
+        # RCCL: the five all-gathers as ONE coalesced group, as GraphedShardedStep does; sequential calls if this torch
+        # build has no coalesced all-gather
+        if self._dist.get_backend(self.group) == "nccl" and getattr(self, "_coalesce", True):
+            try:
+                with self._dist._coalescing_manager(group=self.group):
+                    for out, k in pairs:
+                        self._dist.all_gather_into_tensor(out, self.local[k], group=self.group)
+                self._coalesce = True
+                return
+            except Exception:
+                if getattr(self, "_coalesce", None) is True:
+                    raise                                   # it worked before: a real failure
+                self._coalesce = False
+        for out, k in pairs:
+            self._gather(out, self.local[k])
+
+    def _seg_a(self):
+        sc, eps, L, row_begin, Bl, B = self._cfg
+        H = self._kd.HipOps
+        for i in range(6):
+            self._f[i].copy_(self.feats[:, i])
+        if self.replicated:
+            return
+        h_fake, m_real, h_real_p, m_fake, h_fake_p, m_real_p = self._f
+        norms = self.norms if self.use_norms else None
+        top = H.mixed_cost_rows(self.R, self.F, sc, row_begin, Bl, norms)
+        bot = H.mixed_cost_rows(self.R, self.F, sc, B + row_begin, Bl, norms)
+        blk = torch.stack([top[0, :, :B], bot[0, :, B:], top[1, :, B:], top[2, :, B:]])
+        lo = slice(row_begin, row_begin + Bl)
+        for k, (h, M) in enumerate(((h_fake, m_real), (h_fake_p, m_real_p), (h_real_p, m_real), (h_fake_p, m_fake))):
+            H.causal_add(blk[k], h[lo], M, sc)
+        self._blk_t.copy_(blk.transpose(0, 1))
+
+    def _seg_b(self):
+        sc, eps, L, row_begin, Bl, B = self._cfg
+        H = self._kd.HipOps
+        if self.replicated:
+            _, Cmix, st = H.mixed_loss_full(self.R, self.F, self._f, sc, eps, L, True)
+        else:
+            Cmix = self._Cg.transpose(0, 1).contiguous()
+            _, st = H.mixed_loss_given(Cmix, eps, L, True)
+        loss = st["small"][4:].reshape(())
+        dCmix = H.mixed_dcmix(st, self._one)
+        dy, dyp = H.mixed_dfake_rows(dCmix, self.R, self.F, sc, row_begin, Bl)
+        df = H.mixed_feature_grads(dCmix, self._one, st, self.R, self.F, self._f, sc, row_begin, Bl, self.replicated)
+        self.Cmix = Cmix
+        g = {"fake": dy, "fake_p": dyp}
+        g.update(zip(_MIXED_FEATS, df))
+        return loss, {k: v.reshape(self._shapes[k]) for k, v in g.items()}, st["nits"]
+
+    def __call__(self, **inputs):
+        with torch.no_grad():
+            for k, v in inputs.items():
+                if k in _MIXED_VIDS:
+                    self.local[k].copy_(v.reshape(self.local[k].shape))
+                else:
+                    self.local["feats"][:, _MIXED_FEATS.index(k)].copy_(v)
+            self._gather_inputs()
+            self.graph_a.replay()
+            if not self.replicated:
+                self._gather(self._Cg, self._blk_t)
+                self.graph_b.replay()
+        return self.loss, self.grads
+
+    step = __call__

@@ -13,7 +13,9 @@ Data-parallel use (one process per GPU, torch.distributed over RCCL): pass ``gro
 feeds its shard of the batch, the loss is the GLOBAL-batch divergence assembled by
 ``kccotgan_amd.dist`` and parameter gradients are all-reduced with SUM (the loss is replicated,
 each rank holds the partial derivative through its own samples).  ``bi_causal=True`` runs there too
-(``dist.sharded_bicausal_sinkhorn_loss``, GPU devices only); ``mixed_sinkhorn=True`` has no sharded form.
+(``dist.sharded_bicausal_sinkhorn_loss``, GPU devices only).  ``mixed_sinkhorn=True`` with a ``group`` is still
+refused: the loss itself has a batch-sharded form (``dist.sharded_mixed_sinkhorn_loss``, ``dist.sharded_mixed_loss_step``),
+but the trainer does not call it yet -- its second real minibatch and the eight differentiated shards are not wired.
 
 ``sample`` is the test-time autoregressive loop (kernel_train.py:340-347), ``fit`` the loop body around the two
 steps (:295-330): per-iteration sigma (annealed or fixed, :308-311), the scalar log ``pM`` / ``Sinkhorn Loss``
@@ -99,7 +101,8 @@ class KCCOTTrainer:
         if mixed_sinkhorn and bi_causal:
             raise ValueError("mixed_sinkhorn=True and bi_causal=True are exclusive loss modes (kernel_train.py:179-184)")
         if mixed_sinkhorn and data_parallel:
-            raise NotImplementedError("mixed_sinkhorn=True has no batch-sharded (data-parallel) form")
+            raise NotImplementedError("mixed_sinkhorn=True: the data-parallel trainer does not run the mixed loss yet; the "
+                                      "loss itself has a batch-sharded form, dist.sharded_mixed_sinkhorn_loss")
         if bi_causal and data_parallel and torch.device(device).type != "cuda":
             # the batch-sharded bi-causal loss (dist.sharded_bicausal_sinkhorn_loss) runs on the HIP library only
             raise NotImplementedError("bi_causal=True with data parallelism: the sharded bi-causal loss runs on the GPU only "
