@@ -1763,11 +1763,15 @@ __global__ __launch_bounds__(256) void maxnorm_bwd_partial_v4(const float* __res
 
 // ---- the sparse half of the folded backward (WALK_ADJS) ----------------------------------------------------------------
 // One workgroup.  Adds the workgroups' records up (res[0] = sum g * out in fp64, res[1] = number of arg-max elements),
-// and, when there are at most SMOOTH_MAX_TIES of them (one, for any real video), subtracts corr * A^T [out == 1] from din:
-// per arg-max element the (2R+1)^axes REFLECT neighbours, one thread per tap combination, taps that fold onto the same
-// position merged first (one writer per position), the elements in index order one after the other: deterministic.
-// More arg-max elements than that (a saturated still image: a whole region ties) -> *dense = 1 and nothing is touched;
+// and, when there are at most SMOOTH_MAX_TIES of them, subtracts corr * A^T [out == 1] from din: per arg-max element the
+// (2R+1)^axes REFLECT neighbours, one thread per tap combination, taps that fold onto the same position merged first (one
+// writer per position), the elements in index order one after the other: deterministic.
+// More arg-max elements than that, or more than TIE_PER_WG in one workgroup's record -> *dense = 1 and nothing is touched;
 // the guarded dense chain behind this launch (the round-2 kernels with WalkArgs::run_if) then recomputes din the plain way.
+// Real videos take that path often: pixels are k/255 and BAIR / GQN frames have saturated regions.  At any sigma every
+// voxel whose stencil lies inside a saturated region ties at the maximum, and once the annealed sigma falls below ~0.15 the
+// taps beyond the centre drop under fp32's resolution (to 0 at 0.03) and EVERY saturated voxel ties: thousands per batch.
+// A unique maximum needs a unique brightest neighbourhood (tests/test_gpu_smoothing_fp64.py holds all three cases).
 struct FixupArgs {
     const TieRec* ties; int nrec;
     const float* mx; float* res; int* dense; float* din;
