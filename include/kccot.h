@@ -53,6 +53,8 @@ extern "C" {
                                           /* in place, in the mixed loss's summation order (see below)                  */
 #define KCCOT_MIXED_CMIX_GIVEN 256u       /* kccot_mixed_sinkhorn_loss_fwd_f32: Cmix is an INPUT -- the cost stage is    */
                                           /* skipped, the solves run on the given matrices (see below)                  */
+#define KCCOT_COST_RBF_SUM 512u           /* kccot_pairwise_cost_f32: C_out is input AND output -- squared distances    */
+                                          /* become exp(-sc * C_out) in place, their fp64 sum goes to ws (see below)    */
 
 /* Sinkhorn stop modes */
 #define KCCOT_STOP_COUNT 0         /* compute_sinkhorn: stop when err<thresh && nits >= Lmin  */
@@ -146,6 +148,22 @@ int kccot_pairwise_cost_f32(const float* x, const float* y, int Bx, int By, int6
  * workspace are not read (they may be NULL / 0); h1, M1 and C_out are required, h2 / M2 must be NULL.  Any T >= 1, J >= 1
  * (T = 1: nothing is added), Bx <= 65535 * 16.  The flag takes no other flag (KCCOT_EINVAL; kccot_last_error() says so);
  * kccot_pairwise_cost3_f32 and the mixed loss's cost stage refuse it. */
+
+/* KCCOT_COST_RBF_SUM turns a finished block of plain squared distances into its Gaussian-kernel block and sums it, for a
+ * caller that assembles the kernel-MMD of kccot_rbf_mmd_f32 from row blocks (kccotgan_amd/dist.py, sharded_rbf_mmd2; an
+ * extension with no reference behaviour, sklearn's rbf_kernel semantics).  C_out [Bx,By] holds squared distances on entry
+ * (by any route); in place,
+ *   C_out[i,j] = expf(-sc * C_out[i,j])                   (sc carries gamma; the expression of kccot_rbf_mmd_f32, so equal
+ *                                                          distances give the same kernel values bit for bit)
+ *   ((double*)ws)[0] = sum_{i,j} C_out[i,j]               (the fp32 kernel values added in fp64)
+ * One wave per 4 x 64 tile of the block ([64,512]: 128 workgroups), one fp64 partial per tile stored behind ws[0], and a
+ * one-workgroup second launch that adds the partials in a fixed order: no atomics, so two calls and a graph replay give
+ * identical bits.  Workspace: 8-byte aligned, ws_bytes >= kccot_pairwise_cost_workspace_bytes(Bx, By, 1) (KCCOT_EWORKSPACE
+ * below it); of it the call writes the first 8 (1 + ceil(Bx / 4) ceil(By / 64)) bytes and nothing else.  x, y, K, the
+ * features, T and J are not read (they may be NULL / 0).  C_out == NULL, ws == NULL, Bx <= 0, By <= 0 or sc <= 0 are
+ * KCCOT_EINVAL; Bx <= 65535 * 4.  The flag takes no other flag (KCCOT_EINVAL, no launch; kccot_last_error() says so);
+ * kccot_pairwise_cost3_f32 and the loss entry points refuse it.  Backward: kccot_rbf_mmd_bwd_f32 on the gathered kernel
+ * blocks [3,B,B], then kccot_pairwise_cost3_bwd_rows_f32. */
 
 /* The three cost matrices of compute_sinkhorn_loss (gan_utils.py:221-223) in one pass that
  * reads `real` and `fake` once:  C3[0] = xy: modified_cost(real, fake, h_fake, m_real)

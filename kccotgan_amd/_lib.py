@@ -18,7 +18,7 @@ EINVAL, EUNSUPPORTED, EWORKSPACE, EABORTED = -1, -2, -3, -4
 
 COST_SAME, COST_FORCE_DIRECT, COST_FORCE_MFMA, COST_PARTIAL_ONLY = 1, 2, 4, 8
 COST_GRAM_SUMS_ONLY, COST_FROM_GRAM_SUMS, COST_BICAUSAL_TERM_ONLY = 16, 32, 64
-COST_CAUSAL_ADD, MIXED_CMIX_GIVEN = 128, 256
+COST_CAUSAL_ADD, MIXED_CMIX_GIVEN, COST_RBF_SUM = 128, 256, 512
 STOP_COUNT, STOP_INDEX = 0, 1
 SMOOTH_T, SMOOTH_H, SMOOTH_W, SMOOTH_NO_DIVIDE, SMOOTH_EXTERNAL_MAX = 1, 2, 4, 16, 32
 SMOOTH_STATS_ONLY, SMOOTH_EXTERNAL_STATS = 64, 128

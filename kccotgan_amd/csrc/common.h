@@ -160,4 +160,9 @@ int launch_bicausal_cost_add(float* C3, int B, const float* h_fake, const float*
 int launch_mixed_causal_add(float* C, int Bx, int By, const float* h, const float* M, int T, int J, float sc,
                             hipStream_t st);
 
+// rbf_sum.hip: C [Bx,By] = exp(-gamma C) in place, the fp64 sum of the block at ws[0] (KCCOT_COST_RBF_SUM); the call
+// touches the first rbf_sum_doubles(Bx, By) doubles of ws (the sum, then one partial per 4 x 64 tile)
+size_t rbf_sum_doubles(int Bx, int By);
+int launch_rbf_sum(float* C, int Bx, int By, float gamma, double* ws, hipStream_t st);
+
 }  // namespace kccot

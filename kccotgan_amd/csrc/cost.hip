@@ -366,6 +366,24 @@ extern "C" int kccot_pairwise_cost_f32(const float* x, const float* y, int Bx, i
             return fail(KCCOT_EUNSUPPORTED, "pairwise_cost: CAUSAL_ADD supports Bx <= %d (got %d)", 65535 * 16, Bx);
         return launch_mixed_causal_add(C_out, Bx, By, h1, M1, T, J, sc, (hipStream_t)stream);
     }
+    if (flags & KCCOT_COST_RBF_SUM) {
+        // C_out = exp(-sc C_out) in place and the block's fp64 sum at ws[0] (rbf_sum.hip): x, y, K and the features unused
+        if (flags != KCCOT_COST_RBF_SUM)
+            return fail(KCCOT_EINVAL, "pairwise_cost: RBF_SUM takes no other flag (flags=%u)", flags);
+        if (!C_out || !ws) return fail(KCCOT_EINVAL, "pairwise_cost: RBF_SUM needs C_out and a workspace");
+        if (Bx <= 0 || By <= 0 || !(sc > 0.f))
+            return fail(KCCOT_EINVAL, "pairwise_cost: RBF_SUM: bad arguments Bx=%d By=%d sc=%g", Bx, By, (double)sc);
+        if ((uintptr_t)ws % sizeof(double))
+            return fail(KCCOT_EINVAL, "pairwise_cost: RBF_SUM: the workspace must be 8-byte aligned (it receives doubles)");
+        if ((Bx + 3) / 4 > 65535)       // 4 x 64 tiles; rows on the y grid axis (capped at 65535)
+            return fail(KCCOT_EUNSUPPORTED, "pairwise_cost: RBF_SUM supports Bx <= %d (got %d)", 65535 * 4, Bx);
+        const size_t need = kccot_pairwise_cost_workspace_bytes(Bx, By, 1);
+        if (ws_bytes < need)
+            return fail(KCCOT_EWORKSPACE, "pairwise_cost: RBF_SUM: workspace %zu < %zu bytes", ws_bytes, need);
+        if (rbf_sum_doubles(Bx, By) * sizeof(double) > need)    // one double per 256 entries against 4 bytes per entry
+            return fail(KCCOT_EUNSUPPORTED, "pairwise_cost: RBF_SUM: Bx=%d By=%d outgrows the workspace query", Bx, By);
+        return launch_rbf_sum(C_out, Bx, By, sc, static_cast<double*>(ws), (hipStream_t)stream);
+    }
     if (flags & KCCOT_MIXED_CMIX_GIVEN) return fail(KCCOT_EINVAL, "pairwise_cost: CMIX_GIVEN does not apply");
     if (!x || !y || !C_out) return fail(KCCOT_EINVAL, "pairwise_cost: null pointer");
     if (Bx <= 0 || By <= 0 || K <= 0)
@@ -420,8 +438,8 @@ extern "C" int kccot_pairwise_cost3_f32(const float* real, const float* fake, in
             return fail(KCCOT_EUNSUPPORTED, "pairwise_cost3: BICAUSAL_TERM_ONLY supports B <= %d (got %d)", 65535 * 8, B);
         return launch_bicausal_cost_add(C3, B, h_fake, h_real, m_real, m_fake, T, J, sc, (hipStream_t)stream);
     }
-    if (flags & (KCCOT_COST_CAUSAL_ADD | KCCOT_MIXED_CMIX_GIVEN))
-        return fail(KCCOT_EINVAL, "pairwise_cost3: the CAUSAL_ADD / CMIX_GIVEN flags do not apply (flags=%u)", flags);
+    if (flags & (KCCOT_COST_CAUSAL_ADD | KCCOT_MIXED_CMIX_GIVEN | KCCOT_COST_RBF_SUM))
+        return fail(KCCOT_EINVAL, "pairwise_cost3: the CAUSAL_ADD / CMIX_GIVEN / RBF_SUM flags do not apply (flags=%u)", flags);
     if (!real || !fake || !C3) return fail(KCCOT_EINVAL, "pairwise_cost3: null pointer");
     const int nfeat = (h_fake != nullptr) + (h_real != nullptr) + (m_real != nullptr) + (m_fake != nullptr);
     if (nfeat != 0 && nfeat != 4)   // all four (the loss) or none (plain squared distances, e.g. for the RBF kernel)

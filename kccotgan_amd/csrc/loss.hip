@@ -18,6 +18,8 @@ static int loss3_fwd(bool bicausal, const float* real, const float* fake, int B,
                      kccot_stream_t stream) {
     if (flags & KCCOT_COST_BICAUSAL_TERM_ONLY)      // a step of the sharded caller's assembly, not a cost-ladder option
         return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_BICAUSAL_TERM_ONLY does not apply to a loss call");
+    if (flags & KCCOT_COST_RBF_SUM)                 // the sharded kernel-MMD's step on a finished distance block
+        return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_RBF_SUM does not apply to a loss call");
     int rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes,
                                       stream);
     if (rc) return rc;

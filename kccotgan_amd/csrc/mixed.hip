@@ -275,8 +275,9 @@ extern "C" int kccot_mixed_sinkhorn_loss_fwd_f32(const float* R, const float* F,
     if ((u_hist == nullptr) != (v_hist == nullptr) || (dCmix_unit && u_hist))
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: give u_hist and v_hist together, or dCmix_unit, not both");
     if (dCmix_unit && !ticket) return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the fused path needs the ticket");
-    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS | KCCOT_COST_BICAUSAL_TERM_ONLY | KCCOT_COST_CAUSAL_ADD))
-        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only / causal-add flags do not apply");
+    if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS | KCCOT_COST_BICAUSAL_TERM_ONLY | KCCOT_COST_CAUSAL_ADD |
+                 KCCOT_COST_RBF_SUM))
+        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only / causal-add / RBF_SUM flags do not apply");
     hipStream_t st = (hipStream_t)stream;
     void* stage = ws;
     size_t stage_bytes = ws_bytes;

@@ -23,6 +23,10 @@ every rank runs the single-GPU loss call itself, above that rank g builds its ro
 row-block calls on the stacked problem (rows g B/G and B + g B/G), adds their causal terms (KCCOT_COST_CAUSAL_ADD), and
 the gathered Cmix goes to the solves (KCCOT_MIXED_CMIX_GIVEN).
 
+sharded_rbf_mmd2 is the RBF-kernel MMD of the global batch (mmd.rbf_mmd2): the same gathers and
+row blocks of plain squared distances, then each rank turns its three [B/G, B] blocks into kernel values and fp64 sums
+(KCCOT_COST_RBF_SUM) and the 3 doubles are all-reduced; it can reuse the videos a sharded loss has already gathered.
+
 The returned loss is the GLOBAL-batch loss (identical on every rank).  Parameter gradients that
 flow back through a rank's local samples are therefore partial sums: combine them with an
 all-reduce SUM (not the mean DistributedDataParallel applies by default).
@@ -402,10 +406,42 @@ class HipOps:
             out = [part[0, 0], part[0, 1] + part[2, 1], part[2, 0], part[3, 1], part[1, 0] + part[3, 0], part[1, 1]]
         return tuple(d[row_begin:row_begin + row_count] for d in out)
 
+    # ---- the RBF-kernel MMD (mmd.rbf_mmd2) ----
+    @staticmethod
+    def mmd_cost_rows(real, fake, row_begin, row_count, norms=None):
+        """Rows [row_begin, row_begin + row_count) of the plain squared distances, [3, row_count, B] = (xy, xx, yy), sc = 1:
+        on the matrix pipe when the gathered `norms` [B,3] are given, else on the direct kernel (one zero [B,1,1] feature
+        tensor with T = J = 1: no causal term)."""
+        zero = _zeros_feat(real.shape[0], real.device)
+        return HipOps.cost3_rows(real, fake, zero, zero, zero, zero, 1.0, row_begin, row_count, norms)
+
+    @staticmethod
+    def rbf_sum_rows(blk, gamma):
+        """The three distance row blocks [3,Bl,B] -> exp(-gamma blk) IN PLACE and their three fp64 sums (KCCOT_COST_RBF_SUM,
+        one call per block).  Each call has a workspace of its own: its first double is the block's sum."""
+        _, Bl, B = blk.shape
+        nd = (int(lib.kccot_pairwise_cost_workspace_bytes(Bl, B, 1)) + 7) // 8
+        ws = _lib.empty((3, nd), torch.float64, blk.device)
+        for p in range(3):
+            check(lib.kccot_pairwise_cost_f32(None, None, Bl, B, 0, float(gamma), None, None, None, None, 1, 1,
+                                              _lib.COST_RBF_SUM, ptr(blk[p]), ws[p].data_ptr(), nd * 8, stream_of(blk)),
+                  "pairwise_cost(rbf sum)")
+        return blk, ws[:, 0].contiguous()
+
+    @staticmethod
+    def rbf_mmd_grad(K3, gamma, g):
+        """gD3 [3,B,B] = g d mmd^2 / d D3 from the gathered kernel matrices (kccot_rbf_mmd_bwd_f32)."""
+        gD3 = _lib.empty_like(K3)
+        g = g.reshape(1).float().contiguous()
+        check(lib.kccot_rbf_mmd_bwd_f32(ptr(K3), K3.shape[1], float(gamma), ptr(g), ptr(gD3), stream_of(K3)), "rbf_mmd_bwd")
+        return gD3
+
 
 # the operations the sharded mixed loss needs of an ops object (an injected one must provide all of them)
 MIXED_OPS = ("replicate_costs", "mixed_loss_full", "mixed_cost_rows", "causal_add", "mixed_loss_given", "mixed_dcmix",
              "mixed_dfake_rows", "mixed_feature_grads")
+# ... and the sharded RBF-kernel MMD
+MMD_OPS = ("mmd_cost_rows", "rbf_sum_rows", "rbf_mmd_grad", "dfake_rows")
 
 _ones = {}
 _zero_feats = {}
@@ -973,6 +1009,107 @@ def sharded_mixed_sinkhorn_loss(f_real_l, f_fake_l, f_real_p_l, f_fake_p_l, scal
     flat = lambda v: cast(v.reshape(Bl, -1)).contiguous()
     return _ShardedMixedLoss.apply(*(flat(v) for v in vids), *(cast(t).contiguous() for t in fl), float(scaling_coef),
                                    float(epsilon), int(L), group, ops).reshape(())
+
+
+# ---- the RBF-kernel MMD of the global batch -------------------------------------------
+class _ShardedRbfMMD2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, real_l, fake_l, gamma, group, ops, real_all, fake_all):
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+        Bl, K = real_l.shape
+        B = Bl * world
+        dev = real_l.device
+        keep = ctx.needs_input_grad[1]
+        _mark("start")
+        # matrix-pipe row blocks need x.x, e.e, x.e of every sample: each rank's own rows, 24 bytes per sample gathered
+        norms = None
+        if (hasattr(ops, "row_norms") and hasattr(ops, "rows_gram_supported") and ops.rows_gram_supported(Bl, B, K)
+                and os.environ.get("KCCOT_DIST_ROWS") != "direct"):
+            norms = torch.empty((B, 3), dtype=torch.float64, device=dev)
+            _gather_into(norms, ops.row_norms(real_l, fake_l), group)
+        if real_all is None:                         # the videos straight into preallocated [B,K] buffers
+            real_all = torch.empty((B, K), dtype=real_l.dtype, device=dev)
+            fake_all = torch.empty((B, K), dtype=real_l.dtype, device=dev)
+            _gather_into(real_all, real_l, group)
+            _gather_into(fake_all, fake_l, group)
+        _mark("exchange_inputs")
+        blk = ops.mmd_cost_rows(real_all, fake_all, rank * Bl, Bl, norms)        # [3,Bl,B] squared distances
+        _mark("cost_rows")
+        blk, sums = ops.rbf_sum_rows(blk, gamma)                                 # kernel values, their 3 fp64 sums
+        _mark("mmd_rows")
+        _all_reduce_sum(sums, group)
+        K3 = None
+        if keep:    # the kernel matrices for the backward travel now: no collective inside backward
+            K3 = all_gather_cat(blk.transpose(0, 1).contiguous(), group).transpose(0, 1).contiguous()      # [3,B,B]
+        _mark("reduce")
+        # sums = (Sxy, Sxx, Syy); the expression of the single-GPU kernel (csrc/martingale.hip, rbf_mmd)
+        m = ((sums[1] + sums[2] - 2.0 * sums[0]) / float(B * B)).to(real_l.dtype)
+        ctx.saved_state = (K3, real_all, fake_all)
+        ctx.cfg = (gamma, rank * Bl, Bl, ops)
+        return m
+
+    @staticmethod
+    def backward(ctx, g):
+        K3, real_all, fake_all = ctx.saved_state
+        gamma, row_begin, Bl, ops = ctx.cfg
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+        _mark("between_fwd_and_bwd")
+        gD3 = ops.rbf_mmd_grad(K3, gamma, g.reshape(()))
+        dfake = ops.dfake_rows(gD3, real_all, fake_all, 1.0, row_begin, Bl)
+        _mark("gradient")
+        return None, dfake, None, None, None, None, None
+
+
+def sharded_rbf_mmd2(real_l, fake_l, gamma=None, group=None, ops=None, gathered=None):
+    """mmd.rbf_mmd2 -- mean(Kxx) + mean(Kyy) - 2 mean(Kxy), K(a,b) = exp(-gamma |a-b|^2), biased, diagonals included -- of
+    the GLOBAL batch of B = G B/G samples from per-rank shards ``real_l``, ``fake_l`` [B/G, ...].  ``gamma=None``: 1 / K, K
+    the flattened feature count (sklearn's default).  Returns the same bits on every rank.  Differentiable w.r.t. ``fake_l``
+    (each rank receives the gradient of its own samples; combine parameter gradients with an all-reduce SUM, as for the
+    sharded losses); a real shard that requires a gradient raises NotImplementedError.
+
+    Data flow: row norms of the local shard and the two videos are all-gathered (``gathered=(real_all, fake_all)``: videos
+    [B, ...] that a sharded loss has gathered already are used instead, so a training step pays that all-gather once; they
+    are read, never differentiated: the gradient still goes to ``fake_l``); rank g forms its rows of the three squared-
+    distance matrices (the matrix pipe when kccot_pairwise_cost3_rows_gram_supported, the direct kernel otherwise;
+    KCCOT_DIST_ROWS=direct forces the latter), turns them into kernel values and three fp64 sums in place
+    (KCCOT_COST_RBF_SUM), the 3 doubles are all-reduced(SUM), mmd^2 = (Sxx + Syy - 2 Sxy) / B^2.  When ``fake_l`` requires
+    a gradient the kernel row blocks are all-gathered in the forward (3 B^2 floats), so the backward -- kccot_rbf_mmd_bwd_f32
+    on the full matrices, kccot_pairwise_cost3_bwd_rows_f32 for this rank's rows -- has no collective.  The ksplit protocol
+    and KCCOT_DIST_GATHER_CHUNKS do not apply.  Injected ``ops`` must provide MMD_OPS.
+
+    Without an initialised process group (and ``group=None``) this is ``mmd.rbf_mmd2(real_l, fake_l, gamma)``."""
+    ops = ops or HipOps
+    missing = [n for n in MMD_OPS if not hasattr(ops, n)]
+    if missing:
+        raise NotImplementedError("sharded rbf mmd: the ops %r lack %s" % (getattr(ops, "__name__", ops), ", ".join(missing)))
+    if real_l.requires_grad:
+        raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+    if real_l.shape != fake_l.shape or real_l.dim() < 2:
+        raise ValueError("the real and fake shards must have the same shape [B/G, ...]: %s vs %s"
+                         % (tuple(real_l.shape), tuple(fake_l.shape)))
+    Bl = real_l.shape[0]
+    Kf = real_l[0].numel()
+    if Bl < 1 or Kf < 1:
+        raise ValueError("empty shard %s" % (tuple(real_l.shape),))
+    gamma = 1.0 / Kf if gamma is None else float(gamma)
+    if not gamma > 0.0:
+        raise ValueError("gamma must be positive (got %r)" % (gamma,))
+    if gathered is not None and (len(gathered) != 2 or gathered[0].shape != gathered[1].shape
+                                 or gathered[0].shape[1:] != real_l.shape[1:]):
+        raise ValueError("gathered must be (real_all, fake_all), two [B, ...] videos of the shards' sample shape")
+    if group is None and ops is HipOps and not (dist.is_available() and dist.is_initialized()):
+        from . import mmd
+        return mmd.rbf_mmd2(real_l, fake_l, gamma)
+    cast = (lambda v: v.float()) if ops is HipOps else (lambda v: v)   # the HIP kernels are fp32
+    real_all = fake_all = None
+    if gathered is not None:
+        B = Bl * dist.get_world_size(group)
+        if gathered[0].shape[0] != B:
+            raise ValueError("gathered videos hold %d samples, the global batch has %d" % (gathered[0].shape[0], B))
+        real_all, fake_all = (cast(v.detach().reshape(B, -1)).contiguous() for v in gathered)
+    flat = lambda v: cast(v.reshape(Bl, -1)).contiguous()
+    return _ShardedRbfMMD2.apply(flat(real_l), flat(fake_l), gamma, group, ops, real_all, fake_all).reshape(())
 
 
 # ---- helpers used by bench.py ---------------------------------------------------------------------

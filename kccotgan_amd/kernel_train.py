@@ -284,6 +284,31 @@ class KCCOTTrainer:
                 test_inputs = torch.cat((test_inputs, preds), dim=2)
         return test_inputs
 
+    @torch.no_grad()
+    def mmd(self, real_data, sigma=None):
+        """Monitor, not part of the reference's loop: the biased RBF-kernel MMD^2 (``mmd.rbf_mmd2``, gamma = 1 / n_features)
+        between a [B,H,T,W,C] batch and what the generator makes of its context frames, generated as ``_forward`` does
+        (fresh z, training-mode networks) and, when ``sigma`` is given, smoothed as there.  Data-parallel (a ``group``, or
+        more than one rank): the MMD of the GLOBAL batch, ``dist.sharded_rbf_mmd2``, the same value on every rank.  No
+        gradient, no optimiser step; the BatchNorm running statistics are put back.  It draws z from the torch RNG."""
+        from . import mmd as _mmd
+        real_data = real_data.to(self.device, torch.float32)
+        real_in = real_data[:, :, :self.int_time_steps]
+        nets = (self.context_encoder, self.decoder)
+        buffers = [(b, b.clone()) for net in nets for b in net.buffers()]
+        with gan.conv_guard():
+            hidden_z = torch.randn(self.z_shape, device=self.device)
+            fake_pred = self.decoder(self.context_encoder(real_data), hidden_z)
+            real, fake = real_data, torch.cat((real_in, fake_pred), dim=2)
+            if sigma is not None:
+                real, fake = self._smooth(real, sigma), self._smooth(fake, sigma)
+        for b, saved in buffers:
+            b.copy_(saved)
+        if self.group is not None or self._world() > 1:
+            from . import dist as kd
+            return kd.sharded_rbf_mmd2(real, fake, group=self.group)
+        return _mmd.rbf_mmd2(real, fake)
+
     @staticmethod
     def sample_image(videos, max_rows=10):
         """kernel_train.py:349-351: [B,H,T,W,C] -> one image [1, min(10,B)*H, W*T, C], a row of frames per sample."""
