@@ -90,6 +90,22 @@ def scale_invariante_martingale_regularization(M, reg_lam, scaling_coef):
     return reg_lam * ((N_std.sum(0) / m).abs().sum() * scaling_coef)
 
 
+def martingale_pieces(M, reg_lam, scaling_coef):
+    """The pieces of scale_invariante_martingale_regularization: (s [T-1,J], std [J], p_M), with the gradient the
+    kernels document for a constant feature column.  torch.sqrt has slope inf at 0, so autograd of the function above
+    gives NaN on every element of a column with std = 0; here such a column (max == min over batch and time: the exact
+    test) takes std = 0 as a constant, i.e. the path through std contributes nothing, and sqrt never sees its variance.
+    On every other column the operations are those of the function above, one for one."""
+    m = M.shape[0]
+    N = M[:, 1:, :] - M[:, :-1, :]
+    flat = M.reshape(-1, M.shape[-1])
+    dead = flat.max(dim=0).values == flat.min(dim=0).values
+    var = ((M - M.mean(dim=(0, 1), keepdim=True)) ** 2).mean(dim=(0, 1))
+    std = torch.where(dead, torch.zeros_like(var), torch.sqrt(torch.where(dead, torch.ones_like(var), var)))
+    s = (N / (std + 1e-06)).sum(0) / m
+    return s, std, reg_lam * (s.abs().sum() * scaling_coef)
+
+
 def flatten_video(f):
     """gan_utils.py:216-220."""
     f = f.permute(0, 2, 1, 3, 4)
