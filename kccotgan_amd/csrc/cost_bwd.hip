@@ -14,19 +14,11 @@
 #include "cost_internal.h"
 #include <stdlib.h>
 #include "options.h"
+#include "bf16x3.h"
 
 namespace kccot {
 
 enum CoeffMode { CO_LOSS3_DFAKE = 0, CO_DX = 1, CO_DY = 2, CO_SAME = 3 };
-
-// exact three-way split of an fp32 value into bf16 pieces (the upper 16 bits of h, m, l): x = h + m + l
-__device__ __forceinline__ void split3u(float x, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned xb = __float_as_uint(x);
-    const float hf = __uint_as_float(xb & 0xFFFF0000u);
-    const float r1 = x - hf;                                               // exact
-    const float mf = __uint_as_float(__float_as_uint(r1) & 0xFFFF0000u);
-    h = xb; m = __float_as_uint(r1); l = __float_as_uint(r1 - mf);         // pieces = the upper 16 bits of each word
-}
 
 // Wt is [R][Bout] (stack-row major) so that one output row block reads contiguous scalars.
 // R = n1 + n2 stack rows: first the n1 rows of src1, then the n2 rows of src2.
@@ -248,7 +240,6 @@ static int launch_causal_grads(CausalGradBatch& cb, int T, int J, float sc, hipS
 // a conflict-free ds_read_b32).  Workgroups walk the column tiles persistently and prefetch the
 // next tile's global loads under the current tile's MFMAs.  HBM traffic = the algorithmic
 // minimum: every element of real/fake read once, every element of the gradient written once.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int AM_COLS = 64;
 constexpr int AM_ROWS = 128;
 
@@ -310,7 +301,7 @@ __global__ __launch_bounds__(256) void apply_coeffs_mfma(const float* __restrict
         if (col < K) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = 32 * mblk + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int m = 32 * mblk + acc_row(r) + 4 * (lane >> 5);
                 if (m < Bout) {
                     // blocked use (more than 128 stack rows): later stack chunks add to the earlier ones' result
                     float* o = out + (int64_t)m * K + col;
@@ -325,13 +316,12 @@ __global__ __launch_bounds__(256) void apply_coeffs_mfma(const float* __restrict
 // ---- the same product on the bf16 matrix pipe, exactly -------------------------------------------------
 // The f32-input MFMA form above is bound by the matrix pipe (64 v_mfma_f32_32x32x2_f32 = 4096 pipe cycles per
 // wave and tile).  As in the Gram kernel, every fp32 value of W and of the video tile is cut EXACTLY into three
-// bf16 pieces (x = h + m + l) and the product is accumulated as hh + (hm + mh) + (hl + lh + mm) in fp32:
-// 48 v_mfma_f32_32x32x16_bf16 = 1536 pipe cycles per wave and tile, the dropped terms below 2^-24 |w z|.
+// bf16 pieces and the product is accumulated with the six-product chain (bf16x3.h):
+// 48 v_mfma_f32_32x32x16_bf16 = 1536 pipe cycles per wave and tile.
 // Eight waves: 0-3 stage (load two adjacent stack rows x four columns, split, pack the row pair of each piece
 // into one dword and write it k-contiguous: LDS plane [column][stack row]), 4-7 own one 32x32 output sub-tile
 // each, keep their W fragments (8 k-steps x 3 pieces) in registers and read the tile's fragments as two
 // ds_read_b64 per piece and step.  Two LDS buffers, one barrier per tile.
-typedef __bf16 abf16x8 __attribute__((ext_vector_type(8)));
 constexpr int AX_COLP = AM_ROWS * 2 + 8;         // 264 bytes per column of a plane: conflict-free b64 reads, 8-byte aligned
 constexpr int AX_PLANE = AM_COLS * AX_COLP;      // 16896
 constexpr int AX_BUF = 3 * AX_PLANE;             // 50688
@@ -348,6 +338,9 @@ __global__ __launch_bounds__(256) void split_coeffs(const float* __restrict__ Wt
     W3[((int64_t)1 * Bout + m) * R + r] = (unsigned short)(mm >> 16);
     W3[((int64_t)2 * Bout + m) * R + r] = (unsigned short)(l >> 16);
 }
+
+// the pieces [h, m, l] of a fragment held as an array (loaded plane by plane) as the chain's operand
+__device__ __forceinline__ Frag3 frag_of(const bf16x8 (&p)[3]) { return Frag3{p[0], p[1], p[2]}; }
 
 // out[bo x 64-column tile] (+)= W[bo x rr] * Z[rr x 64]: W3 planes hold ALL output rows / stack rows of the
 // problem (Bt x Rt); this launch uses output rows [0, bo) of the block W3 points at and stack rows [r0, r0 + rr).
@@ -398,10 +391,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3(const unsigned short* __r
                     split3u(a[c], ha, ma, la);
                     split3u(b[c], hb, mb, lb);
                     const int off = (c4 + c) * AX_COLP + r * 2;
-                    // dword = bf16(row r) | bf16(row r+1) << 16
-                    *reinterpret_cast<unsigned*>(zb + off) = __builtin_amdgcn_perm(hb, ha, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + AX_PLANE + off) = __builtin_amdgcn_perm(mb, ma, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + 2 * AX_PLANE + off) = __builtin_amdgcn_perm(lb, la, 0x07060302u);
+                    store_pairs3(zb, AX_PLANE, off, ha, hb, ma, mb, la, lb);        // dword = bf16(row r) | bf16(row r+1) << 16
                 }
             }
             if (tile + gridDim.x < ntiles) load_tile(tile + gridDim.x);
@@ -413,7 +403,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3(const unsigned short* __r
     // -------------------------------------------------------------------- consumers
     const int w = wave - 4, mblk = w & 1, cblk = w >> 1;
     const int nsteps = rr >> 4;
-    abf16x8 Ah[8], Am[8], Al[8];
+    bf16x8 Ah[8], Am[8], Al[8];
     {
         int m = 32 * mblk + (lane & 31);
         if (m >= bo) m = bo - 1;                              // rows past the block: any valid row (their outputs are not stored)
@@ -422,9 +412,9 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3(const unsigned short* __r
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             if (s < nsteps) {
-                Ah[s] = *reinterpret_cast<const abf16x8*>(wr + 16 * s);
-                Am[s] = *reinterpret_cast<const abf16x8*>(wr + plane + 16 * s);
-                Al[s] = *reinterpret_cast<const abf16x8*>(wr + 2 * plane + 16 * s);
+                Ah[s] = *reinterpret_cast<const bf16x8*>(wr + 16 * s);
+                Am[s] = *reinterpret_cast<const bf16x8*>(wr + plane + 16 * s);
+                Al[s] = *reinterpret_cast<const bf16x8*>(wr + 2 * plane + 16 * s);
             }
         }
     }
@@ -438,35 +428,19 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3(const unsigned short* __r
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = 32 * mblk + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int m = 32 * mblk + acc_row(r) + 4 * (lane >> 5);
             acc[r] = (ACCUM && col < K && m < bo) ? out[(int64_t)m * K + col] : 0.f;
         }
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             if (s < nsteps) {
-                abf16x8 Bh, Bm, Bl;
-                uint2* ph = reinterpret_cast<uint2*>(&Bh);
-                uint2* pm = reinterpret_cast<uint2*>(&Bm);
-                uint2* pl = reinterpret_cast<uint2*>(&Bl);
-                ph[0] = *reinterpret_cast<const uint2*>(zb + boff + 32 * s);
-                ph[1] = *reinterpret_cast<const uint2*>(zb + boff + 32 * s + 8);
-                pm[0] = *reinterpret_cast<const uint2*>(zb + AX_PLANE + boff + 32 * s);
-                pm[1] = *reinterpret_cast<const uint2*>(zb + AX_PLANE + boff + 32 * s + 8);
-                pl[0] = *reinterpret_cast<const uint2*>(zb + 2 * AX_PLANE + boff + 32 * s);
-                pl[1] = *reinterpret_cast<const uint2*>(zb + 2 * AX_PLANE + boff + 32 * s + 8);
-                // smallest terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am[s], Bm, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah[s], Bl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al[s], Bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah[s], Bm, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am[s], Bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah[s], Bh, acc, 0, 0, 0);
+                mfma_x3(acc, Frag3{Ah[s], Am[s], Al[s]}, ld_frag3_b64(zb, AX_PLANE, boff + 32 * s));
             }
         }
         if (col < K) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = 32 * mblk + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int m = 32 * mblk + acc_row(r) + 4 * (lane >> 5);
                 if (m < bo) out[(int64_t)m * K + col] = acc[r];
             }
         }
@@ -673,9 +647,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_loss3(Loss3Apply a) {
                     split3u(x[c], ha, ma, la);
                     split3u(y[c], hb, mb, lb);
                     const int off = (c4 + c) * AX_COLP + r * 2;
-                    *reinterpret_cast<unsigned*>(zb + off) = __builtin_amdgcn_perm(hb, ha, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + AX_PLANE + off) = __builtin_amdgcn_perm(mb, ma, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + 2 * AX_PLANE + off) = __builtin_amdgcn_perm(lb, la, 0x07060302u);
+                    store_pairs3(zb, AX_PLANE, off, ha, hb, ma, mb, la, lb);        // dword = bf16(row r) | bf16(row r+1) << 16
                 }
             }
             if (tile + a.nmain < ntiles) load_tile(tile + a.nmain);
@@ -687,7 +659,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_loss3(Loss3Apply a) {
     // -------------------------------------------------------------------- consumers: their W fragments first
     const int w = wave - 4, mblk = w & 1, cblk = w >> 1;
     const int nsteps = rr >> 4;
-    abf16x8 Ah[8], Am[8], Al[8];
+    bf16x8 Ah[8], Am[8], Al[8];
     {
         int m = 32 * mblk + (lane & 31);
         if (m >= B) m = B - 1;                                // rows past the batch: any valid row (their outputs are not stored)
@@ -744,14 +716,14 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_loss3(Loss3Apply a) {
             unsigned ph[4], pm[4], pl[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                ph[j] = __builtin_amdgcn_perm(hh[2 * j + 1], hh[2 * j], 0x07060302u);
-                pm[j] = __builtin_amdgcn_perm(mm[2 * j + 1], mm[2 * j], 0x07060302u);
-                pl[j] = __builtin_amdgcn_perm(ll[2 * j + 1], ll[2 * j], 0x07060302u);
+                ph[j] = bf16_pair(hh[2 * j], hh[2 * j + 1]);
+                pm[j] = bf16_pair(mm[2 * j], mm[2 * j + 1]);
+                pl[j] = bf16_pair(ll[2 * j], ll[2 * j + 1]);
             }
             const uint4 uh = {ph[0], ph[1], ph[2], ph[3]}, um = {pm[0], pm[1], pm[2], pm[3]}, ul = {pl[0], pl[1], pl[2], pl[3]};
-            Ah[s] = *reinterpret_cast<const abf16x8*>(&uh);
-            Am[s] = *reinterpret_cast<const abf16x8*>(&um);
-            Al[s] = *reinterpret_cast<const abf16x8*>(&ul);
+            Ah[s] = *reinterpret_cast<const bf16x8*>(&uh);
+            Am[s] = *reinterpret_cast<const bf16x8*>(&um);
+            Al[s] = *reinterpret_cast<const bf16x8*>(&ul);
         }
     }
     const int boff = (32 * cblk + (lane & 31)) * AX_COLP + 16 * (lane >> 5);
@@ -766,29 +738,13 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_loss3(Loss3Apply a) {
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             if (s < nsteps) {
-                abf16x8 Bh, Bm, Bl;
-                uint2* ph = reinterpret_cast<uint2*>(&Bh);
-                uint2* pm = reinterpret_cast<uint2*>(&Bm);
-                uint2* pl = reinterpret_cast<uint2*>(&Bl);
-                ph[0] = *reinterpret_cast<const uint2*>(zb + boff + 32 * s);
-                ph[1] = *reinterpret_cast<const uint2*>(zb + boff + 32 * s + 8);
-                pm[0] = *reinterpret_cast<const uint2*>(zb + AX_PLANE + boff + 32 * s);
-                pm[1] = *reinterpret_cast<const uint2*>(zb + AX_PLANE + boff + 32 * s + 8);
-                pl[0] = *reinterpret_cast<const uint2*>(zb + 2 * AX_PLANE + boff + 32 * s);
-                pl[1] = *reinterpret_cast<const uint2*>(zb + 2 * AX_PLANE + boff + 32 * s + 8);
-                // smallest terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am[s], Bm, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah[s], Bl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al[s], Bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah[s], Bm, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am[s], Bh, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah[s], Bh, acc, 0, 0, 0);
+                mfma_x3(acc, Frag3{Ah[s], Am[s], Al[s]}, ld_frag3_b64(zb, AX_PLANE, boff + 32 * s));
             }
         }
         if (col < K) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = 32 * mblk + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int m = 32 * mblk + acc_row(r) + 4 * (lane >> 5);
                 if (m < B) a.out[(int64_t)m * K + col] = acc[r];
             }
         }
@@ -866,9 +822,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256(const unsigned short
                     split3u(a[cc], ha, ma, la);
                     split3u(b[cc], hb, mb, lb);
                     const int off = (c4 + cc) * AX_COLP + r * 2;
-                    *reinterpret_cast<unsigned*>(zb + off) = __builtin_amdgcn_perm(hb, ha, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + AX_PLANE + off) = __builtin_amdgcn_perm(mb, ma, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + 2 * AX_PLANE + off) = __builtin_amdgcn_perm(lb, la, 0x07060302u);
+                    store_pairs3(zb, AX_PLANE, off, ha, hb, ma, mb, la, lb);        // dword = bf16(row r) | bf16(row r+1) << 16
                 }
             }
         };
@@ -905,13 +859,13 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256(const unsigned short
     const int64_t plane = (int64_t)Bt * Rt;
     const unsigned short* wb0 = W3 + (int64_t)((m0 + 64 * w) / 32) * nsteps * 512 + lane * 8;
     const unsigned short* wb1 = wb0 + (int64_t)nsteps * 512;
-    abf16x8 A[4][2][3];                                       // ring of fragment sets: step g lives in A[g & 3]
+    bf16x8 A[4][2][3];                                       // ring of fragment sets: step g lives in A[g & 3]
     auto ldA = [&](int g, int slot) {
         const int64_t o = (int64_t)512 * g;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-            A[slot][0][pl] = *reinterpret_cast<const abf16x8*>(wb0 + pl * plane + o);
-            A[slot][1][pl] = *reinterpret_cast<const abf16x8*>(wb1 + pl * plane + o);
+            A[slot][0][pl] = *reinterpret_cast<const bf16x8*>(wb0 + pl * plane + o);
+            A[slot][1][pl] = *reinterpret_cast<const bf16x8*>(wb1 + pl * plane + o);
         }
     };
     ldA(0, 0); ldA(1, 1); ldA(2, 2);
@@ -924,16 +878,12 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256(const unsigned short
         for (int r = 0; r < 16; ++r) { acc00[r] = 0.f; acc01[r] = 0.f; acc10[r] = 0.f; acc11[r] = 0.f; }
         for (int c = 0; c < nchunk; ++c, buf ^= 1) {
             const unsigned char* zb = zs + buf * AX_BUF;
-            abf16x8 Bf[2][2][3];                              // [step parity][column tile][piece]: one k-step ahead
+            bf16x8 Bf[2][2][3];                              // [step parity][column tile][piece]: one k-step ahead
             auto ldB = [&](int st, int par) {
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
-                    uint2* p0 = reinterpret_cast<uint2*>(&Bf[par][0][pl]);
-                    uint2* p1 = reinterpret_cast<uint2*>(&Bf[par][1][pl]);
-                    p0[0] = *reinterpret_cast<const uint2*>(zb + pl * AX_PLANE + boff0 + 32 * st);
-                    p0[1] = *reinterpret_cast<const uint2*>(zb + pl * AX_PLANE + boff0 + 32 * st + 8);
-                    p1[0] = *reinterpret_cast<const uint2*>(zb + pl * AX_PLANE + boff1 + 32 * st);
-                    p1[1] = *reinterpret_cast<const uint2*>(zb + pl * AX_PLANE + boff1 + 32 * st + 8);
+                    Bf[par][0][pl] = ld_piece_b64(zb + pl * AX_PLANE + boff0 + 32 * st);
+                    Bf[par][1][pl] = ld_piece_b64(zb + pl * AX_PLANE + boff1 + 32 * st);
                 }
             };
             ldB(0, 0);
@@ -948,6 +898,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256(const unsigned short
                 if (s < 7) ldB(s + 1, (s + 1) & 1);
                 __builtin_amdgcn_sched_barrier(0);
                 // product-major order over the four accumulators (no MFMA waits on the one before it), smallest terms first
+// (KCCOT_MFMA_X3_2X2 written out: through the header macro this kernel's schedule changed)
 #define KCCOT_A4(PA, PB)                                                                                              \
                 acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 3][0][PA], Bf[s & 1][0][PB], acc00, 0, 0, 0); \
                 acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 3][0][PA], Bf[s & 1][1][PB], acc01, 0, 0, 0); \
@@ -962,7 +913,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256(const unsigned short
         const int64_t col = tile * AM_COLS + (lane & 31);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + 64 * w + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int64_t m = m0 + 64 * w + acc_row(r) + 4 * (lane >> 5);
             if (col < K) { out[m * K + col] = acc00[r]; out[(m + 32) * K + col] = acc10[r]; }
             if (col + 32 < K) { out[m * K + col + 32] = acc01[r]; out[(m + 32) * K + col + 32] = acc11[r]; }
         }
@@ -1019,9 +970,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_rows(const unsigned short
                     split3u(a[cc], ha, ma, la);
                     split3u(b[cc], hb, mb, lb);
                     const int off = (c4 + cc) * AX_COLP + r * 2;
-                    *reinterpret_cast<unsigned*>(zb + off) = __builtin_amdgcn_perm(hb, ha, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + AX_PLANE + off) = __builtin_amdgcn_perm(mb, ma, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + 2 * AX_PLANE + off) = __builtin_amdgcn_perm(lb, la, 0x07060302u);
+                    store_pairs3(zb, AX_PLANE, off, ha, hb, ma, mb, la, lb);        // dword = bf16(row r) | bf16(row r+1) << 16
                 }
             }
         };
@@ -1060,14 +1009,14 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_rows(const unsigned short
     // W3 is the fragment-major copy (retile_coeffs): row tile mt, k-step g -> 1 KiB at ((pl*Bt/32 + mt)*nsteps + g)*512
     const int64_t plane = (int64_t)Bt * Rt;
     const unsigned short* wb0 = W3 + (int64_t)(mw / 32) * nsteps * 512 + lane * 8;
-    abf16x8 A[4][RT][3];                                      // ring of fragment sets: step g lives in A[g & 3]
+    bf16x8 A[4][RT][3];                                      // ring of fragment sets: step g lives in A[g & 3]
     auto ldA = [&](int g, int slot) {
         const int64_t o = (int64_t)512 * g;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
             for (int i = 0; i < RT; ++i)
-                A[slot][i][pl] = *reinterpret_cast<const abf16x8*>(wb0 + (int64_t)i * nsteps * 512 + pl * plane + o);
+                A[slot][i][pl] = *reinterpret_cast<const bf16x8*>(wb0 + (int64_t)i * nsteps * 512 + pl * plane + o);
     };
     if (active) { ldA(0, 0); ldA(1, 1); ldA(2, 2); }
     const int boff0 = ((lane & 31) + 32 * CT * wc) * AX_COLP + 16 * (lane >> 5);
@@ -1084,16 +1033,13 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_rows(const unsigned short
         for (int c = 0; c < nchunk; ++c, buf ^= 1) {
             if (active) {
                 const unsigned char* zb = zs + buf * AX_BUF;
-                abf16x8 Bf[2][CT][3];                         // [step parity][column tile][piece]: one k-step ahead
+                bf16x8 Bf[2][CT][3];                         // [step parity][column tile][piece]: one k-step ahead
                 auto ldB = [&](int st, int par) {
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-                        for (int j = 0; j < CT; ++j) {
-                            uint2* p0 = reinterpret_cast<uint2*>(&Bf[par][j][pl]);
-                            p0[0] = *reinterpret_cast<const uint2*>(zb + pl * AX_PLANE + boff0 + j * 32 * AX_COLP + 32 * st);
-                            p0[1] = *reinterpret_cast<const uint2*>(zb + pl * AX_PLANE + boff0 + j * 32 * AX_COLP + 32 * st + 8);
-                        }
+                        for (int j = 0; j < CT; ++j)
+                            Bf[par][j][pl] = ld_piece_b64(zb + pl * AX_PLANE + boff0 + j * 32 * AX_COLP + 32 * st);
                 };
                 ldB(0, 0);
 #pragma unroll
@@ -1107,12 +1053,14 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_rows(const unsigned short
                     if (s < 7) ldB(s + 1, (s + 1) & 1);
                     __builtin_amdgcn_sched_barrier(0);
                     // product-major order over the accumulators (no MFMA waits on the one before it), smallest terms first
-#define KCCOT_A4(PA, PB)                                                                                              \
-                    _Pragma("unroll") for (int i = 0; i < RT; ++i)                                                    \
-                        _Pragma("unroll") for (int j = 0; j < CT; ++j)                                                \
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 3][i][PA], Bf[s & 1][j][PB], acc[i][j], 0, 0, 0);
-                    KCCOT_A4(1, 1) KCCOT_A4(0, 2) KCCOT_A4(2, 0) KCCOT_A4(0, 1) KCCOT_A4(1, 0) KCCOT_A4(0, 0)
-#undef KCCOT_A4
+{
+                        Frag3 a[RT], b[CT];
+#pragma unroll
+                        for (int i = 0; i < RT; ++i) a[i] = frag_of(A[s & 3][i]);
+#pragma unroll
+                        for (int j = 0; j < CT; ++j) b[j] = frag_of(Bf[s & 1][j]);
+                        mfma_x3_tiles(acc, a, b);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -1127,7 +1075,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_rows(const unsigned short
                     if (col + 32 * j < K) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int64_t m = mw + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                            const int64_t m = mw + 32 * i + acc_row(r) + 4 * (lane >> 5);
                             out[m * K + col + 32 * j] = acc[i][j][r];
                         }
                     }
@@ -1188,9 +1136,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256n128(const unsigned s
                     split3u(a[cc], ha, ma, la);
                     split3u(b[cc], hb, mb, lb);
                     const int off = (c4 + cc) * AY_COLP + r * 2;
-                    *reinterpret_cast<unsigned*>(zb + off) = __builtin_amdgcn_perm(hb, ha, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + AY_PLANE + off) = __builtin_amdgcn_perm(mb, ma, 0x07060302u);
-                    *reinterpret_cast<unsigned*>(zb + 2 * AY_PLANE + off) = __builtin_amdgcn_perm(lb, la, 0x07060302u);
+                    store_pairs3(zb, AY_PLANE, off, ha, hb, ma, mb, la, lb);        // dword = bf16(row r) | bf16(row r+1) << 16
                 }
             }
             if (++c == nchunk) { c = 0; tile += gridDim.x; }
@@ -1207,13 +1153,13 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256n128(const unsigned s
     const int64_t plane = (int64_t)Bt * Rt;
     const unsigned short* wb0 = W3 + (int64_t)((m0 + 64 * w) / 32) * nsteps * 512 + lane * 8;
     const unsigned short* wb1 = wb0 + (int64_t)nsteps * 512;
-    abf16x8 A[2][2][3];                                       // k-step g lives in A[g & 1]: one step (48 MFMAs) ahead
+    bf16x8 A[2][2][3];                                       // k-step g lives in A[g & 1]: one step (48 MFMAs) ahead
     auto ldA = [&](int g, int slot) {
         const int64_t o = (int64_t)512 * g;
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-            A[slot][0][pl] = *reinterpret_cast<const abf16x8*>(wb0 + pl * plane + o);
-            A[slot][1][pl] = *reinterpret_cast<const abf16x8*>(wb1 + pl * plane + o);
+            A[slot][0][pl] = *reinterpret_cast<const bf16x8*>(wb0 + pl * plane + o);
+            A[slot][1][pl] = *reinterpret_cast<const bf16x8*>(wb1 + pl * plane + o);
         }
     };
     ldA(0, 0);
@@ -1230,17 +1176,13 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256n128(const unsigned s
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         for (int c = 0; c < nchunk; ++c, buf ^= 1) {
             const unsigned char* zb = zs + buf * AY_BUF;
-            abf16x8 Bf[2][2][3];                              // [pair parity][column tile of the pair][piece]
+            bf16x8 Bf[2][2][3];                              // [pair parity][column tile of the pair][piece]
             auto ldB = [&](int st, int pair, int par) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        uint2* q = reinterpret_cast<uint2*>(&Bf[par][j][pl]);
-                        const unsigned char* src = zb + pl * AY_PLANE + boff + (64 * pair + 32 * j) * AY_COLP + 32 * st;
-                        q[0] = *reinterpret_cast<const uint2*>(src);
-                        q[1] = *reinterpret_cast<const uint2*>(src + 8);
-                    }
+                    for (int pl = 0; pl < 3; ++pl)
+                        Bf[par][j][pl] = ld_piece_b64(zb + pl * AY_PLANE + boff + (64 * pair + 32 * j) * AY_COLP + 32 * st);
             };
             ldB(0, 0, 0);
 #pragma unroll
@@ -1254,13 +1196,10 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256n128(const unsigned s
                     if (pair == 0) ldB(s, 1, 1);
                     else if (s < 3) ldB(s + 1, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
-#define KCCOT_A4(PA, PB)                                                                                                         \
-                    acc[0][2 * pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 1][0][PA], Bf[pair][0][PB], acc[0][2 * pair], 0, 0, 0);         \
-                    acc[0][2 * pair + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 1][0][PA], Bf[pair][1][PB], acc[0][2 * pair + 1], 0, 0, 0); \
-                    acc[1][2 * pair] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 1][1][PA], Bf[pair][0][PB], acc[1][2 * pair], 0, 0, 0);         \
-                    acc[1][2 * pair + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[s & 1][1][PA], Bf[pair][1][PB], acc[1][2 * pair + 1], 0, 0, 0);
-                    KCCOT_A4(1, 1) KCCOT_A4(0, 2) KCCOT_A4(2, 0) KCCOT_A4(0, 1) KCCOT_A4(1, 0) KCCOT_A4(0, 0)
-#undef KCCOT_A4
+{
+                        const Frag3 a0 = frag_of(A[s & 1][0]), a1 = frag_of(A[s & 1][1]), b0 = frag_of(Bf[pair][0]), b1 = frag_of(Bf[pair][1]);
+                        KCCOT_MFMA_X3_2X2(acc[0][2 * pair], acc[0][2 * pair + 1], acc[1][2 * pair], acc[1][2 * pair + 1], a0, a1, b0, b1)
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -1273,7 +1212,7 @@ __global__ __launch_bounds__(512) void apply_coeffs_x3_m256n128(const unsigned s
             if (col < K) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int64_t m = m0 + 64 * w + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const int64_t m = m0 + 64 * w + acc_row(r) + 4 * (lane >> 5);
                     out[m * K + col] = acc[0][j][r];
                     out[(m + 32) * K + col] = acc[1][j][r];
                 }

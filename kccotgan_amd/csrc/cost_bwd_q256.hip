@@ -20,7 +20,7 @@
 // holds columns 128 wc + 4 lane + u -- a lane's four column tiles are four ADJACENT columns, stored as one float4.  The W
 // fragments are copied with the lane order of the LDS rows.  (First build: column group = lane, k-group = wave: every
 // 8-byte stage write hit the same bank pair -- 64 cycles per write instruction, 18.1 ms against 13.2 for the old kernel.)
-// The stage layout, fragment reads and the six-product chain are gram_q.h's (3 planes x 512 rows x 32 bytes: W rows 0..255,
+// The stage layout is gram_q.h's, fragment reads and the six-product chain bf16x3.h's (3 planes x 512 rows x 32 bytes: W rows 0..255,
 // Z columns as rows 256..511); two stages are resident (96 KB).  Same products in the same order per output as the other
 // apply kernels (k ascending, mm, hl, lh, hm, mh, hh), fp32 accumulation over the 2B stack rows.
 #include "common.h"
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void apply_q256(ApplyQ a) {
             for (int f = 0; f < 6; ++f) {
                 const int ff = 6 * wave + f, mt = ff / 3, pl = ff % 3;
                 const unsigned so = (unsigned)((pl * wplane + ((int64_t)mt * (a.Rt / 16) + sc) * 512) * 2);
-                R.Wg[f] = __builtin_bit_cast(uint4, (qu32x4)__builtin_amdgcn_raw_buffer_load_b128(rw, (int)wvo, (int)so, 0));
+                R.Wg[f] = __builtin_bit_cast(uint4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rw, (int)wvo, (int)so, 0));
             }
             const int r0 = 16 * sc;                       // the step's 16 stack rows lie in one source (n1 % 16 == 0)
             const float* base = r0 < a.n1 ? a.src1 + (int64_t)r0 * K : a.src2 + (int64_t)(r0 - a.n1) * K;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void apply_q256(ApplyQ a) {
             const unsigned zvo = (unsigned)(((int64_t)(4 * rg) * K + c) * 4);                              // 15 rows < 4 GiB: K <= 2^26 (host)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                R.Zg[j] = __builtin_bit_cast(float4, (qu32x4)__builtin_amdgcn_raw_buffer_load_b128(rz, (int)zvo, (int)((unsigned)(j * K * 4)), 0));
+                R.Zg[j] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rz, (int)zvo, (int)((unsigned)(j * K * 4)), 0));
         };
         auto emit = [&](const StageRegs& R, unsigned char* zst) {
             const uint4 (&Wg)[6] = R.Wg;
@@ -125,38 +125,31 @@ __global__ __launch_bounds__(256) void apply_q256(ApplyQ a) {
             for (int c = 0; c < 4; ++c) {    // column 4 cg + c: k = 4 rg .. 4 rg + 3 of the step, three planes of 8 bytes
                 unsigned h[4], m[4], l[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float x = cok ? zc[c][j] : 0.f;
-                    const unsigned xb = __float_as_uint(x);
-                    const float r1 = x - __uint_as_float(xb & 0xFFFF0000u);            // exact
-                    const unsigned mb = __float_as_uint(r1);
-                    const float r2 = r1 - __uint_as_float(mb & 0xFFFF0000u);           // exact, <= 8 bits
-                    h[j] = xb; m[j] = mb; l[j] = __float_as_uint(r2);
-                }
-                const uint2 ph = {__builtin_amdgcn_perm(h[1], h[0], 0x07060302u), __builtin_amdgcn_perm(h[3], h[2], 0x07060302u)};
-                const uint2 pm = {__builtin_amdgcn_perm(m[1], m[0], 0x07060302u), __builtin_amdgcn_perm(m[3], m[2], 0x07060302u)};
-                const uint2 pl = {__builtin_amdgcn_perm(l[1], l[0], 0x07060302u), __builtin_amdgcn_perm(l[3], l[2], 0x07060302u)};
+                for (int j = 0; j < 4; ++j) split3u(cok ? zc[c][j] : 0.f, h[j], m[j], l[j]);
+                const uint2 ph = {bf16_pair(h[0], h[1]), bf16_pair(h[2], h[3])};
+                const uint2 pm = {bf16_pair(m[0], m[1]), bf16_pair(m[2], m[3])};
+                const uint2 pl = {bf16_pair(l[0], l[1]), bf16_pair(l[2], l[3])};
                 *reinterpret_cast<uint2*>(zst + zlds + 64 * c * QROWB) = ph;
                 *reinterpret_cast<uint2*>(zst + AQ_PLANE + zlds + 64 * c * QROWB) = pm;
                 *reinterpret_cast<uint2*>(zst + 2 * AQ_PLANE + zlds + 64 * c * QROWB) = pl;
             }
         };
 
-        QAcc acc[16];
+        X3Acc acc[16];
 #pragma unroll
         for (int t2 = 0; t2 < 16; ++t2)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) QACC(acc[t2], r) = 0.f;
+            for (int r = 0; r < 16; ++r) X3ACC(acc[t2], r) = 0.f;
         auto step = [&](const unsigned char* zst) {
             // all four column tiles held (48 fragment registers), every W fragment read ONCE: 24 fragment reads per step
-            QFrag bf[4];
+            Frag3 bf[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) bf[u] = gq_frag<AQ_PLANE>(zst, boff + 2 * u * 32 * QROWB);
+            for (int u = 0; u < 4; ++u) bf[u] = ld_frag3(zst, AQ_PLANE, boff + 2 * u * 32 * QROWB);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const QFrag af = gq_frag<AQ_PLANE>(zst, aoff + i * 32 * QROWB);
+                const Frag3 af = ld_frag3(zst, AQ_PLANE, aoff + i * 32 * QROWB);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) gq_mfma6(acc[4 * i + u], af, bf[u]);
+                for (int u = 0; u < 4; ++u) mfma_x3(acc[4 * i + u], af, bf[u]);
             }
         };
         // per MFMA at most one LDS read, two VALU instructions of the split, one LDS write; the next step's ten loads spread
@@ -195,7 +188,7 @@ __global__ __launch_bounds__(256) void apply_q256(ApplyQ a) {
             __builtin_amdgcn_sched_barrier(0);
         }
 
-        // accumulator register r of lane l is element ((r & 3) + 8 (r >> 2) + 4 (l >> 5), column lane l & 31) of its tile; the
+        // accumulator register r of lane l is element (acc_row(r) + 4 (l >> 5), column lane l & 31) of its tile; the
         // lane's four column tiles are the columns 128 wc + 4 (l & 31) + u, u = 0..3: one 16-byte store per (row tile, r)
         const int64_t cbase = col0 + 128 * wc + 4 * (lane & 31);
         float* o = a.out + ((int64_t)rtile * AQ_P + 128 * wr + 4 * (lane >> 5)) * K + cbase;
@@ -204,8 +197,8 @@ __global__ __launch_bounds__(256) void apply_q256(ApplyQ a) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const float4 v = {QACC(acc[4 * i], r), QACC(acc[4 * i + 1], r), QACC(acc[4 * i + 2], r), QACC(acc[4 * i + 3], r)};
-                    *reinterpret_cast<float4*>(o + (int64_t)(32 * i + (r & 3) + 8 * (r >> 2)) * K) = v;
+                    const float4 v = {X3ACC(acc[4 * i], r), X3ACC(acc[4 * i + 1], r), X3ACC(acc[4 * i + 2], r), X3ACC(acc[4 * i + 3], r)};
+                    *reinterpret_cast<float4*>(o + (int64_t)(32 * i + acc_row(r)) * K) = v;
                 }
         }
     }

@@ -19,7 +19,7 @@
 //
 // MFMA fragment maps (cdna_hip_programming.md section 3): for mfma_f32_32x32x2f32 lane l supplies
 // A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31]; accumulator register r of lane l is
-// D[(r&3) + 8*(r>>2) + 4*(l>>5)][l&31].  With A[i][k] = Z[32a+i][k] and B[k][j] = Z[32b+j][k]
+// D[acc_row(r) + 4*(l>>5)][l&31] (bf16x3.h).  With A[i][k] = Z[32a+i][k] and B[k][j] = Z[32b+j][k]
 // the result is the Gram sub-tile (a,b).  Each lane reads 4 consecutive k of its row with one
 // ds_read_b128 (k = kk + 4*(l>>5) + {0..3}); A and B use the same k mapping, and a sum over k does
 // not care in which order the eight k of a group are visited.
@@ -27,10 +27,9 @@
 #include <stdlib.h>
 #include "cost_internal.h"
 #include "options.h"
+#include "bf16x3.h"
 
 namespace kccot {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GPITCH = GRAM_KT + 4;   // 36 floats: conflict-free ds_read_b128 over 32 rows
 constexpr int GRAM_SLABS = 12;        // 10 sub-tiles + 2 second halves of the k-split ones
@@ -225,64 +224,33 @@ __global__ __launch_bounds__(256) void gram128_partial(GramArgs ga) {
         __syncthreads();
     }
 
-    // accumulator register r of lane l is element ((r&3) + 8*(r>>2) + 4*(l>>5), l&31)
     float* base = ga.gpart + (int64_t)blockIdx.x * GRAM_SLABS * 1024;
     const int col = lane & 31, rbase = 4 * (lane >> 5);
     if (ww.n > 0) {
         float* o = base + ww.slab[0] * 1024;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2) + rbase) * 32 + col] = acc0[r];
+        for (int r = 0; r < 16; ++r) o[(acc_row(r) + rbase) * 32 + col] = acc0[r];
     }
     if (ww.n > 1) {
         float* o = base + ww.slab[1] * 1024;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2) + rbase) * 32 + col] = acc1[r];
+        for (int r = 0; r < 16; ++r) o[(acc_row(r) + rbase) * 32 + col] = acc1[r];
     }
     if (ww.n > 2) {
         float* o = base + ww.slab[2] * 1024;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2) + rbase) * 32 + col] = acc2[r];
+        for (int r = 0; r < 16; ++r) o[(acc_row(r) + rbase) * 32 + col] = acc2[r];
     }
 }
 
 // ------------------------------------------------------------------------------------------
 // Same stacked Gram, all ten sub-tiles, on the bf16 MFMA pipe with an EXACT three-way split.
 //
-// Every fp32 value is cut into three bf16 pieces by truncation, x = h + m + l exactly (8 + 8 + 8
-// significand bits: h = top half of the word, m = top half of x - h, l = x - h - m), while the
-// tile is staged; the Gram entry is accumulated in fp32 as
-//     sum_k  xh*yh + (xh*ym + xm*yh) + (xh*yl + xl*yh + xm*ym)
-// -- six v_mfma_f32_32x32x16_bf16 per 16 k instead of eight v_mfma_f32_32x32x2_f32, each of them
-// four times shorter in issue cycles per k: the f32-MFMA-bound kernel becomes HBM-bound.  bf16 x
-// bf16 products are exact in fp32; the dropped terms xm*yl + xl*ym + xl*yl are below 2^-24 of
-// |x*y|, i.e. under the rounding of the fp32 accumulation itself, so this is fp32 arithmetic to
-// working precision (parity tests run both kernels against the same golden vectors).
+// The exact three-way split and its six-product chain are bf16x3.h's: the f32-MFMA-bound kernel becomes HBM-bound.
 // ------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int XKT = 64;                         // floats of K per stage
 constexpr int XPITCH = XKT * 2 + 16;            // bytes per row of one bf16 plane (+16: conflict-free b128 reads)
 constexpr int XPLANE = GRAM_ROWS * XPITCH;      // 18432 bytes
-
-__device__ __forceinline__ void split3_store(unsigned char* zs, int byte_off, float4 v) {
-    const unsigned x[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-    unsigned m[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float h = __uint_as_float(x[i] & 0xFFFF0000u);
-        const float r1 = __uint_as_float(x[i]) - h;                        // exact
-        const float mm = __uint_as_float(__float_as_uint(r1) & 0xFFFF0000u);
-        m[i] = __float_as_uint(r1);
-        l[i] = __float_as_uint(r1 - mm);                                   // exact, <= 8 significant bits
-    }
-    // pack the upper halves of consecutive elements: dword = bf16(e0) | bf16(e1) << 16
-    uint2 ph, pm, pl;
-    ph.x = __builtin_amdgcn_perm(x[1], x[0], 0x07060302u); ph.y = __builtin_amdgcn_perm(x[3], x[2], 0x07060302u);
-    pm.x = __builtin_amdgcn_perm(m[1], m[0], 0x07060302u); pm.y = __builtin_amdgcn_perm(m[3], m[2], 0x07060302u);
-    pl.x = __builtin_amdgcn_perm(l[1], l[0], 0x07060302u); pl.y = __builtin_amdgcn_perm(l[3], l[2], 0x07060302u);
-    *reinterpret_cast<uint2*>(zs + byte_off) = ph;
-    *reinterpret_cast<uint2*>(zs + XPLANE + byte_off) = pm;
-    *reinterpret_cast<uint2*>(zs + 2 * XPLANE + byte_off) = pl;
-}
 
 // ---- consumer side of the wave-specialised kernel -------------------------------------------------
 // One ds_read_b128 moves 1 KB = 8 cycles of the CU's LDS port, one bf16 MFMA keeps a SIMD's matrix
@@ -307,34 +275,6 @@ __device__ __forceinline__ void split3_store(unsigned char* zs, int byte_off, fl
 //    packed upper triangles, and the whole partial leaves the CU as ONE contiguous 33 KB record written with 16-byte
 //    stores by all consumer threads:  12 slabs x 4 KB = 48 KB per chunk  ->  8256 floats (GRAM_CPT) -- 11.8 MB -> 7.9 MB of
 //    partial tiles at configs[1], for the store AND for gram_reduce's read.
-struct Frag3 { bf16x8 h, m, l; };
-
-__device__ __forceinline__ Frag3 ld_frag3(const unsigned char* zs, int off) {
-    Frag3 f;
-    f.h = *reinterpret_cast<const bf16x8*>(zs + off);
-    f.m = *reinterpret_cast<const bf16x8*>(zs + XPLANE + off);
-    f.l = *reinterpret_cast<const bf16x8*>(zs + 2 * XPLANE + off);
-    return f;
-}
-
-// acc += A * B^T with the exact three-way split: hh + (hm + mh) + (hl + lh + mm), smallest terms first
-__device__ __forceinline__ void mfma_x3(f32x16& acc, const Frag3& A, const Frag3& B) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.m, B.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.h, B.l, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.l, B.h, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.h, B.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.m, B.h, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A.h, B.h, acc, 0, 0, 0);
-}
-
-// diagonal sub-tile: S += mm + hh (symmetric products), A += hl + hm (their transposes are the two products left out)
-__device__ __forceinline__ void mfma_x3_diag(f32x16& accS, f32x16& accA, const Frag3& F) {
-    accS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F.m, F.m, accS, 0, 0, 0);
-    accA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F.h, F.l, accA, 0, 0, 0);
-    accA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F.h, F.m, accA, 0, 0, 0);
-    accS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F.h, F.h, accS, 0, 0, 0);
-}
-
 // Compact partial record of one K-chunk (floats): the six off-diagonal sub-tiles (a < b) row-major [32][32] at
 // gram_od(a, b) * 1024, then the four diagonal sub-tiles as packed upper triangles (528 each) at 6144 + 528 a.
 constexpr int GRAM_TRI = 528;
@@ -343,12 +283,11 @@ static_assert(GRAM_CPT % 64 == 0 && GRAM_CPT * 4 <= 3 * XPLANE, "one 256-byte li
 __host__ __device__ __forceinline__ int gram_od(int a, int b) { return a == 0 ? b - 1 : (a == 1 ? b + 1 : 5); }
 __host__ __device__ __forceinline__ int gram_tri(int r, int c) { return r * 32 - ((r * (r - 1)) >> 1) + (c - r); }   // r <= c
 
-// accumulator register r of lane l is element ((r&3) + 8*(r>>2) + 4*(l>>5), l&31)
 __device__ __forceinline__ void img_tile(float* img, int od, int lane, const f32x16& acc) {
     const int col = lane & 31, rbase = 4 * (lane >> 5);
     float* o = img + od * 1024;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2) + rbase) * 32 + col] = acc[r];
+    for (int r = 0; r < 16; ++r) o[(acc_row(r) + rbase) * 32 + col] = acc[r];
 }
 
 template <int W>
@@ -365,11 +304,11 @@ __device__ __forceinline__ void x3ws_consume(unsigned char* zsA, unsigned char* 
         const unsigned char* zs = (s & 1) ? zsB : zsA;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
-            const Frag3 fx = ld_frag3(zs, ox + kb * 32), fy = ld_frag3(zs, oy + kb * 32);
+            const Frag3 fx = ld_frag3(zs, XPLANE, ox + kb * 32), fy = ld_frag3(zs, XPLANE, oy + kb * 32);
             mfma_x3_diag(accS, accA, fx);
             if (W != 3) mfma_x3(acc1, fx, fy); else mfma_x3(acc1, fy, fx);      // (X,Y), or (0,3) = (Y,X) for W = 3
             if (kb >= KB0 && kb < KB0 + 2) {
-                const Frag3 fz = ld_frag3(zs, oz + kb * 32);
+                const Frag3 fz = ld_frag3(zs, XPLANE, oz + kb * 32);
                 if (W == 0) mfma_x3(acc2, fx, fz);          // (0,2)
                 else if (W == 3) mfma_x3(acc2, fz, fx);     // (1,3)
                 else mfma_x3(acc2, fz, fy);                 // (0,2) resp. (1,3)
@@ -389,7 +328,7 @@ __device__ __forceinline__ void x3ws_consume(unsigned char* zsA, unsigned char* 
     }
     // G = S + A + A^T of the diagonal sub-tile, upper triangle only
 #pragma unroll
-    for (int r = 0; r < 16; ++r) tr[((r & 3) + 8 * (r >> 2) + rbase) * 33 + col] = accA[r];
+    for (int r = 0; r < 16; ++r) tr[(acc_row(r) + rbase) * 33 + col] = accA[r];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -397,7 +336,7 @@ __device__ __forceinline__ void x3ws_consume(unsigned char* zsA, unsigned char* 
         float* o = img + 6 * 1024 + X * GRAM_TRI;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + rbase;
+            const int row = acc_row(r) + rbase;
             const float g = (accS[r] + accA[r]) + tr[col * 33 + row];
             if (row <= col) o[gram_tri(row, col)] = g;
         }
@@ -456,8 +395,8 @@ __device__ __forceinline__ void x3ws_emit(DeepSet& d, const bool (&ok)[8], bool 
         }
         if (pair_diff) { b.x -= a.x; b.y -= a.y; b.z -= a.z; b.w -= a.w; }
         // (the subtractions as packed v_pk_add_f32, half as many instructions, measured SLOWER: 20.7-21.2 us vs 19.1-20.4)
-        split3_store(zb, wbase + 16 * j * XPITCH, a);
-        split3_store(zb, wbase + (64 + 16 * j) * XPITCH, b);
+        split3_store4(zb, XPLANE, wbase + 16 * j * XPITCH, a);
+        split3_store4(zb, XPLANE, wbase + (64 + 16 * j) * XPITCH, b);
     }
 }
 

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void rows_gram(RowsArgs a) {
     float4 GA[AP], GB[8], GS[8];                         // A rows; column-side rows; their subtrahends (E halves only)
     float2 carry[AP + 8];
     auto ld = [&](auto r, unsigned vo, int p) {
-        return __builtin_bit_cast(float4, (qu32x4)__builtin_amdgcn_raw_buffer_load_b128(r, (int)vo, (int)(p * rstep), 0));
+        return __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(r, (int)vo, (int)(p * rstep), 0));
     };
     auto issue = [&](int g) {
         int64_t k = kbeg + (int64_t)g * QG + 4 * q;
@@ -115,13 +115,13 @@ __global__ __launch_bounds__(256) void rows_gram(RowsArgs a) {
         for (int p = 0; p < AP + 8; ++p) {
             float4 v = value(p);
             if (RAGGED) { v.x = kok ? v.x : 0.f; v.y = kok ? v.y : 0.f; v.z = kok ? v.z : 0.f; v.w = kok ? v.w : 0.f; }
-            gq_split_store<PLANE>(zs, woff + 32 * p * QROWB, v.x, v.y);
+            split3_store2(zs, PLANE, woff + 32 * p * QROWB, v.x, v.y);
             carry[p] = make_float2(v.z, v.w);
         }
     };
     auto emit_odd = [&](unsigned char* zs) {
 #pragma unroll
-        for (int p = 0; p < AP + 8; ++p) gq_split_store<PLANE>(zs, woff + 32 * p * QROWB, carry[p].x, carry[p].y);
+        for (int p = 0; p < AP + 8; ++p) split3_store2(zs, PLANE, woff + 32 * p * QROWB, carry[p].x, carry[p].y);
     };
 
     // ---- consuming role.  AM = 128: wave (wr, wc) = A rows 64 wr .. x columns 128 wc .. (2 x 4 tiles);
@@ -131,20 +131,20 @@ __global__ __launch_bounds__(256) void rows_gram(RowsArgs a) {
     const int wr = AM == 128 ? wave >> 1 : 0, wc = AM == 128 ? wave & 1 : wave;
     const int aoff = (64 * wr) * QROWB + lo;
     const int boff = (AM + 32 * NB * wc) * QROWB + lo;
-    qf32x16 acc[NT];
+    f32x16 acc[NT];
 #pragma unroll
     for (int t2 = 0; t2 < NT; ++t2)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t2][r] = 0.f;
     auto step = [&](const unsigned char* zs) {
-        QFrag bf[NB];
+        Frag3 bf[NB];
 #pragma unroll
-        for (int j = 0; j < NB; ++j) bf[j] = gq_frag<PLANE>(zs, boff + j * 32 * QROWB);
+        for (int j = 0; j < NB; ++j) bf[j] = ld_frag3(zs, PLANE, boff + j * 32 * QROWB);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const QFrag af2 = gq_frag<PLANE>(zs, aoff + i * 32 * QROWB);
+            const Frag3 af2 = ld_frag3(zs, PLANE, aoff + i * 32 * QROWB);
 #pragma unroll
-            for (int j = 0; j < NB; ++j) gq_mfma6(acc[NB * i + j], af2, bf[j]);
+            for (int j = 0; j < NB; ++j) mfma_x3(acc[NB * i + j], af2, bf[j]);
         }
     };
     auto interleave = [&](bool with_loads) {              // see gram_q256: one wave per SIMD, the staging rides in the MFMAs' shadow
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void rows_gram(RowsArgs a) {
     for (int t2 = 0; t2 < NT; ++t2) {
         float* ot = o + (32 * (t2 / NB)) * RB + 32 * (t2 % NB);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) ot[((r & 3) + 8 * (r >> 2)) * RB] = acc[t2][r];
+        for (int r = 0; r < 16; ++r) ot[acc_row(r) * RB] = acc[t2][r];
     }
 }
 

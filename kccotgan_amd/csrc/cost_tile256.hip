@@ -101,16 +101,16 @@ __device__ __forceinline__ void q256_body(const Q256Args& a, int pa, int pb, int
         const unsigned vo = lrow + (unsigned)(k * 4);
 #pragma unroll
         for (int p = 0; p < (HALF ? 4 : 8); ++p)
-            G[p] = __builtin_bit_cast(float4, (qu32x4)__builtin_amdgcn_raw_buffer_load_b128(ra, (int)vo, (int)(p * rstep), 0));
+            G[p] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(ra, (int)vo, (int)(p * rstep), 0));
         if constexpr (HALF) {
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                G[4 + p] = __builtin_bit_cast(float4, (qu32x4)__builtin_amdgcn_raw_buffer_load_b128(rb, (int)vo, (int)(p * rstep), 0));
+                G[4 + p] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rb, (int)vo, (int)(p * rstep), 0));
         }
         if constexpr (!SAME) {
 #pragma unroll
             for (int p = 0; p < 8; ++p)
-                G[8 + p] = __builtin_bit_cast(float4, (qu32x4)__builtin_amdgcn_raw_buffer_load_b128(rb, (int)vo, (int)(p * rstep), 0));
+                G[8 + p] = __builtin_bit_cast(float4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rb, (int)vo, (int)(p * rstep), 0));
         }
     };
     // granule g has landed: E rows formed (EPAIR), the even step's pairs split into `zs`, the odd step's kept in `carry`
@@ -126,17 +126,17 @@ __device__ __forceinline__ void q256_body(const Q256Args& a, int pa, int pb, int
                 v.x -= G[p - 8].x; v.y -= G[p - 8].y; v.z -= G[p - 8].z; v.w -= G[p - 8].w;
                 // unconditional: a granule past the end of the chunk re-writes the E values of columns another workgroup
                 // owns -- the same bits from the same inputs -- rather than put a branch into the step's block
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(qu32x4, v), re, (int)vo, (int)((p - 8) * rstep), 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), re, (int)vo, (int)((p - 8) * rstep), 0);
             }
             if (RAGGED) { v.x = kok ? v.x : 0.f; v.y = kok ? v.y : 0.f; v.z = kok ? v.z : 0.f; v.w = kok ? v.w : 0.f; }
-            gq_split_store<QPLANE>(zs, woff + 32 * p * QROWB, v.x, v.y);
+            split3_store2(zs, QPLANE, woff + 32 * p * QROWB, v.x, v.y);
             carry[p] = make_float2(v.z, v.w);
         }
     };
     auto emit_odd = [&](unsigned char* zs) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-            gq_split_store<QPLANE>(zs, woff + 32 * p * QROWB, carry[p].x, carry[p].y);
+            split3_store2(zs, QPLANE, woff + 32 * p * QROWB, carry[p].x, carry[p].y);
         }
     };
 
@@ -157,36 +157,36 @@ __device__ __forceinline__ void q256_body(const Q256Args& a, int pa, int pb, int
     const int aoff = tr0 * 32 * QROWB + lo;
     const int boff = (SAME ? 0 : QP * QROWB) + tc0 * 32 * QROWB + lo;        // a diagonal pair reads its B fragments from the A rows
     const int eoff = ter * 32 * QROWB + lo;
-    QAcc acc[NT];
+    X3Acc acc[NT];
 #pragma unroll
     for (int t2 = 0; t2 < NT; ++t2)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) QACC(acc[t2], r) = 0.f;
+        for (int r = 0; r < 16; ++r) X3ACC(acc[t2], r) = 0.f;
     auto step = [&](const unsigned char* zs) {
         if constexpr (SAME) {
-            QFrag bf[4];
+            Frag3 bf[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = gq_frag<QPLANE>(zs, boff + j * 32 * QROWB);
+            for (int j = 0; j < 4; ++j) bf[j] = ld_frag3(zs, QPLANE, boff + j * 32 * QROWB);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const QFrag af = gq_frag<QPLANE>(zs, aoff + i * 32 * QROWB);
+                const Frag3 af = ld_frag3(zs, QPLANE, aoff + i * 32 * QROWB);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) gq_mfma6(acc[4 * i + j], af, bf[j]);
+                for (int j = 0; j < 4; ++j) mfma_x3(acc[4 * i + j], af, bf[j]);
             }
-            const QFrag ea = gq_frag<QPLANE>(zs, eoff);                            // row tile `ter` = column tile `ter`: one fragment
-            gq_mfma6(acc[8], ea, ea);
-            const QFrag eb = gq_frag<QPLANE>(zs, eoff + (wave < 2 ? 32 * QROWB : 0));
-            gq_mfma6(acc[9], ea, eb);
+            const Frag3 ea = ld_frag3(zs, QPLANE, eoff);                            // row tile `ter` = column tile `ter`: one fragment
+            mfma_x3(acc[8], ea, ea);
+            const Frag3 eb = ld_frag3(zs, QPLANE, eoff + (wave < 2 ? 32 * QROWB : 0));
+            mfma_x3(acc[9], ea, eb);
         } else {
             // two B tiles at a time (24 fragment registers instead of 48; the A fragments are read twice per step)
 #pragma unroll
             for (int jh = 0; jh < 2; ++jh) {
-                const QFrag b0 = gq_frag<QPLANE>(zs, boff + (2 * jh) * 32 * QROWB), b1 = gq_frag<QPLANE>(zs, boff + (2 * jh + 1) * 32 * QROWB);
+                const Frag3 b0 = ld_frag3(zs, QPLANE, boff + (2 * jh) * 32 * QROWB), b1 = ld_frag3(zs, QPLANE, boff + (2 * jh + 1) * 32 * QROWB);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const QFrag af = gq_frag<QPLANE>(zs, aoff + i * 32 * QROWB);
-                    gq_mfma6(acc[4 * i + 2 * jh], af, b0);
-                    gq_mfma6(acc[4 * i + 2 * jh + 1], af, b1);
+                    const Frag3 af = ld_frag3(zs, QPLANE, aoff + i * 32 * QROWB);
+                    mfma_x3(acc[4 * i + 2 * jh], af, b0);
+                    mfma_x3(acc[4 * i + 2 * jh + 1], af, b1);
                 }
             }
         }
@@ -243,7 +243,7 @@ __device__ __forceinline__ void q256_body(const Q256Args& a, int pa, int pb, int
         for (int g = 0; g < ng; ++g) granule(G0, g);
     }
 
-    // accumulator register r of lane l is element ((r & 3) + 8 (r >> 2) + 4 (l >> 5), l & 31) of its 32 x 32 tile
+    // accumulator register r of lane l is element (acc_row(r) + 4 (l >> 5), l & 31) of its 32 x 32 tile
     float* o = a.part + ((int64_t)q256_pair_slot(a.nt, pa, pb) * a.nchunk + chunk_id) * QELEMS + (4 * (lane >> 5)) * QP + (lane & 31);
 #pragma unroll
     for (int t2 = 0; t2 < NT; ++t2) {
@@ -253,7 +253,7 @@ __device__ __forceinline__ void q256_body(const Q256Args& a, int pa, int pb, int
         if (SAME && t2 == 9 && wave >= 2) continue;                          // the duplicate of waves 2 and 3
         float* ot = o + (32 * trow) * QP + 32 * tcol;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) ot[((r & 3) + 8 * (r >> 2)) * QP] = QACC(acc[t2], r);
+        for (int r = 0; r < 16; ++r) ot[acc_row(r) * QP] = X3ACC(acc[t2], r);
     }
 }
 

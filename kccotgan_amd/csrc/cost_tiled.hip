@@ -18,11 +18,9 @@
 #include "common.h"
 #include "cost_internal.h"
 #include "options.h"
+#include "bf16x3.h"
 
 namespace kccot {
-
-typedef __bf16 tbf16x8 __attribute__((ext_vector_type(8)));
-typedef float tf32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TK = 32;                       // floats of K per stage (two LDS buffers of 3 planes x 256 rows: 120 KB)
 constexpr int TPITCH = TK * 2 + 16;          // 80 bytes per row of one bf16 plane: 16-lane b128 groups hit 16 distinct 4-bank slots
@@ -57,44 +55,6 @@ __global__ __launch_bounds__(256) void ediff_rows(const float* __restrict__ real
 __device__ __forceinline__ float4 tld4(const float* __restrict__ row, int64_t k, int64_t kend) {
     // K % 4 == 0 and 16-byte aligned rows (checked on the host); a stage may run past the chunk end
     return (k + 4 <= kend) ? *reinterpret_cast<const float4*>(row + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-__device__ __forceinline__ void tsplit3_store(unsigned char* zs, int byte_off, float4 v) {
-    const unsigned x[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-    unsigned m[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float h = __uint_as_float(x[i] & 0xFFFF0000u);
-        const float r1 = __uint_as_float(x[i]) - h;                        // exact
-        const float mm = __uint_as_float(__float_as_uint(r1) & 0xFFFF0000u);
-        m[i] = __float_as_uint(r1);
-        l[i] = __float_as_uint(r1 - mm);                                   // exact, <= 8 significant bits
-    }
-    uint2 ph, pm, pl;   // dword = bf16(e0) | bf16(e1) << 16
-    ph.x = __builtin_amdgcn_perm(x[1], x[0], 0x07060302u); ph.y = __builtin_amdgcn_perm(x[3], x[2], 0x07060302u);
-    pm.x = __builtin_amdgcn_perm(m[1], m[0], 0x07060302u); pm.y = __builtin_amdgcn_perm(m[3], m[2], 0x07060302u);
-    pl.x = __builtin_amdgcn_perm(l[1], l[0], 0x07060302u); pl.y = __builtin_amdgcn_perm(l[3], l[2], 0x07060302u);
-    *reinterpret_cast<uint2*>(zs + byte_off) = ph;
-    *reinterpret_cast<uint2*>(zs + TPLANE + byte_off) = pm;
-    *reinterpret_cast<uint2*>(zs + 2 * TPLANE + byte_off) = pl;
-}
-
-struct TFrag { tbf16x8 h, m, l; };
-__device__ __forceinline__ TFrag tld_frag(const unsigned char* zs, int off) {
-    TFrag f;
-    f.h = *reinterpret_cast<const tbf16x8*>(zs + off);
-    f.m = *reinterpret_cast<const tbf16x8*>(zs + TPLANE + off);
-    f.l = *reinterpret_cast<const tbf16x8*>(zs + 2 * TPLANE + off);
-    return f;
-}
-__device__ __forceinline__ void tmfma_x3(tf32x16& acc, const TFrag& a, const TFrag& b) {
-    // smallest terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
 }
 
 // pair index q -> (pa, pb), pa <= pb < nt, row-major over the upper triangle
@@ -145,12 +105,12 @@ __device__ __forceinline__ void tile_emit(TStageRegs& g, bool kok, unsigned char
         float4 a = g.va[j];
         if (AS) { a.x -= g.qa[j].x; a.y -= g.qa[j].y; a.z -= g.qa[j].z; a.w -= g.qa[j].w; }
         a.x = kok ? a.x : 0.f; a.y = kok ? a.y : 0.f; a.z = kok ? a.z : 0.f; a.w = kok ? a.w : 0.f;
-        tsplit3_store(zb, wbase + 32 * j * TPITCH, a);
+        split3_store4(zb, TPLANE, wbase + 32 * j * TPITCH, a);
         if (!SAME) {
             float4 b = g.vb[j];
             if (BS) { b.x -= g.qb[j].x; b.y -= g.qb[j].y; b.z -= g.qb[j].z; b.w -= g.qb[j].w; }
             b.x = kok ? b.x : 0.f; b.y = kok ? b.y : 0.f; b.z = kok ? b.z : 0.f; b.w = kok ? b.w : 0.f;
-            tsplit3_store(zb, wbase + (TP + 32 * j) * TPITCH, b);
+            split3_store4(zb, TPLANE, wbase + (TP + 32 * j) * TPITCH, b);
         }
     }
 }
@@ -264,7 +224,7 @@ __global__ __launch_bounds__(512) void gram_tile_x3(TileArgs ta) {
     // accumulators therefore only run over TFLUSH stages (96 accumulations) and are then folded into a second set of
     // fp32 sums (144 additions per chunk at that size): 64 v_add per 384 MFMAs, and the chunk sums stay fp64.
     constexpr int TFLUSH = 8;
-    tf32x16 acc00, acc01, acc10, acc11, sum00, sum01, sum10, sum11;
+    f32x16 acc00, acc01, acc10, acc11, sum00, sum01, sum10, sum11;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         acc00[r] = 0.f; acc01[r] = 0.f; acc10[r] = 0.f; acc11[r] = 0.f;
@@ -275,16 +235,9 @@ __global__ __launch_bounds__(512) void gram_tile_x3(TileArgs ta) {
         const unsigned char* zs = (s & 1) ? zsB : zsA;
 #pragma unroll
         for (int kb = 0; kb < TK / 16; ++kb) {
-            const TFrag a0 = tld_frag(zs, aoff0 + kb * 32), a1 = tld_frag(zs, aoff1 + kb * 32);
-            const TFrag b0 = tld_frag(zs, boff0 + kb * 32), b1 = tld_frag(zs, boff1 + kb * 32);
-            // product-major order: the four accumulators take turns, so no MFMA waits on the one issued before it
-#define KCCOT_T4(PA, PB)                                                                             \
-            acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0.PA, b0.PB, acc00, 0, 0, 0);               \
-            acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0.PA, b1.PB, acc01, 0, 0, 0);               \
-            acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.PA, b0.PB, acc10, 0, 0, 0);               \
-            acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.PA, b1.PB, acc11, 0, 0, 0);
-            KCCOT_T4(m, m) KCCOT_T4(h, l) KCCOT_T4(l, h) KCCOT_T4(h, m) KCCOT_T4(m, h) KCCOT_T4(h, h)   // smallest terms first
-#undef KCCOT_T4
+            const Frag3 a0 = ld_frag3(zs, TPLANE, aoff0 + kb * 32), a1 = ld_frag3(zs, TPLANE, aoff1 + kb * 32);
+            const Frag3 b0 = ld_frag3(zs, TPLANE, boff0 + kb * 32), b1 = ld_frag3(zs, TPLANE, boff1 + kb * 32);
+            KCCOT_MFMA_X3_2X2(acc00, acc01, acc10, acc11, a0, a1, b0, b1)
         }
         if ((s % TFLUSH) == TFLUSH - 1) {
             sum00 += acc00; sum01 += acc01; sum10 += acc10; sum11 += acc11;
@@ -295,12 +248,11 @@ __global__ __launch_bounds__(512) void gram_tile_x3(TileArgs ta) {
     }
     sum00 += acc00; sum01 += acc01; sum10 += acc10; sum11 += acc11;
 
-    // accumulator register r of lane l is element ((r&3) + 8*(r>>2) + 4*(l>>5), l&31) of its 32 x 32 tile
     float* o = ta.part + ((int64_t)pair * ta.nchunk + chunk_id) * TELEMS;
     const int col = 64 * wc + (lane & 31), rowb = 64 * wr + 4 * (lane >> 5);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = rowb + (r & 3) + 8 * (r >> 2);
+        const int row = rowb + (r & 3) + 8 * (r >> 2);     // = rowb + acc_row(r), written out: see profiles/bf16x3_isa_identity.txt
         o[row * TP + col] = sum00[r];
         o[row * TP + col + 32] = sum01[r];
         o[(row + 32) * TP + col] = sum10[r];

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Timing-only ablation: the B = 512 Gram (gram_q256<*>) and video-gradient (apply_q256) kernels with every
-# v_mfma_f32_32x32x16_bf16 replaced by two v_mfma_f32_16x16x32_bf16 on quarter tiles (gram_q.h, KCCOT_ABLATE_MFMA16; results are
+# v_mfma_f32_32x32x16_bf16 replaced by two v_mfma_f32_16x16x32_bf16 on quarter tiles (bf16x3.h, KCCOT_ABLATE_MFMA16; results are
 # garbage, FLOPs / operand reads / registers equal).  Question: does the 1.12x of tools/micro/mfma_shape.hip survive in the
 # kernels?   build: here;  run: GPU box
 set -e
