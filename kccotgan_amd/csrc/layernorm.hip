@@ -17,10 +17,14 @@ __global__ __launch_bounds__(256) void chan_ln_fwd(const float* __restrict__ x, 
     const float* xp = x + n * C * HW + p;
     float s = 0.f;
     for (int c = 0; c < C; ++c) s += xp[(int64_t)c * HW];
-    const float m = s / (float)C;
-    float v = 0.f;
-    for (int c = 0; c < C; ++c) { const float d = xp[(int64_t)c * HW] - m; v = fmaf(d, d, v); }
-    const float r = 1.0f / sqrtf(v / (float)C + eps);
+    const float m0 = s / (float)C;
+    // the sequential sum leaves m0 off the mean by its rounding (about sqrt(C) 2^-24 |m|: it shows where a common offset
+    // dwarfs the spread, and on a constant pixel, whose variance is 0).  The centred pass sees what is left: the residuals
+    // x - m0 are small, their sum is accurate, and sum (x - m)^2 = sum d^2 - C dm^2 holds for any shift.
+    float v = 0.f, sd = 0.f;
+    for (int c = 0; c < C; ++c) { const float d = xp[(int64_t)c * HW] - m0; sd += d; v = fmaf(d, d, v); }
+    const float dm = sd / (float)C, m = m0 + dm;
+    const float r = 1.0f / sqrtf(fmaxf(v / (float)C - dm * dm, 0.f) + eps);
     float* yp = y + n * C * HW + p;
     for (int c = 0; c < C; ++c) yp[(int64_t)c * HW] = (xp[(int64_t)c * HW] - m) * r * gamma[c] + beta[c];
     mean[g] = m;
@@ -31,11 +35,15 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_dx(const float* __restrict__ 
                                                       const float* __restrict__ gamma, const float* __restrict__ mean,
                                                       const float* __restrict__ rstd, int64_t npix, int C, int64_t HW,
                                                       float* __restrict__ dx) {
+#pragma clang fp contract(off)      // see dg below; the fmaf calls stay fused
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= npix) return;
     const int64_t n = g / HW, p = g - n * HW, base = n * C * HW + p;
     const float m = mean[g], r = rstd[g];
     float a = 0.f, b = 0.f;      // a = sum_c dy g xhat, b = sum_c dy g
+    // dg is a rounded product both times (contraction off: never fused into the sum or the difference below), so that the
+    // second pass subtracts from it exactly what the first pass averaged: with one channel dg - b is 0, not the rounding
+    // error of the product
     for (int c = 0; c < C; ++c) {
         const float dg = dy[base + (int64_t)c * HW] * gamma[c];
         a = fmaf(dg, (x[base + (int64_t)c * HW] - m) * r, a);
