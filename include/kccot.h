@@ -546,6 +546,21 @@ int kccot_rbf_mmd_bwd_f32(const float* K3, int B, float gamma, const float* gmmd
 #define KCCOT_SMOOTH_EXTERNAL_MAX 32u
 #define KCCOT_SMOOTH_STATS_ONLY 64u      /* kccot_smooth_bwd_sharded_f32 only */
 #define KCCOT_SMOOTH_EXTERNAL_STATS 128u /* kccot_smooth_bwd_sharded_f32 only */
+/* KCCOT_SMOOTH_CAUSAL_T: the past-only temporal smoothing.  NOT reference behaviour -- the reference has only the symmetric
+ * stencil, whose frame t contains frames t+1 .. t+r.  With w_d = exp(-d^2 / (2 sigma^2)), d = 0..r, and
+ * Z_t = sum_{d=0}^{min(r,t)} w_d:
+ *     s[b,h,t,w,c] = ( sum_{d=0}^{min(r,t)} w_d * x[b,h,t-d,w,c] ) / Z_t,      out = s / max(s)   (maximum of the WHOLE tensor)
+ * There is no padding: the early frames use the truncated, renormalised window, so s[t=0] = x[t=0] and a constant input gives
+ * ones.  Each s is summed in fp32 in ascending d and multiplied by the fp32 reciprocal of Z_t.  The backward applies the adjoint
+ * (S^T g)[t'] = sum_{d=0}^{r, t'+d<T} (w_d / Z_{t'+d}) g[t'+d] behind the adjoint of the division by the global maximum (arg-max
+ * ties share the correction, as in every smoothing call).
+ *   - Valid only together with KCCOT_SMOOTH_T and without KCCOT_SMOOTH_H / KCCOT_SMOOTH_W, in all three entry points; anything
+ *     else returns KCCOT_EINVAL, kccot_last_error() names the flag, and nothing is launched.
+ *   - Composes with NO_DIVIDE, EXTERNAL_MAX, STATS_ONLY and EXTERNAL_STATS exactly as the symmetric call does.
+ *   - Workspace: kccot_smooth_workspace_bytes, unchanged.
+ *   - Every radius 0 .. 7 is accepted, radius >= T included (the REFLECT restriction does not apply); T = 1 is the identity
+ *     followed by the division by the maximum. */
+#define KCCOT_SMOOTH_CAUSAL_T 8u
 size_t kccot_smooth_workspace_bytes(int B, int H, int T, int W, int C);
 int kccot_smooth_fwd_f32(const float* in, int B, int H, int T, int W, int C, float sigma,
                          int radius, unsigned axes_flags, float* out, float* max_inout,

@@ -22,6 +22,7 @@ COST_CAUSAL_ADD, MIXED_CMIX_GIVEN, COST_RBF_SUM = 128, 256, 512
 STOP_COUNT, STOP_INDEX = 0, 1
 SMOOTH_T, SMOOTH_H, SMOOTH_W, SMOOTH_NO_DIVIDE, SMOOTH_EXTERNAL_MAX = 1, 2, 4, 16, 32
 SMOOTH_STATS_ONLY, SMOOTH_EXTERNAL_STATS = 64, 128
+SMOOTH_CAUSAL_T = 8       # one-sided (past-only) T stencil; with SMOOTH_T alone
 
 _c = ctypes
 _fp = _c.c_void_p      # device pointers travel as plain addresses

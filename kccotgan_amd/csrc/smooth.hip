@@ -35,6 +35,20 @@ static Taps make_taps(float sigma, int r) {
     return tp;
 }
 
+// KCCOT_SMOOTH_CAUSAL_T (NOT reference behaviour: the reference has no one-sided smoothing).  w[d] = exp(-d^2 / (2 sigma^2)),
+// d = 0..r, is the non-negative half of the taps above before their normalisation (w[0] = 1); iz[t] = 1 / Z_t with
+// Z_t = w[0] + .. + w[min(r, t)] summed in fp32 in ascending d, t = 0..r (every t >= r has Z_r).  Entries behind r are zero.
+struct CausalTaps { float w[SM_MAXR + 1]; float iz[SM_MAXR + 1]; int r; };
+
+static CausalTaps make_causal_taps(float sigma, int r) {
+    CausalTaps ct{};
+    ct.r = r;
+    const float coef = (float)(-0.5 / ((double)sigma * (double)sigma));
+    float z = 0.f;
+    for (int d = 0; d <= r; ++d) { ct.w[d] = expf(coef * (float)(d * d)); z += ct.w[d]; ct.iz[d] = 1.0f / z; }
+    return ct;
+}
+
 __device__ __forceinline__ int reflect(int p, int len) { return p < 0 ? -p : (p >= len ? 2 * (len - 1) - p : p); }
 
 // out[e] = sum_d w[d] * in[e with its axis position moved to reflect(p+d)]           (adjoint = 0)
@@ -1777,6 +1791,7 @@ struct FixupArgs {
     const float* mx; float* res; int* dense; float* din;
     int len[3]; long long stride[3]; int na;   // the smoothed axes
     Taps tp;
+    int causal; CausalTaps ct;                 // KCCOT_SMOOTH_CAUSAL_T: the one-sided T stencil (na = 1) instead of tp
 };
 
 __global__ __launch_bounds__(1024) void maxnorm_bwd_fixup(FixupArgs a) {
@@ -1823,6 +1838,12 @@ __global__ __launch_bounds__(1024) void maxnorm_bwd_fixup(FixupArgs a) {
     for (int x = 0; x < a.na; ++x) combos *= nt;
     for (int t = 0; t < c; ++t) {
         const long long e = list[t];
+        if (a.causal) {     // S^T [out == 1]: frame p0 reaches the frames p0 - d, d = 0..min(r, p0), with w[d] / Z_p0
+            const int p0 = (int)((e / a.stride[0]) % a.len[0]), d = threadIdx.x;
+            if (d <= a.ct.r && d <= p0) a.din[e - (long long)d * a.stride[0]] -= corr * (a.ct.w[d] * a.ct.iz[min(p0, a.ct.r)]);
+            __syncthreads();
+            continue;
+        }
         for (int q = threadIdx.x; q < combos; q += 1024) {
             int rem = q;
             long long target = e;
@@ -1919,6 +1940,209 @@ static int collect_axes(int H, int T, int W, int C, unsigned flags, Axis* ax) {
     return na;
 }
 
+
+// ---- KCCOT_SMOOTH_CAUSAL_T: the one-sided (past-only) T stencil -------------------------------------------------------------
+//     s[t] = (sum_{d=0}^{min(r,t)} w[d] x[t-d]) / Z_t,   out = s / max(s)             (NOT reference behaviour, see CausalTaps)
+// No padding: the early frames use the truncated window with its own normalisation, so s[0] = x[0].  T is a strided axis
+// (stride W*C): a thread owns VW contiguous floats of one (b, h, w, c) column and walks along T with the last R inputs in
+// registers, the next U frames of the column in flight -- every element is read once and written once, consecutive lanes on
+// consecutive addresses at every step.  Frames in front of the first are zeros in the window (their products add exact zeros),
+// the sum runs in ascending d, and 1 / Z_t is applied to the finished sum.
+// The adjoint is the same walk one window later: with y[t] = x[t] / Z_t (x = the gradient behind the normalisation's adjoint)
+//     din[t'] = sum_{d=0}^{r, t'+d<T} w[d] y[t'+d],
+// so frame q = t' + r completes din[q - r], the window holds y[q-1] .. y[q-r], frames behind the last are zero, and the
+// coefficients are the forward's in reverse.  Modes as smooth_walk: WALK_MAX / WALK_WRITE / WALK_RAW forward, WALK_ADJX with the
+// normalisation's adjoint applied at the loads, WALK_ADJS without it but gathering the workgroup's TieRec.
+// R = 3 and 4 are compile-time radii; R = SM_MAXR is the generic form (runtime radius 0..SM_MAXR, window of SM_MAXR).
+struct CausalArgs {
+    const float* in;       // forward: input; adjoint: incoming gradient
+    const float* out_fwd;  // adjoint: the forward's normalised output
+    float* out;
+    float* blockmax;       // WALK_MAX: written; WALK_WRITE with nblk > 0: read
+    const float* mx;       // WALK_WRITE with nblk == 0 / adjoint: device scalar, the tensor maximum
+    const float* res;      // WALK_ADJX: {sum gout*out, #ties}
+    float* mx_out;         // WALK_WRITE with nblk > 0: the tensor maximum is written here
+    TieRec* ties;          // WALK_ADJS: one record per workgroup
+    const int* run_if;     // WALK_ADJX: non-null -> the launch does nothing unless *run_if != 0
+    int nblk;
+    int T;
+    int64_t S;             // T stride in floats = W * C
+    int64_t inner;         // S / VW
+    int64_t ncols;         // numel / T / VW
+    CausalTaps ct;
+};
+
+template <int R, int VW, int MODE>
+__global__ __launch_bounds__(256) void smooth_causal(CausalArgs a) {
+    typedef typename WalkVec<VW>::type V;
+    constexpr bool ADJ = MODE == WALK_ADJX || MODE == WALK_ADJS, FIXED = R != SM_MAXR;
+    constexpr int U = (ADJ && VW == 4) ? 4 : 8;     // frames in flight (the adjoint loads two tensors)
+    __shared__ float red[16];
+    __shared__ TieNote note;
+    if (MODE == WALK_ADJX && a.run_if && *a.run_if == 0) return;
+    const int T = a.T, r = FIXED ? R : a.ct.r;
+    const int64_t S = a.S;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool ok = gid < a.ncols;
+    const int64_t g = ok ? gid : 0;
+    const int64_t off = (g / a.inner) * T * S + (g % a.inner) * VW;
+    float m = 1.f, corr = 0.f;
+    if ((MODE == WALK_WRITE && a.nblk <= 0) || ADJ) m = a.mx[0];
+    if (MODE == WALK_ADJX) corr = a.res[1] > 0.f ? a.res[0] / (m * a.res[1]) : 0.f;
+    double sdot = 0.0;                  // WALK_ADJS
+    if (MODE == WALK_ADJS) note.clear();
+    // coefficient of the incoming frame, then of the window's slots (slot j = the frame j + 1 steps back)
+    float cf[R + 1];
+#pragma unroll
+    for (int j = 0; j <= R; ++j) cf[j] = j <= r ? a.ct.w[ADJ ? r - j : j] : 0.f;
+    V zero;
+#pragma unroll
+    for (int c = 0; c < VW; ++c) vat<VW>(zero, c) = 0.f;
+    const int NQ = ADJ ? T + r : T;     // steps of the walk
+    V nxt[U], nxo[ADJ ? U : 1];
+    auto fetch = [&](int j, int q) {    // frame q into slot j (addresses clamped, never predicated)
+        const int64_t o = off + (int64_t)(q < T ? q : T - 1) * S;
+        nxt[j] = *reinterpret_cast<const V*>(a.in + o);
+        if (ADJ) nxo[j] = *reinterpret_cast<const V*>(a.out_fwd + o);
+    };
+#pragma unroll
+    for (int j = 0; j < U; ++j) fetch(j, j);
+    if (MODE == WALK_WRITE && a.nblk > 0) {     // see smooth_walk: the preceding WALK_MAX launch's block maxima
+        float v = -FLT_MAX;
+        for (int i = threadIdx.x; i < a.nblk; i += 256) v = fmaxf(v, a.blockmax[i]);
+        m = block_max(v, red);
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.mx_out[0] = m;
+    }
+    V win[R > 0 ? R : 1];
+#pragma unroll
+    for (int j = 0; j < R; ++j) win[j] = zero;
+    float vmax = -FLT_MAX;
+    for (int q0 = 0; q0 < NQ; q0 += U) {
+        V cur[U], curo[ADJ ? U : 1];
+#pragma unroll
+        for (int j = 0; j < U; ++j) { cur[j] = nxt[j]; if (ADJ) curo[j] = nxo[j]; }
+#pragma unroll
+        for (int j = 0; j < U; ++j) fetch(j, q0 + U + j);
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int q = q0 + j;               // uniform
+            const bool live = q < NQ;
+            const float iz = a.ct.iz[q < r ? q : r];
+            V v = cur[j];
+            if (ADJ) {                          // y[q] = (g / max - corr [out == 1]) / Z_q, zero behind the last frame
+                const bool inside = q < T;
+#pragma unroll
+                for (int c = 0; c < VW; ++c) {
+                    const float gg = vat<VW>(v, c), oo = vat<VW>(curo[j], c);
+                    if (MODE == WALK_ADJS && ok && inside) {
+                        sdot = fma((double)gg, (double)oo, sdot);
+                        if (oo == 1.0f) note.add((long long)(off + (int64_t)q * S + c));
+                    }
+                    const float xg = MODE == WALK_ADJX ? gg / m - (oo == 1.0f ? corr : 0.f) : gg / m;
+                    vat<VW>(v, c) = inside ? xg * iz : 0.f;
+                }
+            }
+            V acc = zero;
+#pragma unroll
+            for (int k = 0; k <= R; ++k) {
+                const V& xk = k == 0 ? v : win[k > 0 ? k - 1 : 0];
+                V t;
+                if constexpr (VW == 1) t = fmaf(cf[k], xk, acc);
+                else {
+                    V wv;
+#pragma unroll
+                    for (int c = 0; c < VW; ++c) vat<VW>(wv, c) = cf[k];
+                    t = __builtin_elementwise_fma(wv, xk, acc);
+                }
+                acc = (FIXED || k <= r) ? t : acc;      // a tap behind the radius adds nothing, whatever the frame holds
+            }
+            if (!ADJ) {
+#pragma unroll
+                for (int c = 0; c < VW; ++c) vat<VW>(acc, c) = vat<VW>(acc, c) * iz;
+            }
+            if (MODE == WALK_MAX) {
+                float mx = vat<VW>(acc, 0);
+#pragma unroll
+                for (int c = 1; c < VW; ++c) mx = fmaxf(mx, vat<VW>(acc, c));
+                vmax = live ? fmaxf(vmax, mx) : vmax;
+            } else {
+                if (MODE == WALK_WRITE) {
+#pragma unroll
+                    for (int c = 0; c < VW; ++c) vat<VW>(acc, c) = vat<VW>(acc, c) / m;
+                }
+                const int tout = ADJ ? q - r : q;
+                if (ok && live && tout >= 0) *reinterpret_cast<V*>(a.out + off + (int64_t)tout * S) = acc;
+            }
+#pragma unroll
+            for (int i = R - 1; i > 0; --i) win[i] = win[i - 1];
+            if (R > 0) win[0] = v;
+        }
+    }
+    if (MODE == WALK_MAX) {
+        const float bm = block_max(ok ? vmax : -FLT_MAX, red);
+        if (threadIdx.x == 0) a.blockmax[blockIdx.x] = bm;
+    }
+    if (MODE == WALK_ADJS) note.store(a.ties + blockIdx.x, sdot);
+}
+
+// float4 pieces when the T stride and every pointer allow, single floats otherwise
+static int causal_vw(int64_t WC, const void* p0, const void* p1, const void* p2) {
+    return (WC % 4 == 0 && (((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2) & 15) == 0) ? 4 : 1;
+}
+
+static int64_t causal_wgs(int64_t numel, int T, int vw) { return (numel / T / vw + 255) / 256; }
+
+template <int MODE>
+static void launch_causal_m(const CausalArgs& ca, int radius, int vw, hipStream_t st) {
+    const dim3 grid((unsigned)((ca.ncols + 255) / 256));
+#define KCCOT_CT(RR)                                                                                            \
+    do {                                                                                                        \
+        if (vw == 4) hipLaunchKernelGGL((smooth_causal<RR, 4, MODE>), grid, dim3(256), 0, st, ca);              \
+        else hipLaunchKernelGGL((smooth_causal<RR, 1, MODE>), grid, dim3(256), 0, st, ca);                      \
+    } while (0)
+    if (radius == 3) KCCOT_CT(3); else if (radius == 4) KCCOT_CT(4); else KCCOT_CT(SM_MAXR);
+#undef KCCOT_CT
+}
+
+static int launch_causal(int mode, CausalArgs ca, int radius, int64_t numel, int vw, hipStream_t st) {
+    ca.inner = ca.S / vw;
+    ca.ncols = numel / ca.T / vw;
+    switch (mode) {
+        case WALK_MAX: launch_causal_m<WALK_MAX>(ca, radius, vw, st); break;
+        case WALK_WRITE: launch_causal_m<WALK_WRITE>(ca, radius, vw, st); break;
+        case WALK_RAW: launch_causal_m<WALK_RAW>(ca, radius, vw, st); break;
+        case WALK_ADJX: launch_causal_m<WALK_ADJX>(ca, radius, vw, st); break;
+        case WALK_ADJS: launch_causal_m<WALK_ADJS>(ca, radius, vw, st); break;
+        default: return fail(KCCOT_EINVAL, "smooth: mode %d has no causal form", mode);
+    }
+    return launch_status("smooth_causal");
+}
+
+// Forward of KCCOT_SMOOTH_CAUSAL_T.  Two phases as the symmetric temporal call: block maxima without a store, then the same
+// kernel again writing s / max (reducing the block maxima itself when there are few), so that NO_DIVIDE and EXTERNAL_MAX
+// evaluate s with the kernel the one-call form uses and the arg-max element comes out as exactly 1.
+static int smooth_causal_fwd(const float* in, float* out, float* max_inout, float* bmax, int64_t n, int T, int64_t WC,
+                             float sigma, int radius, bool ext, bool nodiv, hipStream_t st) {
+    int rc;
+    const int vw = causal_vw(WC, in, out, out);
+    const int64_t wgs = causal_wgs(n, T, vw);
+    CausalArgs ca{};
+    ca.ct = make_causal_taps(sigma, radius);
+    ca.in = in; ca.T = T; ca.S = WC;
+    if (!ext) {
+        ca.blockmax = bmax;
+        if ((rc = launch_causal(WALK_MAX, ca, radius, n, vw, st))) return rc;
+        if (!nodiv && wgs <= 4096) {
+            ca.nblk = (int)wgs;
+        } else {
+            hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, wgs, max_inout);
+            if ((rc = launch_status("reduce_blockmax"))) return rc;
+        }
+    }
+    ca.out = out; ca.mx = max_inout; ca.mx_out = max_inout;
+    return launch_causal(nodiv ? WALK_RAW : WALK_WRITE, ca, radius, n, vw, st);
+}
+
 }  // namespace kccot
 
 using namespace kccot;
@@ -1939,6 +2163,11 @@ static int smooth_check(const char* who, const void* a, const void* b, int B, in
         return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", who, B, H, T, W, C);
     if (radius < 0 || radius > SM_MAXR) return fail(KCCOT_EUNSUPPORTED, "%s: radius %d > %d", who, radius, SM_MAXR);
     if (!(sigma > 0.f)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", who);
+    if (flags & KCCOT_SMOOTH_CAUSAL_T) {    // the one-sided T stencil: T alone; no padding, so any radius up to SM_MAXR
+        if ((flags & (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W)) != KCCOT_SMOOTH_T)
+            return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_CAUSAL_T goes with KCCOT_SMOOTH_T alone (no H, no W)", who);
+        return 0;
+    }
     // REFLECT padding needs pad < dim (tf.pad rejects it otherwise)
     if (((flags & KCCOT_SMOOTH_T) && radius >= T) || ((flags & KCCOT_SMOOTH_H) && radius >= H) ||
         ((flags & KCCOT_SMOOTH_W) && radius >= W))
@@ -1965,6 +2194,8 @@ extern "C" int kccot_smooth_fwd_f32(const float* in, int B, int H, int T, int W,
     const bool ext = (flags & KCCOT_SMOOTH_EXTERNAL_MAX) != 0, nodiv = (flags & KCCOT_SMOOTH_NO_DIVIDE) != 0;
     if (ext && nodiv) return fail(KCCOT_EINVAL, "smooth_fwd: EXTERNAL_MAX and NO_DIVIDE are exclusive");
     if (na > 0 && in == out) return fail(KCCOT_EINVAL, "smooth_fwd: in-place convolution is not supported");
+    if (flags & KCCOT_SMOOTH_CAUSAL_T)
+        return smooth_causal_fwd(in, out, max_inout, bmax, n, T, (int64_t)W * C, sigma, radius, ext, nodiv, st);
     const Taps tp = make_taps(sigma, radius);
     const unsigned axes = flags & (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W);
     const bool r34 = radius == 3 || radius == 4;
@@ -2140,6 +2371,44 @@ static int smooth_bwd_impl(const float* gout, const float* out, const float* max
     const int64_t nparts = wide ? 2048 : nb;
     float* scal = reinterpret_cast<float*>(p + 2 * align_up((size_t)nb * sizeof(float), 256));   // workspace scalars {dot, ties, .., .., 1, 0, 0, dense}
     TieRec* recs = reinterpret_cast<TieRec*>(p + 2 * align_up((size_t)nb * sizeof(float), 256) + 256);
+    if (flags & KCCOT_SMOOTH_CAUSAL_T) {
+        // The one-sided T stencil on the same statistics / fix-up machinery: two-pass (the sums first, then the adjoint walk with
+        // the normalisation's adjoint at its loads) or folded (the walk gathers TieRecs, then the sparse fix-up, then the guarded
+        // dense walk), by the same option and threshold as the symmetric temporal call.  One TieRec per workgroup: where the
+        // grid would exceed the records of the workspace (T of one or two frames) the two-pass form runs whatever the option says.
+        const int64_t WC = (int64_t)W * C;
+        const int vw = causal_vw(WC, gout, out, stats_only ? nullptr : din);
+        const int64_t nrec = causal_wgs(n, T, vw);
+        const int fold_opt = opt(OPT_SMOOTH_BWD_FOLD);
+        const bool fold = !stats_only && !stats_in && (fold_opt == 2 || (fold_opt == 1 && n >= ((int64_t)1 << 22))) &&
+                          nrec <= tie_rec_capacity(n);
+        if (fold) {
+            recs = reinterpret_cast<TieRec*>(p);
+            scal = res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n) + smooth_rec_bytes(n));
+        } else if (stats_in) {
+            res = stats_ext;
+        } else {
+            if (stats_only) res = stats_ext;
+            if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, pdot, pcnt);
+            else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, pdot, pcnt);
+            if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
+            hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)pdot, (const float*)pcnt, nparts, res);
+            if ((rc = launch_status("maxnorm_bwd_combine"))) return rc;
+            if (stats_only) return 0;
+        }
+        CausalArgs ca{};
+        ca.ct = make_causal_taps(sigma, radius);
+        ca.in = gout; ca.out_fwd = out; ca.out = din; ca.mx = max_in; ca.res = res; ca.ties = recs; ca.T = T; ca.S = WC;
+        if ((rc = launch_causal(fold ? WALK_ADJS : WALK_ADJX, ca, radius, n, vw, st)) || !fold) return rc;
+        int* dense = reinterpret_cast<int*>(scal + 7);
+        FixupArgs fa{};
+        fa.ties = recs; fa.nrec = (int)nrec; fa.mx = max_in; fa.res = res; fa.dense = dense; fa.din = din; fa.na = 1;
+        fa.len[0] = T; fa.stride[0] = WC; fa.causal = 1; fa.ct = ca.ct;
+        hipLaunchKernelGGL(maxnorm_bwd_fixup, dim3(1), dim3(1024), 0, st, fa);
+        if ((rc = launch_status("maxnorm_bwd_fixup"))) return rc;
+        ca.run_if = dense;
+        return launch_causal(WALK_ADJX, ca, radius, n, vw, st);
+    }
     const unsigned axes = flags & (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W);
     // The streaming chains (temporal only / all three axes, radius 3 or 4).  Decided in front of the statistics: with the
     // option "smooth_bwd_fold" the chain's first stage gathers them itself (WALK_ADJS) and the pass below is skipped.

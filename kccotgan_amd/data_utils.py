@@ -130,6 +130,14 @@ class KernelSmoothing:
         """data_utils.py:503-521: 1-D Gaussian along T (REFLECT), then / global max."""
         return self._apply(inputs, sigma, self.temporal_radius, _lib.SMOOTH_T)
 
+    def causal_temporal_convolution(self, inputs, sigma):
+        """NOT reference behaviour.  The reference's only temporal smoothing is the symmetric stencil above, whose frame t
+        contains frames t+1 .. t+r: features that are meant to depend on frames <= t see the future through it.  This is
+        the past-only counterpart (KCCOT_SMOOTH_CAUSAL_T in include/kccot.h): with w_d = exp(-d^2 / (2 sigma^2)),
+        s[t] = sum_{d=0}^{min(r,t)} w_d x[t-d] / sum_{d=0}^{min(r,t)} w_d -- no padding, the early frames use the truncated,
+        renormalised window, so s[0] = x[0] -- then / global max.  Radius: the temporal one."""
+        return self._apply(inputs, sigma, self.temporal_radius, _lib.SMOOTH_T | _lib.SMOOTH_CAUSAL_T)
+
     def spatial_convolution(self, inputs, sigma):
         """NOT reference behaviour.  The reference's 2-D path (data_utils.py:523-550) convolves
         VALID without padding and then reshapes the shrunken result to the input shape, which

@@ -181,6 +181,8 @@ class KCCOTTrainer:
     def _smooth(self, v, sigma):
         if self.kernel_choice == "1d":                                           # :229-239
             return self.gaussian_kernel.temporal_convolution(v, sigma)
+        if self.kernel_choice == "1d_causal":                                    # not in the reference: frame t keeps to frames <= t
+            return self.gaussian_kernel.causal_temporal_convolution(v, sigma)
         if self.kernel_choice == "2d":
             return self.gaussian_kernel.spatial_convolution(v, sigma)
         if self.kernel_choice == "3d":
