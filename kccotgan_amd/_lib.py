@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``).
+"""ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h`` and ``include/kccot_models.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -106,6 +106,14 @@ SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_models.h one to one (model-side kernels, outside the versioned
+# surface of kccot.h)
+MODEL_SIGNATURES = {
+    "kccot_sigmoid_lstm_fwd_f32": (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
+    "kccot_sigmoid_lstm_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -116,8 +124,8 @@ def _load():
             "kccotgan_amd: %s is missing -- build it with `make -C kccotgan_amd/csrc` "
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError here = header and library out of step
+    for name, (res, args) in list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()):
+        fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args
     return lib

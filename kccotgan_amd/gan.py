@@ -328,6 +328,46 @@ class VideoDecoderConvLSTM(nn.Module):
     call = forward
 
 
+def _sigmoid_lstm_hip(gx, wh, save_c):
+    """h_seq [B,T,U] and, when save_c, c_seq of kccot_sigmoid_lstm_fwd_f32 (c_seq = NULL otherwise: inference)."""
+    from ._lib import lib, ptr, check, stream_of, empty
+    B, T, U = gx.shape[0], gx.shape[1], wh.shape[1]
+    h_seq = empty((B, T, U), torch.float32, gx.device)
+    c_seq = empty((B, T, U), torch.float32, gx.device) if save_c else None
+    check(lib.kccot_sigmoid_lstm_fwd_f32(ptr(gx), ptr(wh), B, T, U, ptr(h_seq), ptr(c_seq), stream_of(gx)), "sigmoid_lstm_fwd")
+    return h_seq, c_seq
+
+
+class _SigmoidLSTMHIP(torch.autograd.Function):
+    """h_seq = lstm(gx, wh): the whole sigmoid-LSTM recurrence over T as ONE HIP launch each way
+    (kccot_sigmoid_lstm_{fwd,bwd}_f32) instead of a dozen tensor-op launches per step.  gx [B,T,4U] = wx(x) with the bias,
+    wh [4U,U]; the gradient of wh is one GEMM over the kernel's dgx."""
+
+    @staticmethod
+    def forward(ctx, gx, wh):
+        gx, wh = gx.contiguous(), wh.contiguous()
+        h_seq, c_seq = _sigmoid_lstm_hip(gx, wh, True)
+        ctx.save_for_backward(gx, wh, h_seq, c_seq)
+        return h_seq
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dh_seq):
+        from ._lib import lib, ptr, check, stream_of, empty_like
+        gx, wh, h_seq, c_seq = ctx.saved_tensors
+        B, T, U = h_seq.shape
+        dh_seq = dh_seq.contiguous()
+        dgx = empty_like(gx)
+        check(lib.kccot_sigmoid_lstm_bwd_f32(ptr(gx), ptr(wh), ptr(h_seq), ptr(c_seq), ptr(dh_seq), B, T, U, ptr(dgx), stream_of(gx)),
+              "sigmoid_lstm_bwd")
+        dwh = dgx[:, 1:].reshape(-1, 4 * U).t() @ h_seq[:, :-1].reshape(-1, U) if ctx.needs_input_grad[1] else None
+        return dgx, dwh
+
+
+# KCCOT_SIGMOID_LSTM=torch: the stock tensor-op loop over T (also what CPU tensors, double precision and units > 64 take)
+_SLSTM_HIP = os.environ.get("KCCOT_SIGMOID_LSTM", "hip") != "torch"
+
+
 class _SigmoidLSTM(nn.Module):
     """Keras LSTM(units, activation='sigmoid', return_sequences=True) (gan.py:418): the cell
     candidate and the output use sigmoid instead of tanh, which nn.LSTM cannot express."""
@@ -341,6 +381,10 @@ class _SigmoidLSTM(nn.Module):
     def forward(self, x):                              # [B, T, F]
         B, T, _ = x.shape
         gx = self.wx(x)
+        if _SLSTM_HIP and gx.is_cuda and gx.dtype == torch.float32 and self.units <= 64:
+            if not (torch.is_grad_enabled() and (gx.requires_grad or self.wh.weight.requires_grad)):
+                return _sigmoid_lstm_hip(gx.contiguous(), self.wh.weight.detach().contiguous(), False)[0]   # nothing to keep
+            return _SigmoidLSTMHIP.apply(gx, self.wh.weight)
         h = x.new_zeros(B, self.units)
         c = torch.zeros_like(h)
         outs = []
