@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h`` and ``include/kccot_models.h``).
+"""ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h`` and
+``include/kccot_weighted.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -114,6 +115,20 @@ MODEL_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_weighted.h one to one (the Sinkhorn solver and the one-batch loss with
+# weighted marginals: an extension outside the versioned surface of kccot.h)
+WEIGHTED_SIGNATURES = {
+    "kccot_sinkhorn_weighted_fwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _f, _i, _i, _f, _i, _fp, _fp, _fp, _fp, _fp, _fp, _sz,
+                                             _fp]),
+    "kccot_sinkhorn_weighted_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_weighted_sinkhorn_loss_workspace_bytes": (_sz, [_i, _i64]),
+    "kccot_weighted_sinkhorn_loss_fwd_f32": (_i, [_fp, _fp, _i, _i64, _f, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _i, _f, _u,
+                                                  _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_weighted_sinkhorn_loss_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i64, _f, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp, _fp,
+                                                  _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -124,7 +139,7 @@ def _load():
             "kccotgan_amd: %s is missing -- build it with `make -C kccotgan_amd/csrc` "
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include "../../include/kccot.h"
+#include "../../include/kccot_weighted.h"
 
 #define KCCOT_WAVE 64
 
@@ -142,6 +143,15 @@ __device__ __forceinline__ float block_max(float v, float* scratch) {
 int sinkhorn_fused_weighted(const float* C, int nprob, const float* w, int n, float eps, int L, int Lmin, float thresh,
                             float* cost_out, int32_t* nits_out, float* loss_out, int32_t* ticket, float* dC_unit,
                             hipStream_t st);
+
+// sinkhorn.hip: the divergence with weighted marginals (a,b), (a,a), (b,b) on C3 = [xy, xx, yy]; a = w_real, b = w_fake [n]
+int sinkhorn_divergence_weighted_fwd(const float* C3, const float* w_real, const float* w_fake, int n, float eps, int L,
+                                     int Lmin, float thresh, float* u_hist, float* v_hist, float* cost3_out,
+                                     int32_t* nits_out, float* loss_out, int32_t* ticket, void* ws, size_t ws_bytes,
+                                     hipStream_t st);
+int sinkhorn_divergence_weighted_bwd(const float* C3, const float* w_real, const float* w_fake, const float* u_hist,
+                                     const float* v_hist, const int32_t* nits, int n, float eps, int L, const float* gloss,
+                                     float* gc3, float* dC3, void* ws, size_t ws_bytes, hipStream_t st);
 
 // cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) over the whole batch.  bicausal selects the
 // feature-gradient jobs of the bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake,

@@ -15,7 +15,7 @@ static int loss3_fwd(bool bicausal, const float* real, const float* fake, int B,
                      const float* h_real, const float* m_real, const float* m_fake, int T, int J, float eps, int L, int Lmin,
                      float thresh, unsigned flags, float* C3, float* u_hist, float* v_hist, float* dC3_unit,
                      float* cost3_out, int32_t* nits_out, float* loss_out, int32_t* ticket, void* ws, size_t ws_bytes,
-                     kccot_stream_t stream) {
+                     kccot_stream_t stream, const float* w_real = nullptr, const float* w_fake = nullptr) {
     if (flags & KCCOT_COST_BICAUSAL_TERM_ONLY)      // a step of the sharded caller's assembly, not a cost-ladder option
         return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_BICAUSAL_TERM_ONLY does not apply to a loss call");
     if (flags & KCCOT_COST_RBF_SUM)                 // the sharded kernel-MMD's step on a finished distance block
@@ -25,6 +25,9 @@ static int loss3_fwd(bool bicausal, const float* real, const float* fake, int B,
     if (rc) return rc;
     if (bicausal && (rc = launch_bicausal_cost_add(C3, B, h_fake, h_real, m_real, m_fake, T, J, sc, (hipStream_t)stream)))
         return rc;
+    if (w_real)     // weighted marginals (kccot_weighted.h): the history path only, the fused launch is not weighted
+        return sinkhorn_divergence_weighted_fwd(C3, w_real, w_fake, B, eps, L, Lmin, thresh, u_hist, v_hist, cost3_out,
+                                                nits_out, loss_out, ticket, ws, ws_bytes, (hipStream_t)stream);
     if (dC3_unit)
         return kccot_sinkhorn_divergence_fused_f32(C3, B, eps, L, Lmin, thresh, cost3_out, nits_out, loss_out, ticket,
                                                    dC3_unit, stream);
@@ -38,7 +41,8 @@ static int loss3_bwd(bool bicausal, const float* gloss, const float* real, const
                      const float* h_fake, const float* h_real, const float* m_real, const float* m_fake, int T, int J,
                      float eps, int L, const float* C3, const float* u_hist, const float* v_hist, const int32_t* nits,
                      const float* dC3_unit, float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake,
-                     void* ws, size_t ws_bytes, kccot_stream_t stream) {
+                     void* ws, size_t ws_bytes, kccot_stream_t stream, const float* w_real = nullptr,
+                     const float* w_fake = nullptr) {
     const hipStream_t st = (hipStream_t)stream;
     if (dC3_unit)
         return cost3_bwd_loss(dC3_unit, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake,
@@ -50,7 +54,10 @@ static int loss3_bwd(bool bicausal, const float* gloss, const float* real, const
     void* stage = base + off_gc + 256;
     const size_t stage_bytes = ws_bytes - off_gc - 256;
     int rc;
-    if (kccot_sinkhorn_workspace_bytes(3, B) > 0) {
+    if (w_real) {
+        rc = sinkhorn_divergence_weighted_bwd(C3, w_real, w_fake, u_hist, v_hist, nits, B, eps, L, gloss, gc, dC3, stage,
+                                              stage_bytes, st);
+    } else if (kccot_sinkhorn_workspace_bytes(3, B) > 0) {
         // streaming solver (n > 128): weights {2,-1,-1} * gloss first, then the generic reverse sweep
         rc = kccot_mixed_divergence_bwd_f32(gloss, gc, stream);
         if (rc) return rc;
@@ -178,4 +185,54 @@ extern "C" int kccot_bicausal_sinkhorn_loss_bwd_f32(const float* gloss, const fl
                     kccot_bicausal_sinkhorn_loss_workspace_bytes(B, K));
     return loss3_bwd(true, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, C3, u_hist, v_hist,
                      nits, dC3_unit, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream);
+}
+
+// ---- the one-batch loss with weighted marginals (include/kccot_weighted.h) -------------------------------------------
+// 2 W(C_xy; a, b) - W(C_xx; a, a) - W(C_yy; b, b) with a = w_real, b = w_fake: the launch sequence of
+// kccot_sinkhorn_loss_fwd_f32 / _bwd_f32 on the dual-history path with the weighted solver kernels.  An EXTENSION: the
+// reference's compute_sinkhorn hard-codes uniform marginals.
+extern "C" size_t kccot_weighted_sinkhorn_loss_workspace_bytes(int B, int64_t K) {
+    return kccot_sinkhorn_loss_workspace_bytes(B, K);
+}
+
+extern "C" int kccot_weighted_sinkhorn_loss_fwd_f32(const float* real, const float* fake, int B, int64_t K, float sc,
+                                                    const float* h_fake, const float* h_real, const float* m_real,
+                                                    const float* m_fake, int T, int J, float eps, int L, int Lmin,
+                                                    float thresh, unsigned flags, const float* w_real, const float* w_fake,
+                                                    float* C3, float* u_hist, float* v_hist, float* cost3_out,
+                                                    int32_t* nits_out, float* loss_out, int32_t* ticket, void* ws,
+                                                    size_t ws_bytes, kccot_stream_t stream) {
+    if (!real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w_real || !w_fake)
+        return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_fwd: null input pointer");
+    if (!C3 || !cost3_out || !nits_out || !loss_out || !ticket)
+        return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_fwd: null output pointer");
+    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
+        return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_fwd: bad arguments B=%d K=%lld T=%d J=%d L=%d eps=%g", B,
+                    (long long)K, T, J, L, (double)eps);
+    if ((u_hist == nullptr) != (v_hist == nullptr))
+        return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_fwd: u_hist and v_hist must be given together");
+    if (!ws || ws_bytes < kccot_weighted_sinkhorn_loss_workspace_bytes(B, K))
+        return fail(KCCOT_EWORKSPACE, "weighted_sinkhorn_loss_fwd: workspace %zu < %zu bytes", ws_bytes,
+                    kccot_weighted_sinkhorn_loss_workspace_bytes(B, K));
+    return loss3_fwd(false, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, Lmin, thresh, flags, C3,
+                     u_hist, v_hist, nullptr, cost3_out, nits_out, loss_out, ticket, ws, ws_bytes, stream, w_real, w_fake);
+}
+
+extern "C" int kccot_weighted_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const float* fake, int B,
+                                                    int64_t K, float sc, const float* h_fake, const float* h_real,
+                                                    const float* m_real, const float* m_fake, int T, int J, float eps,
+                                                    int L, const float* w_real, const float* w_fake, const float* C3,
+                                                    const float* u_hist, const float* v_hist, const int32_t* nits,
+                                                    float* dfake, float* dh_fake, float* dh_real, float* dm_real,
+                                                    float* dm_fake, void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w_real || !w_fake)
+        return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_bwd: null input pointer");
+    if (!C3 || !u_hist || !v_hist || !nits) return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_bwd: null pointer");
+    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
+        return fail(KCCOT_EINVAL, "weighted_sinkhorn_loss_bwd: bad arguments B=%d K=%lld T=%d J=%d", B, (long long)K, T, J);
+    if (!ws || ws_bytes < kccot_weighted_sinkhorn_loss_workspace_bytes(B, K))
+        return fail(KCCOT_EWORKSPACE, "weighted_sinkhorn_loss_bwd: workspace %zu < %zu bytes", ws_bytes,
+                    kccot_weighted_sinkhorn_loss_workspace_bytes(B, K));
+    return loss3_bwd(false, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, C3, u_hist, v_hist,
+                     nits, nullptr, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream, w_real, w_fake);
 }

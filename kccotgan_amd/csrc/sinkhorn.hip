@@ -70,7 +70,21 @@ struct SinkArgs {
     float* loss_out;      // mixed divergence 2*cost[0]-cost[1]-cost[2] (nprob == 3), or null
     int* ticket;          // arrival counter for loss_out: zero on entry, reset to zero by the last workgroup
     int shortcut;         // 1: exact periodic-state shortcut enabled (see sinkhorn_fwd_reg)
+    // weighted marginals (the _w kernels only; an extension, not reference behaviour): strictly positive finite weights,
+    // log taken once per lane before the loop.  w_div = 0: wa, wb are [nprob,n], problem p reads row p.  w_div = 1: wa =
+    // w_real [n], wb = w_fake [n] and the three problems of the divergence read (a,b), (a,a), (b,b).  NULL: mu = nu = 1/n.
+    const float* wa;
+    const float* wb;
+    int w_div;
 };
+
+// the marginal weights of problem p (see SinkArgs::wa)
+__device__ __forceinline__ const float* weights_of(const float* wa, const float* wb, int w_div, int p, int n, bool rows) {
+    if (w_div) return rows ? (p == 2 ? wb : wa) : (p == 1 ? wa : wb);
+    return (rows ? wa : wb) + (int64_t)p * n;
+}
+// a weight the solvers accept: strictly positive and finite (NaN fails the first comparison)
+__device__ __forceinline__ bool weight_ok(float w) { return w > 0.f && w < INFINITY; }
 
 // Load the EPT contiguous duals a thread needs (entries q*EPT .. q*EPT+EPT-1) from LDS.
 template <int EPT>
@@ -154,7 +168,7 @@ __device__ __forceinline__ void load_costs(const float* __restrict__ C, int n, i
     }
 }
 
-template <int EPT, int LPR, bool SHORTCUT>
+template <int EPT, int LPR, bool SHORTCUT, bool WEIGHTED>
 __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     // padded so that the float4 reads of lines past n stay inside the arrays
     __shared__ __attribute__((aligned(16))) float u_s[SK_MAXN + 16 * 16];
@@ -172,6 +186,19 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     __syncthreads();
 
     const float lw2 = __builtin_amdgcn_logf(1.0f / (float)n);   // log2(mu) = log2(nu), gan_utils.py:138-139
+    // log2 of this line's marginals: the constant, or (WEIGHTED) the line's own weights, loaded and checked ONCE here.  A
+    // weight that is <= 0 or not finite poisons the whole problem (NaN cost, nits = -1: the convention of an aborted
+    // multi-CU solve) instead of producing a finite, plausible and wrong cost; the loop is then not entered.
+    float lwu = lw2, lwv = lw2;
+    bool bad = false;
+    if constexpr (WEIGHTED) {
+        const float wu = active ? weights_of(a.wa, a.wb, a.w_div, p, n, true)[line] : 1.f;
+        const float wv = active ? weights_of(a.wa, a.wb, a.w_div, p, n, false)[line] : 1.f;
+        bad = __syncthreads_or(!(weight_ok(wu) && weight_ok(wv)));
+        lwu = __builtin_amdgcn_logf(wu);
+        lwv = __builtin_amdgcn_logf(wv);
+    }
+    const int Lrun = (WEIGHTED && bad) ? 0 : a.L;
     // stop rule in log2 units: sum|u-u_prev| = sum|U-U_prev| * eps*ln2
     const float err_scale = a.eps * LN2;
 
@@ -205,10 +232,10 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
 
     int nits = 0;
     float ui = 0.f, vj = 0.f;   // this line's duals (every lane of the line holds them)
-    for (int it = 0; it < a.L; ++it) {
+    for (int it = 0; it < Lrun; ++it) {
         // every lane executes the half-steps (DPP reads neighbours); only real lines store
         KCCOT_STAMP(0);
-        const float un = half_step<EPT, LPR, true>(crow, ui, v_s, q, lw2);
+        const float un = half_step<EPT, LPR, true>(crow, ui, v_s, q, lwu);
         KCCOT_STAMP(1);
         const float du = (active && q == 0) ? fabsf(un - ui) : 0.f;
         int bits = 0;
@@ -227,7 +254,7 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
         KCCOT_STAMP(2);
         lds_barrier();      // the history stores stay in flight (nothing in this kernel reads them back)
         KCCOT_STAMP(3);
-        const float vn = half_step<EPT, LPR, false>(ccol, vj, u_s, q, lw2);
+        const float vn = half_step<EPT, LPR, false>(ccol, vj, u_s, q, lwv);
         KCCOT_STAMP(4);
         if (SHORTCUT && detect) {
             const unsigned b = __float_as_uint(vn);
@@ -306,13 +333,15 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
         for (int m = 0; m < EPT; ++m) {
             const int idx = q * EPT + m;
             if (idx < n) {
-                const float pi = __builtin_amdgcn_exp2f((ui - crow[m]) + v_s[idx]);
+                float pi = __builtin_amdgcn_exp2f((ui - crow[m]) + v_s[idx]);
+                if (WEIGHTED && bad) pi = NAN;
                 part += pi * C[(int64_t)line * n + idx];
                 if (a.pi_out) a.pi_out[(int64_t)p * n * n + (int64_t)line * n + idx] = pi;
             }
         }
     }
-    const float cost = block_sum(part, red);
+    float cost = block_sum(part, red);
+    if (WEIGHTED && bad) { cost = NAN; nits = -1; }
     if (t == 0) {
         // the last of the three workgroups to arrive combines the costs (gan_utils.py:225).  Placement-independent
         // hand-off without fences -- the FIRST ROW of MI355X_MICROARCH.md's table of measured hand-offs ("one lane of each
@@ -343,9 +372,14 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
 
 // the default (exact periodic-state shortcut compiled in) and the every-iteration variant
 template <int EPT, int LPR>
-__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fwd_reg(SinkArgs a) { sinkhorn_fwd_body<EPT, LPR, true>(a); }
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fwd_reg(SinkArgs a) { sinkhorn_fwd_body<EPT, LPR, true, false>(a); }
 template <int EPT, int LPR>
-__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fwd_reg_full(SinkArgs a) { sinkhorn_fwd_body<EPT, LPR, false>(a); }
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fwd_reg_full(SinkArgs a) { sinkhorn_fwd_body<EPT, LPR, false, false>(a); }
+// the same two with weighted marginals (SinkArgs::wa / wb)
+template <int EPT, int LPR>
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fwd_reg_w(SinkArgs a) { sinkhorn_fwd_body<EPT, LPR, true, true>(a); }
+template <int EPT, int LPR>
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fwd_reg_full_w(SinkArgs a) { sinkhorn_fwd_body<EPT, LPR, false, true>(a); }
 
 // ------------------------------------------------------------------------------------------
 // reverse sweep
@@ -377,11 +411,24 @@ struct SinkBwdArgs {
     int n, L;
     float eps, inv_eps;
     int div_weights;      // 1: gcost[p] = {2,-1,-1}[p] * gcost[0]   (d(2 xy - xx - yy), gan_utils.py:225)
+    const float* wa;      // weighted marginals as in SinkArgs (sinkhorn_bwd_reg_w only)
+    const float* wb;
+    int w_div;
 };
 
-template <int EPT, int LPR>
-__global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
+// WEIGHTED (mu = a, nu = b): the column sums of the second argument are b_j and the row sums of the first a_i, so
+//   Q_t[i,j] = exp2((U_t,i - c2_ij) + (V_t,j - log2 b_j)),   P_t[i,j] = exp2(((U_t,i - log2 a_i) - c2_ij) + V_{t-1,j})
+// -- the one place where the sweep substitutes the marginal for a sum of a plan.  The shifted duals U - log2 a and
+// V - log2 b are formed by the thread that refills the LDS slots (off the dependent chain) and parked beside the plain
+// ones, so a pass costs the same instructions as with the constant; everything else is unchanged (log a and log b enter
+// the updates additively; the weights themselves are not differentiated).  A problem the forward poisoned (nits < 0: a
+// weight <= 0 or not finite) gets NaN gradients.
+template <int EPT, int LPR, bool WEIGHTED>
+__device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
     constexpr int PADN = SK_MAXN + 16 * 16;
+    __shared__ __attribute__((aligned(16))) float Ua[WEIGHTED ? 2 : 1][WEIGHTED ? PADN : 4];
+    __shared__ __attribute__((aligned(16))) float Va[WEIGHTED ? 2 : 1][WEIGHTED ? PADN : 4];
+    __shared__ float lab[WEIGHTED ? 2 : 1][WEIGHTED ? SK_MAXN : 1];     // log2 a, log2 b: entry t is thread t's alone
     __shared__ __attribute__((aligned(16))) float U[2][PADN];
     __shared__ __attribute__((aligned(16))) float V[2][PADN];
     __shared__ __attribute__((aligned(16))) float gu[PADN];
@@ -395,6 +442,22 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
     const int nits = a.nits[p];
     const float* uh = a.u_hist + (int64_t)p * a.L * n;
     const float* vh = a.v_hist + (int64_t)p * a.L * n;
+    if constexpr (WEIGHTED) {
+        if (nits < 0) {           // block-uniform
+            if (active) {
+#pragma unroll
+                for (int m = 0; m < EPT; ++m) {
+                    const int idx = q * EPT + m;
+                    if (idx < n) a.dC[(int64_t)p * n * n + (int64_t)line * n + idx] = NAN;
+                }
+            }
+            return;
+        }
+        if (t < n) {    // kept in LDS, not in two registers: the EPT = 16 forms run at the 128-VGPR cap
+            lab[0][t] = __builtin_amdgcn_logf(weights_of(a.wa, a.wb, a.w_div, p, n, true)[t]);
+            lab[1][t] = __builtin_amdgcn_logf(weights_of(a.wa, a.wb, a.w_div, p, n, false)[t]);
+        }
+    }
 
     float crow[EPT], ccol[EPT], drow[EPT], dcol[EPT];
     load_costs<EPT, LPR>(C, n, line, q, k2, crow, ccol);
@@ -403,6 +466,7 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
     for (int i = t; i < PADN; i += blockDim.x) {
         U[0][i] = U[1][i] = V[0][i] = V[1][i] = 0.f;
         gu[i] = gv[i] = 0.f;
+        if constexpr (WEIGHTED) Ua[0][i] = Ua[1][i] = Va[0][i] = Va[1][i] = 0.f;
     }
     __syncthreads();
     // history index k holds (U_{k+1}, V_{k+1}); iteration `it` (1-based) lives in slot it & 1;
@@ -413,6 +477,11 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
         U[nits & 1][t] = hist_u(nits, t);
         V[nits & 1][t] = hist_v(nits, t);
         V[(nits - 1) & 1][t] = hist_v(nits - 1, t);
+        if constexpr (WEIGHTED) {
+            Ua[nits & 1][t] = hist_u(nits, t) - lab[0][t];
+            Va[nits & 1][t] = hist_v(nits, t) - lab[1][t];
+            Va[(nits - 1) & 1][t] = hist_v(nits - 1, t) - lab[1][t];
+        }
     }
     // prefetch for the first in-loop refill: U_{nits-1}, V_{nits-2}
     float nu = (t < n) ? hist_u(nits - 1, t) : 0.f;
@@ -453,9 +522,9 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
         const float* Vp = V[(it - 1) & 1];
         // (A) through v_t: row pass with Q_t
         {
-            const float ui = Uc[lsafe] - lw2;
+            const float ui = WEIGHTED ? Uc[lsafe] : Uc[lsafe] - lw2;
             float ov[EPT], og[EPT];
-            load_other<EPT>(ov, Vc, q);
+            load_other<EPT>(ov, WEIGHTED ? Va[it & 1] : Vc, q);
             load_other<EPT>(og, gv, q);
             float s = 0.f;
 #pragma unroll
@@ -475,14 +544,15 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
         if (t < n) {
             U[(it - 1) & 1][t] = nu;
             V[it & 1][t] = nv;
+            if constexpr (WEIGHTED) { Ua[(it - 1) & 1][t] = nu - lab[0][t]; Va[it & 1][t] = nv - lab[1][t]; }
             nu = hist_u(it - 2, t);
             nv = hist_v(it - 3, t);
         }
         // (B) through u_t: column pass with P_t
         {
-            const float vj = Vp[lsafe] - lw2;
+            const float vj = WEIGHTED ? Vp[lsafe] : Vp[lsafe] - lw2;
             float ou[EPT], og[EPT];
-            load_other<EPT>(ou, Uc, q);
+            load_other<EPT>(ou, WEIGHTED ? Ua[it & 1] : Uc, q);
             load_other<EPT>(og, gu, q);
             float r = 0.f;
 #pragma unroll
@@ -516,6 +586,11 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) {
         }
     }
 }
+
+template <int EPT, int LPR>
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) { sinkhorn_bwd_body<EPT, LPR, false>(a); }
+template <int EPT, int LPR>
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg_w(SinkBwdArgs a) { sinkhorn_bwd_body<EPT, LPR, true>(a); }
 
 // ------------------------------------------------------------------------------------------
 // Fused solve + reverse sweep of the mixed divergence (compute_sinkhorn_loss when a gradient is wanted):
@@ -846,9 +921,10 @@ namespace kccot {
 size_t sinkhorn_gen_workspace_bytes(int nprob, int n);
 int launch_sinkhorn_fwd_gen(const float* C, int nprob, int n, float eps, int L, int Lmin, float thresh, int stop_mode,
                             float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
-                            size_t ws_bytes, hipStream_t st);
+                            size_t ws_bytes, hipStream_t st, const float* wa, const float* wb, int w_div);
 int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
-                            float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st);
+                            float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st,
+                            const float* wa, const float* wb, int w_div);
 }  // namespace kccot
 
 using namespace kccot;
@@ -881,11 +957,16 @@ extern "C" size_t kccot_sinkhorn_workspace_bytes(int nprob, int n) {
     }
 
 // div_loss / div_ticket: the loss and the arrival counter of the divergence forward's in-kernel combine
-// (kccot_sinkhorn_divergence_fwd_f32); null for the plain solves
+// (kccot_sinkhorn_divergence_fwd_f32); null for the plain solves.  wa / wb / w_div: weighted marginals (SinkArgs), both
+// null for mu = nu = 1/n.  Weighted solves run the register kernels (n <= 128) or the streaming single-workgroup solver,
+// never the multi-CU one.
 static int sinkhorn_fwd(const float* C, int nprob, int n, float eps, int L, int Lmin, float thresh, int stop_mode,
                         float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
-                        size_t ws_bytes, kccot_stream_t stream, float* div_loss, int* div_ticket) {
+                        size_t ws_bytes, kccot_stream_t stream, float* div_loss, int* div_ticket,
+                        const float* wa = nullptr, const float* wb = nullptr, int w_div = 0) {
     if (!C || !cost_out || !nits_out) return fail(KCCOT_EINVAL, "sinkhorn_fwd: null pointer");
+    if ((wa == nullptr) != (wb == nullptr)) return fail(KCCOT_EINVAL, "sinkhorn_fwd: give both weight vectors or neither");
+    if (w_div && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_fwd: the divergence's weights need nprob = 3");
     if (nprob <= 0 || n <= 0 || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "sinkhorn_fwd: bad arguments nprob=%d n=%d L=%d eps=%g", nprob, n, L, (double)eps);
     if ((u_hist == nullptr) != (v_hist == nullptr))
@@ -894,14 +975,22 @@ static int sinkhorn_fwd(const float* C, int nprob, int n, float eps, int L, int 
         return fail(KCCOT_EINVAL, "sinkhorn_fwd: bad stop_mode %d", stop_mode);
     if (n > SK_MAXN)
         return launch_sinkhorn_fwd_gen(C, nprob, n, eps, L, Lmin, thresh, stop_mode, u_hist, v_hist, cost_out, nits_out,
-                                       pi_out, ws, ws_bytes, (hipStream_t)stream);
+                                       pi_out, ws, ws_bytes, (hipStream_t)stream, wa, wb, w_div);
     SinkGeom g = sink_geom(n, true);
     SinkArgs a{C, n, L, Lmin, stop_mode, eps, (float)(1.0 / (double)eps), thresh, u_hist, v_hist, cost_out, nits_out, pi_out,
-               nullptr, div_loss, div_ticket, sink_shortcut_enabled()};
+               nullptr, div_loss, div_ticket, sink_shortcut_enabled(), wa, wb, w_div};
 #ifdef KCCOT_DIAG
     a.diag = static_cast<unsigned long long*>(ws);   // diagnostic build: ws carries the stamp buffer
 #endif
     hipStream_t st = (hipStream_t)stream;
+    if (wa) {
+        if (a.shortcut) {
+            KCCOT_SK_DISPATCH(sinkhorn_fwd_reg_w, a, g, nprob, st)
+        } else {
+            KCCOT_SK_DISPATCH(sinkhorn_fwd_reg_full_w, a, g, nprob, st)
+        }
+        return launch_status("sinkhorn_fwd_reg_w");
+    }
     if (a.shortcut) {
         KCCOT_SK_DISPATCH(sinkhorn_fwd_reg, a, g, nprob, st)
     } else {
@@ -936,17 +1025,24 @@ extern "C" int kccot_sinkhorn_status(const int32_t* nits, int nprob, kccot_strea
 // (kccot_sinkhorn_divergence_bwd_f32); 0: gcost holds one float per problem
 static int sinkhorn_bwd(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
                         float eps, int L, const float* gcost, float* dC_out, void* ws, size_t ws_bytes,
-                        kccot_stream_t stream, int div_weights) {
+                        kccot_stream_t stream, int div_weights, const float* wa = nullptr, const float* wb = nullptr,
+                        int w_div = 0) {
     if (!C || !u_hist || !v_hist || !nits || !gcost || !dC_out)
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: null pointer");
+    if ((wa == nullptr) != (wb == nullptr)) return fail(KCCOT_EINVAL, "sinkhorn_bwd: give both weight vectors or neither");
+    if (w_div && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_bwd: the divergence's weights need nprob = 3");
     if (nprob <= 0 || n <= 0 || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: bad arguments nprob=%d n=%d L=%d eps=%g", nprob, n, L, (double)eps);
     if (n > SK_MAXN)
         return launch_sinkhorn_bwd_gen(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes,
-                                       (hipStream_t)stream);
+                                       (hipStream_t)stream, wa, wb, w_div);
     SinkGeom g = sink_geom(n, false);
-    SinkBwdArgs a{C, u_hist, v_hist, nits, gcost, dC_out, n, L, eps, (float)(1.0 / (double)eps), div_weights};
+    SinkBwdArgs a{C, u_hist, v_hist, nits, gcost, dC_out, n, L, eps, (float)(1.0 / (double)eps), div_weights, wa, wb, w_div};
     hipStream_t st = (hipStream_t)stream;
+    if (wa) {
+        KCCOT_SK_DISPATCH(sinkhorn_bwd_reg_w, a, g, nprob, st)
+        return launch_status("sinkhorn_bwd_reg_w");
+    }
     KCCOT_SK_DISPATCH(sinkhorn_bwd_reg, a, g, nprob, st)
     return launch_status("sinkhorn_bwd_reg");
 }
@@ -1071,4 +1167,56 @@ extern "C" int kccot_sinkhorn_divergence_bwd_f32(const float* C3, const float* u
     if (!gloss) return fail(KCCOT_EINVAL, "sinkhorn_divergence_bwd: null pointer");
     if (n > SK_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_divergence_bwd: use mixed_divergence_bwd + sinkhorn_bwd for n > %d", SK_MAXN);
     return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3_out, ws, ws_bytes, stream, 1);
+}
+
+// ---- weighted marginals (include/kccot_weighted.h) ---------------------------------------------------------------------
+// The solve and its reverse sweep with mu = a, nu = b instead of 1/n: an EXTENSION (the reference's compute_sinkhorn
+// hard-codes the uniform marginals).  Same kernels, instantiated with the weights; the one-launch fused loss and the
+// multi-CU solver are not weighted and are never selected here.
+extern "C" int kccot_sinkhorn_weighted_fwd_f32(const float* C, const float* a, const float* b, int nprob, int n, float eps,
+                                               int L, int Lmin, float thresh, int stop_mode, float* u_hist, float* v_hist,
+                                               float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
+                                               size_t ws_bytes, kccot_stream_t stream) {
+    if (!a || !b) return fail(KCCOT_EINVAL, "sinkhorn_weighted_fwd: null weight pointer");
+    return sinkhorn_fwd(C, nprob, n, eps, L, Lmin, thresh, stop_mode, u_hist, v_hist, cost_out, nits_out, pi_out, ws,
+                        ws_bytes, stream, nullptr, nullptr, a, b, 0);
+}
+
+extern "C" int kccot_sinkhorn_weighted_bwd_f32(const float* C, const float* a, const float* b, const float* u_hist,
+                                               const float* v_hist, const int32_t* nits, int nprob, int n, float eps, int L,
+                                               const float* gcost, float* dC_out, void* ws, size_t ws_bytes,
+                                               kccot_stream_t stream) {
+    if (!a || !b) return fail(KCCOT_EINVAL, "sinkhorn_weighted_bwd: null weight pointer");
+    return sinkhorn_bwd(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes, stream, 0, a, b, 0);
+}
+
+// the three solves of the weighted divergence on C3 = [xy, xx, yy] with marginals (a,b), (a,a), (b,b), a = w_real,
+// b = w_fake, and loss = 2 xy - xx - yy (loss.hip)
+int kccot::sinkhorn_divergence_weighted_fwd(const float* C3, const float* w_real, const float* w_fake, int n, float eps,
+                                            int L, int Lmin, float thresh, float* u_hist, float* v_hist, float* cost3_out,
+                                            int32_t* nits_out, float* loss_out, int32_t* ticket, void* ws, size_t ws_bytes,
+                                            hipStream_t st) {
+    if (!w_real || !w_fake || !loss_out || !ticket) return fail(KCCOT_EINVAL, "weighted divergence: null pointer");
+    if (n > SK_MAXN) {   // streaming solver: no in-kernel combine
+        int rc = sinkhorn_fwd(C3, 3, n, eps, L, Lmin, thresh, KCCOT_STOP_COUNT, u_hist, v_hist, cost3_out, nits_out, nullptr,
+                              ws, ws_bytes, st, nullptr, nullptr, w_real, w_fake, 1);
+        if (rc) return rc;
+        return kccot_mixed_divergence_fwd_f32(cost3_out, loss_out, st);
+    }
+    return sinkhorn_fwd(C3, 3, n, eps, L, Lmin, thresh, KCCOT_STOP_COUNT, u_hist, v_hist, cost3_out, nits_out, nullptr, ws,
+                        ws_bytes, st, loss_out, reinterpret_cast<int*>(ticket), w_real, w_fake, 1);
+}
+
+// dC3 = d loss / d C3 scaled by gloss[0]; gc3: three floats of scratch (the per-problem weights, n > 128 only)
+int kccot::sinkhorn_divergence_weighted_bwd(const float* C3, const float* w_real, const float* w_fake, const float* u_hist,
+                                            const float* v_hist, const int32_t* nits, int n, float eps, int L,
+                                            const float* gloss, float* gc3, float* dC3, void* ws, size_t ws_bytes,
+                                            hipStream_t st) {
+    if (!w_real || !w_fake || !gloss || !gc3) return fail(KCCOT_EINVAL, "weighted divergence backward: null pointer");
+    if (n > SK_MAXN) {
+        int rc = kccot_mixed_divergence_bwd_f32(gloss, gc3, st);
+        if (rc) return rc;
+        return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gc3, dC3, ws, ws_bytes, st, 0, w_real, w_fake, 1);
+    }
+    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3, ws, ws_bytes, st, 1, w_real, w_fake, 1);
 }

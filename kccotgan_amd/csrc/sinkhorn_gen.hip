@@ -83,10 +83,39 @@ struct SinkGenArgs {
     float* cost_out;
     int32_t* nits_out;
     float* pi_out;
+    // weighted marginals (the <true> instantiations only; an extension, not reference behaviour).  w_div = 0: wa, wb are
+    // [nprob,n], problem p reads row p; w_div = 1: wa = w_real [n], wb = w_fake [n] and the three problems of the
+    // divergence read (a,b), (a,a), (b,b).  NULL: mu = nu = 1/n.
+    const float* wa;
+    const float* wb;
+    int w_div;
 };
 
+__device__ __forceinline__ const float* gen_weights_of(const float* wa, const float* wb, int w_div, int p, int n, bool rows) {
+    if (w_div) return rows ? (p == 2 ? wb : wa) : (p == 1 ? wa : wb);
+    return (rows ? wa : wb) + (int64_t)p * n;
+}
+
+// Stage scale * log(weight) of problem p's marginals in LDS, once, before the loop.  Returns (block-uniform) whether a
+// weight is <= 0 or not finite: the problem is then poisoned (NaN cost, nits = -1) instead of solved.
+__device__ __forceinline__ bool gen_stage_weights(const float* wa, const float* wb, int w_div, int p, int n, float scale,
+                                                  float* la_s, float* lb_s) {
+    const float* pa = gen_weights_of(wa, wb, w_div, p, n, true);
+    const float* pb = gen_weights_of(wa, wb, w_div, p, n, false);
+    int bad = 0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const float x = pa[i], y = pb[i];
+        bad |= !(x > 0.f && x < INFINITY && y > 0.f && y < INFINITY);
+        la_s[i] = scale * logf(x);
+        lb_s[i] = scale * logf(y);
+    }
+    return __syncthreads_or(bad);
+}
+
+template <bool W>
 __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen(SinkGenArgs a) {
     __shared__ float u_s[SG_MAXN], v_s[SG_MAXN], red[16];
+    __shared__ float la_s[W ? SG_MAXN : 1], lb_s[W ? SG_MAXN : 1];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
     const float* C = a.C + (int64_t)p * n * n;
@@ -95,12 +124,15 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen(SinkGenArgs a) {
     for (int i = t; i < n; i += SG_THREADS) { u_s[i] = 0.f; v_s[i] = 0.f; }
     __syncthreads();
     const float log_w = logf(1.0f / (float)n);
+    bool bad = false;
+    if constexpr (W) bad = gen_stage_weights(a.wa, a.wb, a.w_div, p, n, 1.f, la_s, lb_s);
+    const int Lrun = (W && bad) ? 0 : a.L;
     int nits = 0;
-    for (int it = 0; it < a.L; ++it) {
+    for (int it = 0; it < Lrun; ++it) {
         float du = 0.f;
         for (int i = wid; i < n; i += nw) {       // u-update: rows of C
             const float ui = u_s[i];
-            const float un = line_update<true>(C + (int64_t)i * n, v_s, n, ui, eps, inv_eps, log_w);
+            const float un = line_update<true>(C + (int64_t)i * n, v_s, n, ui, eps, inv_eps, W ? la_s[i] : log_w);
             if (lane == 0) {
                 du += fabsf(un - ui);
                 // written after the barrier below would need a second array; u_s[i] is read by this
@@ -112,7 +144,7 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen(SinkGenArgs a) {
         __syncthreads();
         for (int j = wid; j < n; j += nw) {       // v-update: rows of C^T, with the new u
             const float vj = v_s[j];
-            const float vn = line_update<false>(CT + (int64_t)j * n, u_s, n, vj, eps, inv_eps, log_w);
+            const float vn = line_update<false>(CT + (int64_t)j * n, u_s, n, vj, eps, inv_eps, W ? lb_s[j] : log_w);
             if (lane == 0) {
                 v_s[j] = vn;
                 if (a.v_hist) a.v_hist[((int64_t)p * a.L + it) * n + j] = vn;
@@ -132,13 +164,15 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen(SinkGenArgs a) {
         const float* row = C + (int64_t)i * n;
         for (int j = lane; j < n; j += 64) {
             const float c = row[j];
-            const float pi = __builtin_amdgcn_exp2f(((-c + ui) + v_s[j]) * inv_eps * SG_LOG2E);
+            float pi = __builtin_amdgcn_exp2f(((-c + ui) + v_s[j]) * inv_eps * SG_LOG2E);
+            if (W && bad) pi = NAN;
             part += pi * c;
             if (a.pi_out) a.pi_out[(int64_t)p * n * n + (int64_t)i * n + j] = pi;
         }
     }
-    const float cost = block_sum(part, red);
-    if (t == 0) { a.cost_out[p] = cost; a.nits_out[p] = nits; a.nits_out[gridDim.x + p] = nits; }
+    float cost = block_sum(part, red);
+    if (W && bad) { cost = NAN; nits = -1; }
+    if (t == 0) { a.cost_out[p] = cost; a.nits_out[p] = nits; a.nits_out[gridDim.x + p] = nits < 0 ? 0 : nits; }
 }
 
 // ---- forward, wide form (n % 4 == 0) --------------------------------------------------------------
@@ -193,10 +227,11 @@ __device__ __forceinline__ float gen_update_line(const float4 (&c)[NV], const fl
     return eps * (log_w - lse) + self;
 }
 
-template <int NV>
+template <int NV, bool W>
 __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen4(SinkGenArgs a) {
     constexpr int RB = 8 / NV;
     __shared__ __attribute__((aligned(16))) float u_s[SG_MAXN], v_s[SG_MAXN];
+    __shared__ float la_s[W ? SG_MAXN : 1], lb_s[W ? SG_MAXN : 1];
     __shared__ float red[16];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
@@ -206,8 +241,12 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen4(SinkGenArgs a) {
     for (int i = t; i < SG_MAXN; i += SG_THREADS) { u_s[i] = 0.f; v_s[i] = 0.f; }
     __syncthreads();
     const float log_w = logf(1.0f / (float)n);
-    // one half-step: lines of M (rows of C, or rows of C^T), `self_s` updated in place, `other_s` read-only
-    auto half = [&](const float* M, float* self_s, const float* other_s, float* hist, bool row, float& du) {
+    bool bad = false;
+    if constexpr (W) bad = gen_stage_weights(a.wa, a.wb, a.w_div, p, n, 1.f, la_s, lb_s);
+    const int Lrun = (W && bad) ? 0 : a.L;
+    // one half-step: lines of M (rows of C, or rows of C^T), `self_s` updated in place, `other_s` read-only;
+    // lw_s: the staged log-weights of the updated side (W only)
+    auto half = [&](const float* M, float* self_s, const float* other_s, float* hist, bool row, float& du, const float* lw_s) {
         float4 o[NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -222,8 +261,9 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen4(SinkGenArgs a) {
             for (int r = 0; r < RB; ++r) {
                 const int line = base + r * nw;
                 const float sv = self_s[line < n ? line : 0];
-                const float nv = row ? gen_update_line<NV, true>(cur[r], o, n, sv, eps, inv_eps, log_w)
-                                     : gen_update_line<NV, false>(cur[r], o, n, sv, eps, inv_eps, log_w);
+                const float lw = W ? lw_s[line < n ? line : 0] : log_w;
+                const float nv = row ? gen_update_line<NV, true>(cur[r], o, n, sv, eps, inv_eps, lw)
+                                     : gen_update_line<NV, false>(cur[r], o, n, sv, eps, inv_eps, lw);
                 if (line < n && lane == 0) {
                     du += fabsf(nv - sv);
                     self_s[line] = nv;          // read by this wave only during the pass
@@ -237,11 +277,11 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen4(SinkGenArgs a) {
         }
     };
     int nits = 0;
-    for (int it = 0; it < a.L; ++it) {
+    for (int it = 0; it < Lrun; ++it) {
         float du = 0.f, dv = 0.f;
-        half(C, u_s, v_s, a.u_hist ? a.u_hist + ((int64_t)p * a.L + it) * n : nullptr, true, du);
+        half(C, u_s, v_s, a.u_hist ? a.u_hist + ((int64_t)p * a.L + it) * n : nullptr, true, du, la_s);
         __syncthreads();
-        half(CT, v_s, u_s, a.v_hist ? a.v_hist + ((int64_t)p * a.L + it) * n : nullptr, false, dv);
+        half(CT, v_s, u_s, a.v_hist ? a.v_hist + ((int64_t)p * a.L + it) * n : nullptr, false, dv, lb_s);
         __syncthreads();
         nits = it + 1;
         const bool reached = (a.stop_mode == KCCOT_STOP_INDEX) ? (it >= a.Lmin) : (nits >= a.Lmin);
@@ -256,13 +296,15 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen4(SinkGenArgs a) {
         const float* row = C + (int64_t)i * n;
         for (int j = lane; j < n; j += 64) {
             const float c = row[j];
-            const float pi = __builtin_amdgcn_exp2f(((-c + ui) + v_s[j]) * inv_eps * SG_LOG2E);
+            float pi = __builtin_amdgcn_exp2f(((-c + ui) + v_s[j]) * inv_eps * SG_LOG2E);
+            if (W && bad) pi = NAN;
             part += pi * c;
             if (a.pi_out) a.pi_out[(int64_t)p * n * n + (int64_t)i * n + j] = pi;
         }
     }
-    const float cost = block_sum(part, red);
-    if (t == 0) { a.cost_out[p] = cost; a.nits_out[p] = nits; a.nits_out[gridDim.x + p] = nits; }
+    float cost = block_sum(part, red);
+    if (W && bad) { cost = NAN; nits = -1; }
+    if (t == 0) { a.cost_out[p] = cost; a.nits_out[p] = nits; a.nits_out[gridDim.x + p] = nits < 0 ? 0 : nits; }
 }
 
 // ---- forward, 16 lanes per line (n % 4 == 0, n <= 512) -----------------------------------------------
@@ -299,9 +341,10 @@ __device__ __forceinline__ float gen16_update(const float4 (&c)[NV], const float
     return eps * (log_w - lse) + self;
 }
 
-template <int NV>
+template <int NV, bool W>
 __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) {
     __shared__ __attribute__((aligned(16))) float u_s[SG_MAXN], v_s[SG_MAXN];
+    __shared__ float la_s[W ? SG_MAXN : 1], lb_s[W ? SG_MAXN : 1];
     __shared__ float red[16];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
@@ -312,6 +355,9 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) 
     for (int i = t; i < SG_MAXN; i += SG_THREADS) { u_s[i] = 0.f; v_s[i] = 0.f; }
     __syncthreads();
     const float log_w = logf(1.0f / (float)n);
+    bool bad = false;
+    if constexpr (W) bad = gen_stage_weights(a.wa, a.wb, a.w_div, p, n, 1.f, la_s, lb_s);
+    const int Lrun = (W && bad) ? 0 : a.L;
     const int ngroups = (n + 3) >> 2;
     auto load_group = [&](float4 (&c)[NV], const float* M, int g) {
         const int line = 4 * g + sub;
@@ -322,7 +368,7 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) 
             c[v] = *reinterpret_cast<const float4*>(M + (int64_t)lc * n + (idx < n ? idx : n - 4));
         }
     };
-    auto half = [&](const float* M, float* self_s, const float* other_s, float* hist, bool row, float& du) {
+    auto half = [&](const float* M, float* self_s, const float* other_s, float* hist, bool row, float& du, const float* lw_s) {
         float4 o[NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -335,8 +381,9 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) 
             if (g + nw < ngroups) load_group(nxt, M, g + nw);
             const int line = 4 * g + sub;
             const float sv = self_s[line < n ? line : 0];
-            const float nv = row ? gen16_update<NV, true>(cur, o, n, q, sv, eps, inv_eps, log_w)
-                                 : gen16_update<NV, false>(cur, o, n, q, sv, eps, inv_eps, log_w);
+            const float lw = W ? lw_s[line < n ? line : 0] : log_w;
+            const float nv = row ? gen16_update<NV, true>(cur, o, n, q, sv, eps, inv_eps, lw)
+                                 : gen16_update<NV, false>(cur, o, n, q, sv, eps, inv_eps, lw);
             if (line < n && q == 0) {
                 du += fabsf(nv - sv);
                 self_s[line] = nv;              // read by this wave only during the pass
@@ -347,11 +394,11 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) 
         }
     };
     int nits = 0;
-    for (int it = 0; it < a.L; ++it) {
+    for (int it = 0; it < Lrun; ++it) {
         float du = 0.f, dv = 0.f;
-        half(C, u_s, v_s, a.u_hist ? a.u_hist + ((int64_t)p * a.L + it) * n : nullptr, true, du);
+        half(C, u_s, v_s, a.u_hist ? a.u_hist + ((int64_t)p * a.L + it) * n : nullptr, true, du, la_s);
         __syncthreads();
-        half(CT, v_s, u_s, a.v_hist ? a.v_hist + ((int64_t)p * a.L + it) * n : nullptr, false, dv);
+        half(CT, v_s, u_s, a.v_hist ? a.v_hist + ((int64_t)p * a.L + it) * n : nullptr, false, dv, lb_s);
         __syncthreads();
         nits = it + 1;
         const bool reached = (a.stop_mode == KCCOT_STOP_INDEX) ? (it >= a.Lmin) : (nits >= a.Lmin);
@@ -366,13 +413,15 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) 
         const float* row = C + (int64_t)i * n;
         for (int j = lane; j < n; j += 64) {
             const float c = row[j];
-            const float pi = __builtin_amdgcn_exp2f(((-c + ui) + v_s[j]) * inv_eps * SG_LOG2E);
+            float pi = __builtin_amdgcn_exp2f(((-c + ui) + v_s[j]) * inv_eps * SG_LOG2E);
+            if (W && bad) pi = NAN;
             part += pi * c;
             if (a.pi_out) a.pi_out[(int64_t)p * n * n + (int64_t)i * n + j] = pi;
         }
     }
-    const float cost = block_sum(part, red);
-    if (t == 0) { a.cost_out[p] = cost; a.nits_out[p] = nits; a.nits_out[gridDim.x + p] = nits; }
+    float cost = block_sum(part, red);
+    if (W && bad) { cost = NAN; nits = -1; }
+    if (t == 0) { a.cost_out[p] = cost; a.nits_out[p] = nits; a.nits_out[gridDim.x + p] = nits < 0 ? 0 : nits; }
 }
 
 struct SinkGenBwdArgs {
@@ -386,13 +435,21 @@ struct SinkGenBwdArgs {
     float* dCT;          // [nprob,n,n]: accumulator of the column passes, in transposed layout
     int n, L;
     float eps, inv_eps;
+    const float* wa;     // weighted marginals as in SinkGenArgs (sinkhorn_bwd_gen<true> only)
+    const float* wb;
+    int w_div;
 };
 
 // See sinkhorn.hip for the derivation.  Accumulators live in global memory (L2): the row pass
 // owns dC[i][:] of its rows, the column pass owns dCT[j][:] of its columns, so every
 // read-modify-write is private to one wave and coalesced.
+// W (mu = a, nu = b): the column sums that normalise Q_t are b_j and the row sums that normalise P_t are a_i, so the
+// constant eps*log(1/n) becomes eps*log b_j in pass A and eps*log a_i in pass B (staged in LDS once).  A problem the
+// forward poisoned (nits < 0) gets NaN gradients.
+template <bool W>
 __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a) {
     __shared__ float ut[SG_MAXN], vt[SG_MAXN], vp[SG_MAXN], gu[SG_MAXN], gv[SG_MAXN];
+    __shared__ float ea_s[W ? SG_MAXN : 1], eb_s[W ? SG_MAXN : 1];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
     const float* C = a.C + (int64_t)p * n * n;
@@ -403,6 +460,13 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
     const int nits = a.nits[p];
     const float* uh = a.u_hist + (int64_t)p * a.L * n;
     const float* vh = a.v_hist + (int64_t)p * a.L * n;
+    if constexpr (W) {
+        if (nits < 0) {          // block-uniform
+            for (int64_t e = t; e < (int64_t)n * n; e += SG_THREADS) { dC[e] = NAN; dCT[e] = 0.f; }
+            return;
+        }
+        gen_stage_weights(a.wa, a.wb, a.w_div, p, n, eps, ea_s, eb_s);
+    }
     for (int i = t; i < n; i += SG_THREADS) {
         ut[i] = nits > 0 ? uh[(int64_t)(nits - 1) * n + i] : 0.f;
         vt[i] = nits > 0 ? vh[(int64_t)(nits - 1) * n + i] : 0.f;
@@ -448,7 +512,7 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
             float s = 0.f;
             for (int j = lane; j < n; j += 64) {
                 const float c = C[(int64_t)i * n + j];
-                const float qq = __builtin_amdgcn_exp2f((((-c + ui) + vt[j]) - aconst) * inv_eps * SG_LOG2E);
+                const float qq = __builtin_amdgcn_exp2f((((-c + ui) + vt[j]) - (W ? eb_s[j] : aconst)) * inv_eps * SG_LOG2E);
                 const float w = qq * gv[j];
                 dC[(int64_t)i * n + j] += w;
                 s += w;
@@ -463,7 +527,7 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
             float r = 0.f;
             for (int i = lane; i < n; i += 64) {
                 const float c = CT[(int64_t)j * n + i];
-                const float pp = __builtin_amdgcn_exp2f((((-c + ut[i]) + vj) - aconst) * inv_eps * SG_LOG2E);
+                const float pp = __builtin_amdgcn_exp2f((((-c + ut[i]) + vj) - (W ? ea_s[i] : aconst)) * inv_eps * SG_LOG2E);
                 const float w = pp * gu[i];
                 dCT[(int64_t)j * n + i] += w;
                 r += w;
@@ -489,32 +553,42 @@ int launch_sinkhorn_bwd_coop(const float* C, const float* u_hist, const float* v
 
 int launch_sinkhorn_fwd_gen(const float* C, int nprob, int n, float eps, int L, int Lmin, float thresh, int stop_mode,
                             float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
-                            size_t ws_bytes, hipStream_t st) {
+                            size_t ws_bytes, hipStream_t st, const float* wa, const float* wb, int w_div) {
     if (n > SG_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fwd: n=%d > %d", n, SG_MAXN);
     const size_t need = sinkhorn_gen_workspace_bytes(nprob, n);
     if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "sinkhorn_fwd: workspace %zu < required %zu", ws_bytes, need);
-    if (sinkhorn_coop_eligible(nprob, n) && L < SK_COOP_MAX_L)     // the exchange tags hold 2 L + 2 half-steps in 20 bits
+    // (the multi-CU solver is not weighted: weighted solves stay on the single-workgroup kernels below)
+    if (!wa && sinkhorn_coop_eligible(nprob, n) && L < SK_COOP_MAX_L)     // the exchange tags hold 2 L + 2 half-steps in 20 bits
         return launch_sinkhorn_fwd_coop(C, nprob, n, eps, L, Lmin, thresh, stop_mode, u_hist, v_hist, cost_out, nits_out, pi_out, ws, st);
     float* CT = static_cast<float*>(ws);
     dim3 tg((n + 31) / 32, (n + 31) / 32, nprob);
     hipLaunchKernelGGL(transpose_batched, tg, dim3(256), 0, st, C, CT, n);
     int rc = launch_status("transpose_batched");
     if (rc) return rc;
-    SinkGenArgs a{C, CT, n, L, Lmin, stop_mode, eps, (float)(1.0 / (double)eps), thresh, u_hist, v_hist, cost_out, nits_out, pi_out};
+    SinkGenArgs a{C, CT, n, L, Lmin, stop_mode, eps, (float)(1.0 / (double)eps), thresh, u_hist, v_hist, cost_out, nits_out, pi_out,
+                  wa, wb, w_div};
     const bool wide = (n % 4 == 0) && ((uintptr_t)C % 16 == 0);
-    if (!wide) hipLaunchKernelGGL(sinkhorn_fwd_gen, dim3(nprob), dim3(SG_THREADS), 0, st, a);
-    else if (n <= 256) hipLaunchKernelGGL(sinkhorn_fwd_gen16<4>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
-    else if (n <= 512) hipLaunchKernelGGL(sinkhorn_fwd_gen16<8>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(sinkhorn_fwd_gen4<4>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    if (wa) {
+        if (!wide) hipLaunchKernelGGL(sinkhorn_fwd_gen<true>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
+        else if (n <= 256) hipLaunchKernelGGL((sinkhorn_fwd_gen16<4, true>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
+        else if (n <= 512) hipLaunchKernelGGL((sinkhorn_fwd_gen16<8, true>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((sinkhorn_fwd_gen4<4, true>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
+        return launch_status("sinkhorn_fwd_gen (weighted)");
+    }
+    if (!wide) hipLaunchKernelGGL(sinkhorn_fwd_gen<false>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    else if (n <= 256) hipLaunchKernelGGL((sinkhorn_fwd_gen16<4, false>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    else if (n <= 512) hipLaunchKernelGGL((sinkhorn_fwd_gen16<8, false>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((sinkhorn_fwd_gen4<4, false>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
     return launch_status("sinkhorn_fwd_gen");
 }
 
 int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
-                            float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st) {
+                            float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st,
+                            const float* wa, const float* wb, int w_div) {
     if (n > SG_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_bwd: n=%d > %d", n, SG_MAXN);
     const size_t need = sinkhorn_gen_workspace_bytes(nprob, n);
     if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "sinkhorn_bwd: workspace %zu < required %zu", ws_bytes, need);
-    if (sinkhorn_coop_eligible(nprob, n) && L < SK_COOP_MAX_L)     // the exchange tags hold 2 L + 2 half-steps in 20 bits
+    if (!wa && sinkhorn_coop_eligible(nprob, n) && L < SK_COOP_MAX_L)     // the exchange tags hold 2 L + 2 half-steps in 20 bits
         return launch_sinkhorn_bwd_coop(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC, ws, st);
     float* CT = static_cast<float*>(ws);
     float* dCT = reinterpret_cast<float*>(static_cast<char*>(ws) + need / 2);
@@ -522,8 +596,9 @@ int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_
     hipLaunchKernelGGL(transpose_batched, tg, dim3(256), 0, st, C, CT, n);
     int rc = launch_status("transpose_batched");
     if (rc) return rc;
-    SinkGenBwdArgs a{C, CT, u_hist, v_hist, nits, gcost, dC, dCT, n, L, eps, (float)(1.0 / (double)eps)};
-    hipLaunchKernelGGL(sinkhorn_bwd_gen, dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    SinkGenBwdArgs a{C, CT, u_hist, v_hist, nits, gcost, dC, dCT, n, L, eps, (float)(1.0 / (double)eps), wa, wb, w_div};
+    if (wa) hipLaunchKernelGGL(sinkhorn_bwd_gen<true>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(sinkhorn_bwd_gen<false>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
     if ((rc = launch_status("sinkhorn_bwd_gen"))) return rc;
     hipLaunchKernelGGL(add_transposed_batched, tg, dim3(256), 0, st, (const float*)dCT, dC, n);
     return launch_status("add_transposed_batched");

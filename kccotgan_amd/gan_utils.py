@@ -17,8 +17,8 @@ from ._lib import lib, check, ptr, stream_of, workspace
 
 __all__ = ["cost_xy", "modified_cost", "bi_causal_modified_cost", "benchmark_sinkhorn",
            "compute_sinkhorn", "compute_N", "scale_invariante_martingale_regularization",
-           "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "compute_bicausal_sinkhorn_loss", "last_info",
-           "raise_if_solver_aborted"]
+           "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "compute_bicausal_sinkhorn_loss",
+           "compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
 
 # executed Sinkhorn iteration counts (device int32 tensors, no host sync) of the latest calls;
 # the reference keeps them in a local (gan_utils.py:148,158) although its docstring promises them
@@ -385,6 +385,128 @@ class _SinkhornLoss(torch.autograd.Function):
         return (None,) * 7 + (dfake, *dfeats)
 
 
+def _weighted_path(n):
+    """The solver a weighted solve of size n runs on (include/kccot_weighted.h): never the multi-CU solver, never the
+    one-launch fused loss."""
+    return "register" if n <= 128 else "streaming"
+
+
+def _weights(w, n, name, normalize):
+    """A weight vector as contiguous fp32 [n] on the device; ``normalize`` divides by its sum there (no host sync)."""
+    if not torch.is_tensor(w):
+        raise TypeError("%s must be a tensor of %d weights" % (name, n))
+    _lib.require_gpu(w)
+    if w.requires_grad:
+        raise NotImplementedError("%s: the weighted Sinkhorn solver does not differentiate w.r.t. the weights" % name)
+    if w.dim() != 1 or w.shape[0] != n:
+        raise ValueError("%s must be [%d], got %s" % (name, n, tuple(w.shape)))
+    w = w if w.dtype == torch.float32 else w.float()
+    if normalize:
+        w = w / w.sum()
+    return w.contiguous()
+
+
+class _WeightedSinkhorn(torch.autograd.Function):
+    """_Sinkhorn with marginals a, b [nprob,n] (kccot_sinkhorn_weighted_fwd_f32 / _bwd_f32); no gradient to a, b."""
+
+    @staticmethod
+    def forward(ctx, C, a, b, eps, L, Lmin, stop_mode, tag):
+        nprob, n, _ = C.shape
+        C = C.contiguous()
+        dev = C.device
+        keep = ctx.needs_input_grad[0]
+        Lh = max(int(L), 1)
+        u_hist = _lib.empty((nprob, Lh, n), torch.float32, dev) if keep else None
+        v_hist = _lib.empty((nprob, Lh, n), torch.float32, dev) if keep else None
+        cost = _lib.empty((nprob,), torch.float32, dev)
+        nits = _lib.empty((2 * nprob,), torch.int32, dev)   # [reference-equivalent counts | iterations executed]
+        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(nprob, n), C)
+        check(lib.kccot_sinkhorn_weighted_fwd_f32(ptr(C), ptr(a), ptr(b), nprob, n, float(eps), int(L), int(Lmin), _THRESH,
+                                                  stop_mode, ptr(u_hist), ptr(v_hist), ptr(cost), ptr(nits), None, ws, wsb,
+                                                  stream_of(C)), "sinkhorn_weighted_fwd")
+        last_info[tag], last_info[tag + "_executed"] = nits[:nprob], nits[nprob:]
+        last_info[tag + "_path"] = _weighted_path(n)
+        if keep:
+            ctx.save_for_backward(C, a, b, u_hist, v_hist, nits)
+        ctx.eps, ctx.Lh = float(eps), Lh
+        return cost
+
+    @staticmethod
+    def backward(ctx, gcost):
+        C, a, b, u_hist, v_hist, nits = ctx.saved_tensors
+        nprob, n, _ = C.shape
+        gcost = gcost.contiguous().float()
+        dC = _lib.empty_like(C)
+        ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(nprob, n), C)
+        check(lib.kccot_sinkhorn_weighted_bwd_f32(ptr(C), ptr(a), ptr(b), ptr(u_hist), ptr(v_hist), ptr(nits), nprob, n,
+                                                  ctx.eps, ctx.Lh, ptr(gcost), ptr(dC), ws, wsb, stream_of(C)),
+              "sinkhorn_weighted_bwd")
+        return dC, None, None, None, None, None, None, None
+
+
+class _WeightedSinkhornLoss(torch.autograd.Function):
+    """The one-batch loss with weighted marginals as ONE library call each way (kccot_weighted_sinkhorn_loss_fwd_f32 /
+    _bwd_f32), modelled on _SinkhornLoss: always the dual-history path (the fused launch is not weighted)."""
+
+    @staticmethod
+    def forward(ctx, tag, sc, eps, L, Lmin, w_real, w_fake, real, fake, *feats):
+        B, K = real.shape
+        if fake.shape != real.shape:
+            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        for t in feats:
+            if t.shape != (B, T, J):
+                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
+        need = ctx.needs_input_grad[7:]                                             # real, fake, *feats
+        if need[0]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
+                                      "use compute_weighted_sinkhorn for a gradient w.r.t. both operands")
+        dev = real.device
+        keep = any(need[1:])
+        Lh = max(int(L), 1)
+        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
+        small = _lib.empty((4,), torch.float32, dev)                                 # costs | loss
+        nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
+        st = stream_of(real)
+        ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_workspace_bytes(B, K), real, st)
+        state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)      # C | u_hist | v_hist
+        uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
+        loss = small[3:]
+        check(lib.kccot_weighted_sinkhorn_loss_fwd_f32(
+            ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
+            ptr(w_real), ptr(w_fake), ptr(state), uh, vh, ptr(small), ptr(nits), ptr(loss), ptr(_ticket(dev)), ws, wsb, st),
+            "weighted_sinkhorn_loss_fwd")
+        last_info[tag], last_info[tag + "_executed"] = nits[:3], nits[3:]
+        last_info[tag + "_costs"] = small[:3]
+        last_info[tag + "_C3"] = state[:3 * B * B].view(3, B, B)
+        last_info[tag + "_fused_sweep"] = False
+        last_info[tag + "_path"] = _weighted_path(B)
+        if keep:
+            ctx.save_for_backward(real, fake, *feats, w_real, w_fake, state, nits)
+        ctx.cfg = (float(sc), float(eps), Lh)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        real, fake, *feats, w_real, w_fake, state, nits = ctx.saved_tensors
+        sc, eps, Lh = ctx.cfg
+        B, K = real.shape
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
+        need = ctx.needs_input_grad[8:]                                             # fake, *feats
+        g = g.reshape(1).contiguous().float()
+        dfake = _lib.empty_like(fake) if need[0] else None
+        df = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[1:]) else None
+        dfeats = [(df[i] if need[1 + i] else None) for i in range(4)]
+        st = stream_of(real)
+        ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_workspace_bytes(B, K), real, st)
+        check(lib.kccot_weighted_sinkhorn_loss_bwd_f32(
+            ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w_real), ptr(w_fake), ptr(state),
+            ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ws, wsb, st),
+            "weighted_sinkhorn_loss_bwd")
+        return (None,) * 8 + (dfake, *dfeats)
+
+
 class _MixedDivergence(torch.autograd.Function):
     """loss = 2*W_xy - W_xx - W_yy (gan_utils.py:225) as one launch each way."""
 
@@ -555,14 +677,60 @@ def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
                                *feats)
 
 
+def compute_weighted_sinkhorn(x, y, hy, Mx, scaling_coef, mu, nu, epsilon=1.0, L=100):
+    """compute_sinkhorn (gan_utils.py:124-165, bi_causal=False) with marginals ``mu`` over the rows (the samples of x) and
+    ``nu`` over the columns (the samples of y) instead of 1/n: the updates subtract from log mu_i / log nu_j.
+    EXTENSION: the reference hard-codes the uniform marginals (gan_utils.py:138-139).  ``mu`` / ``nu``: [n] device tensors,
+    strictly positive, finite and normalised by the caller; they are not differentiated (one that requires a gradient
+    raises NotImplementedError).  With mu = nu = 1/n this is compute_sinkhorn to rounding.  A weight that is <= 0 or not
+    finite gives a NaN cost and a negative count in last_info["compute_weighted_sinkhorn"] (raise_if_solver_aborted
+    reports it).  n <= 128 runs the register-resident kernels, larger n the streaming single-workgroup solver; the multi-CU
+    solver is not weighted and never used here (last_info["compute_weighted_sinkhorn_path"])."""
+    C = modified_cost(x, y, hy, Mx, scaling_coef)
+    n = C.shape[0]
+    if C.shape[1] != n:
+        raise ValueError("the weighted solver needs as many samples in x as in y; got %s" % (tuple(C.shape),))
+    a, b = _weights(mu, n, "mu", False), _weights(nu, n, "nu", False)
+    return _WeightedSinkhorn.apply(C.unsqueeze(0), a.unsqueeze(0), b.unsqueeze(0), float(epsilon), int(L), _LMIN,
+                                   _lib.STOP_COUNT, "compute_weighted_sinkhorn")[0]
+
+
+def compute_weighted_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
+                                   m_fake, w_real, w_fake, video=True, normalize=True):
+    """The one-batch causal loss with weighted samples,
+
+        2 W(C_xy; a, b) - W(C_xx; a, a) - W(C_yy; b, b),   a = w_real, b = w_fake,
+
+    with the three cost matrices of compute_sinkhorn_loss and W the Sinkhorn cost whose marginals are a over the rows and
+    b over the columns (compute_weighted_sinkhorn).  EXTENSION, not reference behaviour: the reference's solver
+    hard-codes mu = nu = 1/n; this is what the kernel estimator of the conditional law, importance weights or shards of
+    unequal mass need.  With uniform weights it is compute_sinkhorn_loss(..., honor_eps_l=True) to rounding.
+
+    ``sinkhorn_eps`` and ``sinkhorn_l`` ARE applied (this function has no reference quirk to mirror).  ``w_real`` /
+    ``w_fake``: [B] device tensors of strictly positive finite weights; ``normalize=True`` divides each by its sum on the
+    device (no host synchronisation), ``normalize=False`` takes them as given.  Differentiable w.r.t. the fake videos and
+    the four features; a real video or a weight tensor that requires a gradient raises NotImplementedError.  Always the
+    dual-history path: the one-launch fused loss and the multi-CU solver are not weighted.  Records
+    last_info["compute_weighted_sinkhorn_loss"] (three counts; negative = a bad weight poisoned that problem, its cost
+    and the gradients are NaN), ``..._executed``, ``..._costs`` [3], ``..._C3`` [3,B,B], ``..._fused_sweep`` (False) and
+    ``..._path`` ("register" for B <= 128, "streaming" above)."""
+    vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l, True)
+    B = vids[0].shape[0]
+    a, b = _weights(w_real, B, "w_real", normalize), _weights(w_fake, B, "w_fake", normalize)
+    return _WeightedSinkhornLoss.apply("compute_weighted_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, a, b, *vids,
+                                       *feats)
+
+
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
     """Synchronising status check of the solves recorded under ``tags`` in ``last_info`` (``kccot_sinkhorn_status``): raises
     ``KccotError`` if a multi-CU Sinkhorn solve gave up (negative iteration count; its cost and gradients are NaN).  The
     training loop calls it where the reference has its non-finite-loss guard (kernel_train.py:323), so that an aborted
     solve is reported as what it is and not as an exploded loss.  Default: the loss the trainer just evaluated (the
     single-GPU and the batch-sharded path both record their counts under "compute_sinkhorn_loss"); pass
-    ``("compute_sinkhorn",)`` / ``("benchmark_sinkhorn",)`` after a direct call of those.  A checked entry is dropped, so a
-    stale record of an earlier call can never be blamed for a later NaN."""
+    ``("compute_sinkhorn",)`` / ``("benchmark_sinkhorn",)`` after a direct call of those.  Under the tags of the weighted
+    solver ("compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss") a negative count means a weight that was <= 0
+    or not finite, and the error says so.  A checked entry is dropped, so a stale record of an earlier call can never be
+    blamed for a later NaN."""
     for tag in tags:
         nits = last_info.pop(tag, None)
         if nits is None or not torch.is_tensor(nits) or not nits.is_cuda:
@@ -570,5 +738,8 @@ def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
         nits = nits.contiguous()
         rc = lib.kccot_sinkhorn_status(ptr(nits), int(nits.numel()), stream_of(nits))
         if rc == _lib.EABORTED:
+            if tag.startswith("compute_weighted_"):     # the weighted solver never runs multi-CU: the only cause
+                raise _lib.KccotError("%s: a marginal weight of a problem was <= 0 or not finite; its cost and gradients "
+                                      "are NaN (counts %s)" % (tag, nits.tolist()))
             raise _lib.KccotError("%s: %s" % (tag, lib.kccot_last_error().decode("utf-8", "replace")))
         check(rc, "sinkhorn_status")
