@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h`` and
-``include/kccot_weighted.h``).
+"""ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
+``include/kccot_weighted.h`` and ``include/kccot_smooth_causal3.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -129,6 +129,15 @@ WEIGHTED_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_smooth_causal3.h one to one (the causal 3-D smoothing -- past-only in
+# time, symmetric in space: an extension outside the versioned surface of kccot.h).  flags: the protocol bits only.
+SMOOTH3C_SIGNATURES = {
+    "kccot_smooth_causal3_fwd_f32": (_i, [_fp, _i, _i, _i, _i, _i, _f, _i, _u, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_causal3_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_causal3_bwd_sharded_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -139,7 +148,8 @@ def _load():
             "kccotgan_amd: %s is missing -- build it with `make -C kccotgan_amd/csrc` "
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) +
+                              list(SMOOTH3C_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
 // per axis plus the max/scale pass (algorithmic minimum: one read + one write in total).
 #include "common.h"
 #include "options.h"
+#include "../../include/kccot_smooth_causal3.h"
 #include <math.h>
 #include <float.h>
 #include <stdlib.h>
@@ -1034,14 +1035,19 @@ struct Fused3Args {
     int nblk, mode;        // mode: 0 maxima only, 1 write s / max, 2 write s
     int H, T, W, wt, ntw, hseg, nseg;
     Taps tp;
+    CausalTaps ct;         // CAUSAL: the one-sided T stencil (behind every other field: their kernarg offsets stay)
 };
 
+// CAUSAL (the causal 3-D call, include/kccot_smooth_causal3.h): the T stage is the one-sided stencil of smooth_causal -- the R
+// rows in front of the plane are ZEROS (written once; nothing mirrors into them), no rows behind it are read, the strip sums
+// w_d x[t-d] in ascending d and multiplies the finished sum by 1 / Z_t of its row (selected per row from the R + 1 reciprocals
+// in the args).  Same fma order as smooth_causal: bit-identical to the causal chain.  W and H stages, window, prefetch unchanged.
 // Registers decide the occupancy, and the occupancy the speed: the SQ counters of the first version said VALU 36 % busy at 1.5 waves
 // per SIMD (180 registers x 384 threads = ONE workgroup per CU) -- bound by LDS round trips and barriers.  Holding that body to 168
 // registers with amdgpu_waves_per_eu made it SLOWER (4.61 -> 6.95 ms at configs[4]: the spill reloads share vmcnt with the plane
 // prefetch and expose its latency every step); buffer descriptors instead of 64-bit per-lane addresses freed the registers
 // without a spill (158), and two workgroups fit.
-template <int R, int CC, int NI>
+template <int R, int CC, int NI, bool CAUSAL>
 __global__ __launch_bounds__(512) void smooth_fused3(Fused3Args a) {
     typedef WalkVec<4>::type V4;        // (arrays of HIP's float4 struct stayed in scratch memory; ext-vectors do not)
     extern __shared__ __attribute__((aligned(16))) float f3lds[];
@@ -1083,8 +1089,10 @@ __global__ __launch_bounds__(512) void smooth_fused3(Fused3Args a) {
         i = ok[n] ? i : T * Q - 1;
         const int t = i / Q, q = i - t * Q;
         goff[n] = (t * WC + w0 * C + 4 * q) * 4;          // bytes within a plane of the sample
-        const int mr = mirror(t);
-        amir[n] = (ok[n] && mr >= 0) ? mr * pitch + HP + 4 * q : dummy;
+        if constexpr (!CAUSAL) {
+            const int mr = mirror(t);
+            amir[n] = (ok[n] && mr >= 0) ? mr * pitch + HP + 4 * q : dummy;
+        }
         boff[n] = t * pitch + HP + 4 * q;
     }
     // owned halo floats: R*C either side of every row
@@ -1101,8 +1109,13 @@ __global__ __launch_bounds__(512) void smooth_fused3(Fused3Args a) {
         hgo[n] = (t * WC + reflect(w, a.W) * C + c) * 4;
         const int col = side ? HP + wtc + jj : HP - RC + jj;
         hao[n] = hok ? (t + R) * pitch + col : dummy;
-        const int mr = mirror(t);
-        hmi[n] = (hok && mr >= 0) ? mr * pitch + col : dummy;
+        if constexpr (!CAUSAL) {
+            const int mr = mirror(t);
+            hmi[n] = (hok && mr >= 0) ? mr * pitch + col : dummy;
+        }
+    }
+    if constexpr (CAUSAL) {     // frames in front of the first: zeros, for the whole walk (the first step's barrier orders them)
+        for (int i = tid; i < R * pitch; i += NT) A[i] = 0.f;
     }
     float m = 1.f;
     if (a.mode == 1) {
@@ -1152,12 +1165,12 @@ __global__ __launch_bounds__(512) void smooth_fused3(Fused3Args a) {
 #pragma unroll
             for (int n = 0; n < NI; ++n) {
                 *reinterpret_cast<V4*>(f3lds + (ok[n] ? boff[n] + R * pitch : dummy)) = x[n];
-                *reinterpret_cast<V4*>(f3lds + amir[n]) = x[n];
+                if constexpr (!CAUSAL) *reinterpret_cast<V4*>(f3lds + amir[n]) = x[n];
             }
 #pragma unroll
             for (int n = 0; n < F3_NH; ++n) {
                 f3lds[hao[n]] = hx[n];
-                f3lds[hmi[n]] = hx[n];
+                if constexpr (!CAUSAL) f3lds[hmi[n]] = hx[n];
             }
             }
             if (!(abl & 1)) {   // the next plane's piece, in flight across this plane's stencils
@@ -1179,17 +1192,31 @@ __global__ __launch_bounds__(512) void smooth_fused3(Fused3Args a) {
                     // smooth_tw_plane does costs NT / QA trips per item here, QA being a dozen -- that was 2/3 of the first version)
                     const int st = (int)(((float)i + 0.5f) * inv_qa), q = i - st * QA, t0 = st * LT;
                     const int c0 = t0 * pitch + 4 * q;                      // row t0 - R of the plane = row t0 of A
-                    const int last = (T + 2 * R - 1 - t0) * pitch;          // the strip may overhang the plane: rows clamped
-                    V4 r[LT + 2 * R];
+                    // the strip may overhang the plane: rows clamped (CAUSAL: to the last row of the plane, nothing lies behind it)
+                    const int last = (T + (CAUSAL ? R : 2 * R) - 1 - t0) * pitch;
+                    constexpr int NR = CAUSAL ? LT + R : LT + 2 * R;
+                    V4 r[NR];
 #pragma unroll
-                    for (int j = 0; j < LT + 2 * R; ++j) r[j] = *reinterpret_cast<const V4*>(A + c0 + min(j * pitch, last));
+                    for (int j = 0; j < NR; ++j) r[j] = *reinterpret_cast<const V4*>(A + c0 + min(j * pitch, last));
 #pragma unroll
                     for (int jo = 0; jo < LT; ++jo) {
                         V4 acc = V4{0.f, 0.f, 0.f, 0.f};
+                        if constexpr (CAUSAL) {
+#pragma unroll
+                            for (int d = 0; d <= R; ++d) {
+                                const float w = a.ct.w[d];
+                                acc = __builtin_elementwise_fma(V4{w, w, w, w}, r[jo + R - d], acc);
+                            }
+                            float iz = a.ct.iz[R];
+#pragma unroll
+                            for (int j = 0; j < R; ++j) iz = (t0 + jo == j) ? a.ct.iz[j] : iz;
+                            acc = acc * V4{iz, iz, iz, iz};
+                        } else {
 #pragma unroll
                         for (int k = -R; k <= R; ++k) {
                             const float w = a.tp.w[k + R];
                             acc = __builtin_elementwise_fma(V4{w, w, w, w}, r[jo + k + R], acc);
+                        }
                         }
                         *reinterpret_cast<V4*>(f3lds + (t0 + jo < T ? (T + 2 * R + t0 + jo) * pitch + 4 * q : dummy)) = acc;
                     }
@@ -1324,8 +1351,12 @@ static Fused3Plan fused3_plan(int B, int H, int T, int W, int C, int radius, con
     return best;
 }
 
-static int launch_fused3(const Fused3Plan& pl, Fused3Args fa, int radius, int C, hipStream_t st) {
-#define KCCOT_F3(RR, CCC, NN) hipLaunchKernelGGL((smooth_fused3<RR, CCC, NN>), dim3((unsigned)pl.grid), dim3(pl.nt), pl.lds, st, fa)
+static int launch_fused3(const Fused3Plan& pl, Fused3Args fa, int radius, int C, hipStream_t st, bool causal = false) {
+#define KCCOT_F3(RR, CCC, NN)                                                                                                   \
+    do {                                                                                                                        \
+        if (causal) hipLaunchKernelGGL((smooth_fused3<RR, CCC, NN, true>), dim3((unsigned)pl.grid), dim3(pl.nt), pl.lds, st, fa); \
+        else hipLaunchKernelGGL((smooth_fused3<RR, CCC, NN, false>), dim3((unsigned)pl.grid), dim3(pl.nt), pl.lds, st, fa);     \
+    } while (0)
 #define KCCOT_F3_N(RR, CCC)                                                                           \
     switch (pl.ni) { case 1: KCCOT_F3(RR, CCC, 1); break; case 2: KCCOT_F3(RR, CCC, 2); break;        \
                      case 3: KCCOT_F3(RR, CCC, 3); break; default: KCCOT_F3(RR, CCC, 4); break; }
@@ -1378,12 +1409,18 @@ struct Fused3AdjArgs {
     const int* run_if;     // XM: non-null -> the launch does nothing unless *run_if != 0 (the dense fallback behind the fix-up)
     int H, T, W, wt, ntw, hseg, nseg;
     Taps tp;
+    CausalTaps ct;         // CAUSAL: the one-sided T stencil (behind every other field)
 };
 
+// CAUSAL (the causal 3-D call): the last stage is the one-sided T^T, din[t'] = sum_{d=0..R} (w_d / Z_{t'+d}) y[t'+d].  The rows of
+// the W^T-smoothed piece are multiplied by 1 / Z_t of their row while they are written to LDS (the folded border columns too);
+// the stencil then reads the rows t' .. t'+R of the zero-extended buffer with the plain w_d -- there is no pad to fold back along
+// T, so the mirror pass of the border rows is gone (its register goes to the row's reciprocal).  H^T, W^T, window, prefetch, the
+// TieRec gathering and the XM form are unchanged.
 // XM: the batch-sharded caller's form (KCCOT_SMOOTH_EXTERNAL_STATS): the two sums are known (all-reduced over the ranks), so the
 // normalisation's adjoint is applied while the planes are loaded, x = gout / max - corr [out == 1] -- for the halo columns too --
 // and nothing is gathered.
-template <int R, int CC, int NI, bool XM>
+template <int R, int CC, int NI, bool XM, bool CAUSAL>
 __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
     typedef WalkVec<4>::type V4;
     extern __shared__ __attribute__((aligned(16))) float f3lds[];
@@ -1421,6 +1458,7 @@ __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
     int goff[NI], ard[NI], brd[NI], bmir[NI];     // ard / brd: the item's position in A / Bz (writes of items a thread does not
                                                   // own are redirected to the dummy slot where they happen)
     bool ok[NI];
+    float izn[NI];                                // CAUSAL: 1 / Z_t of the item's row
 #pragma unroll
     for (int n = 0; n < NI; ++n) {
         int i = tid + NT * n;
@@ -1430,8 +1468,15 @@ __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
         goff[n] = (t * WC + w0 * C + 4 * q) * 4;          // bytes within a plane of the sample
         ard[n] = t * pitch + HP + 4 * q;
         brd[n] = (t + 2 * R) * wtc + 4 * q;
-        const int mt = (t >= 1 && t <= R) ? -t : ((t >= T - 1 - R && t <= T - 2) ? 2 * (T - 1) - t : -4 * R);
-        bmir[n] = (ok[n] && mt > -4 * R) ? (mt + 2 * R) * wtc + 4 * q : -1;
+        if constexpr (CAUSAL) {
+            float iz = a.ct.iz[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) iz = (t == j) ? a.ct.iz[j] : iz;
+            izn[n] = iz;
+        } else {
+            const int mt = (t >= 1 && t <= R) ? -t : ((t >= T - 1 - R && t <= T - 2) ? 2 * (T - 1) - t : -4 * R);
+            bmir[n] = (ok[n] && mt > -4 * R) ? (mt + 2 * R) * wtc + 4 * q : -1;
+        }
     }
     int hgo[NH], hao[NH];
     float hz[NH];
@@ -1557,7 +1602,7 @@ __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
                 float acc = 0.f;
 #pragma unroll
                 for (int k = -R; k <= R; ++k) acc = fmaf(a.tp.w[k + R], v[HP + j + k * C], acc);
-                r[j] = acc;
+                r[j] = CAUSAL ? acc * izn[n] : acc;
             }
             *reinterpret_cast<V4*>(f3lds + (ok[n] ? T * pitch + brd[n] : dummy)) = V4{r[0], r[1], r[2], r[3]};
         }
@@ -1573,6 +1618,12 @@ __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
                 for (int k = j; k <= R; ++k)        // y[-j] = sum_{k >= j} w[k] x[k-j];  right: the mirror image
                     sum = fmaf(a.tp.w[k + R], right ? row[(a.wt - 1 - (k - j)) * C] : row[(k - j) * C], sum);
                 float* dst = Bz + (t + 2 * R) * wtc + (right ? a.wt - 1 - j : j) * C + c;
+                if constexpr (CAUSAL) {
+                    float iz = a.ct.iz[R];
+#pragma unroll
+                    for (int jz = 0; jz < R; ++jz) iz = (t == jz) ? a.ct.iz[jz] : iz;
+                    sum *= iz;
+                }
                 *dst += sum;
             }
             lds_barrier();
@@ -1581,12 +1632,20 @@ __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
 #pragma unroll
         for (int n = 0; n < NI; ++n) {
             V4 acc = V4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (CAUSAL) {     // rows t' + R .. t' (the order of smooth_causal's adjoint walk); rows behind T - 1 are zero
+#pragma unroll
+                for (int d = R; d >= 0; --d) {
+                    const float w = a.ct.w[d];
+                    acc = __builtin_elementwise_fma(V4{w, w, w, w}, *reinterpret_cast<const V4*>(Bz + brd[n] + d * wtc), acc);
+                }
+            } else {
 #pragma unroll
             for (int k = -R; k <= R; ++k) {
                 const float w = a.tp.w[k + R];
                 acc = __builtin_elementwise_fma(V4{w, w, w, w}, *reinterpret_cast<const V4*>(Bz + brd[n] + k * wtc), acc);
             }
-            if (bmir[n] >= 0) {
+            }
+            if (!CAUSAL && bmir[n] >= 0) {
                 V4 acc2 = V4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int k = -R; k <= R; ++k) {
@@ -1607,8 +1666,12 @@ __global__ __launch_bounds__(512) void smooth_fused3_adj(Fused3AdjArgs a) {
     if (!XM) note.store(a.ties + blockIdx.x, sdot);
 }
 
-static int launch_fused3_adj(const Fused3Plan& pl, Fused3AdjArgs fa, int C, bool xm, hipStream_t st) {
-#define KCCOT_F3A(CCC, NN, XX) hipLaunchKernelGGL((smooth_fused3_adj<3, CCC, NN, XX>), dim3((unsigned)pl.grid), dim3(pl.nt), pl.lds, st, fa)
+static int launch_fused3_adj(const Fused3Plan& pl, Fused3AdjArgs fa, int C, bool xm, hipStream_t st, bool causal = false) {
+#define KCCOT_F3A(CCC, NN, XX)                                                                                                       \
+    do {                                                                                                                             \
+        if (causal) hipLaunchKernelGGL((smooth_fused3_adj<3, CCC, NN, XX, true>), dim3((unsigned)pl.grid), dim3(pl.nt), pl.lds, st, fa); \
+        else hipLaunchKernelGGL((smooth_fused3_adj<3, CCC, NN, XX, false>), dim3((unsigned)pl.grid), dim3(pl.nt), pl.lds, st, fa);   \
+    } while (0)
 #define KCCOT_F3A_N(CCC, XX) switch (pl.ni) { case 1: KCCOT_F3A(CCC, 1, XX); break; case 2: KCCOT_F3A(CCC, 2, XX); break; default: KCCOT_F3A(CCC, 3, XX); break; }
     if (xm) { if (C == 1) { KCCOT_F3A_N(1, true) } else { KCCOT_F3A_N(3, true) } }
     else { if (C == 1) { KCCOT_F3A_N(1, false) } else { KCCOT_F3A_N(3, false) } }
@@ -1791,7 +1854,8 @@ struct FixupArgs {
     const float* mx; float* res; int* dense; float* din;
     int len[3]; long long stride[3]; int na;   // the smoothed axes
     Taps tp;
-    int causal; CausalTaps ct;                 // KCCOT_SMOOTH_CAUSAL_T: the one-sided T stencil (na = 1) instead of tp
+    int causal; CausalTaps ct;                 // one-sided T stencil on axis 0 (KCCOT_SMOOTH_CAUSAL_T: na = 1; the causal 3-D
+                                               // call: na = 3, axes 1 and 2 symmetric with tp) instead of tp
 };
 
 __global__ __launch_bounds__(1024) void maxnorm_bwd_fixup(FixupArgs a) {
@@ -1838,9 +1902,34 @@ __global__ __launch_bounds__(1024) void maxnorm_bwd_fixup(FixupArgs a) {
     for (int x = 0; x < a.na; ++x) combos *= nt;
     for (int t = 0; t < c; ++t) {
         const long long e = list[t];
-        if (a.causal) {     // S^T [out == 1]: frame p0 reaches the frames p0 - d, d = 0..min(r, p0), with w[d] / Z_p0
-            const int p0 = (int)((e / a.stride[0]) % a.len[0]), d = threadIdx.x;
-            if (d <= a.ct.r && d <= p0) a.din[e - (long long)d * a.stride[0]] -= corr * (a.ct.w[d] * a.ct.iz[min(p0, a.ct.r)]);
+        if (a.causal) {     // S^T [out == 1]: frame p0 reaches the frames p0 - d, d = 0..min(r, p0), with w[d] / Z_p0; the other
+                            // axes (causal 3-D call) carry the border-folded symmetric weights, merged as below
+            const int nd = a.ct.r + 1;
+            int sym = 1;
+            for (int x = 1; x < a.na; ++x) sym *= 2 * a.ct.r + 1;
+            const int p0t = (int)((e / a.stride[0]) % a.len[0]);
+            for (int q = threadIdx.x; q < nd * sym; q += 1024) {
+                const int d = q % nd;
+                int rem = q / nd;
+                long long target = e - (long long)d * a.stride[0];
+                float w = a.ct.w[d] * a.ct.iz[min(p0t, a.ct.r)];
+                bool owner = d <= p0t;
+                for (int x = 1; x < a.na; ++x) {
+                    const int nt2 = 2 * a.ct.r + 1, k = rem % nt2;
+                    rem /= nt2;
+                    const int p0 = (int)((e / a.stride[x]) % a.len[x]);
+                    const int pos = reflect(p0 + k - a.ct.r, a.len[x]);
+                    float wx = 0.f;
+                    for (int k2 = 0; k2 < nt2; ++k2)
+                        if (reflect(p0 + k2 - a.ct.r, a.len[x]) == pos) {
+                            if (k2 < k) owner = false;
+                            wx += a.tp.w[k2];
+                        }
+                    w *= wx;
+                    target += (long long)(pos - p0) * a.stride[x];
+                }
+                if (owner) a.din[target] -= corr * w;
+            }
             __syncthreads();
             continue;
         }
@@ -1975,11 +2064,13 @@ struct CausalArgs {
 template <int R, int VW, int MODE>
 __global__ __launch_bounds__(256) void smooth_causal(CausalArgs a) {
     typedef typename WalkVec<VW>::type V;
-    constexpr bool ADJ = MODE == WALK_ADJX || MODE == WALK_ADJS, FIXED = R != SM_MAXR;
-    constexpr int U = (ADJ && VW == 4) ? 4 : 8;     // frames in flight (the adjoint loads two tensors)
+    // WALK_ADJ: the plain adjoint, y = g / Z_t with no maximum and no correction (the last stage of the causal 3-D backward)
+    constexpr bool ADJ = MODE == WALK_ADJX || MODE == WALK_ADJS || MODE == WALK_ADJ, FIXED = R != SM_MAXR;
+    constexpr bool TWO = MODE == WALK_ADJX || MODE == WALK_ADJS;     // reads the forward output next to the gradient
+    constexpr int U = (TWO && VW == 4) ? 4 : 8;     // frames in flight (the adjoint loads two tensors)
     __shared__ float red[16];
     __shared__ TieNote note;
-    if (MODE == WALK_ADJX && a.run_if && *a.run_if == 0) return;
+    if ((MODE == WALK_ADJX || MODE == WALK_ADJ) && a.run_if && *a.run_if == 0) return;
     const int T = a.T, r = FIXED ? R : a.ct.r;
     const int64_t S = a.S;
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1987,7 +2078,7 @@ __global__ __launch_bounds__(256) void smooth_causal(CausalArgs a) {
     const int64_t g = ok ? gid : 0;
     const int64_t off = (g / a.inner) * T * S + (g % a.inner) * VW;
     float m = 1.f, corr = 0.f;
-    if ((MODE == WALK_WRITE && a.nblk <= 0) || ADJ) m = a.mx[0];
+    if ((MODE == WALK_WRITE && a.nblk <= 0) || TWO) m = a.mx[0];
     if (MODE == WALK_ADJX) corr = a.res[1] > 0.f ? a.res[0] / (m * a.res[1]) : 0.f;
     double sdot = 0.0;                  // WALK_ADJS
     if (MODE == WALK_ADJS) note.clear();
@@ -1999,11 +2090,11 @@ __global__ __launch_bounds__(256) void smooth_causal(CausalArgs a) {
 #pragma unroll
     for (int c = 0; c < VW; ++c) vat<VW>(zero, c) = 0.f;
     const int NQ = ADJ ? T + r : T;     // steps of the walk
-    V nxt[U], nxo[ADJ ? U : 1];
+    V nxt[U], nxo[TWO ? U : 1];
     auto fetch = [&](int j, int q) {    // frame q into slot j (addresses clamped, never predicated)
         const int64_t o = off + (int64_t)(q < T ? q : T - 1) * S;
         nxt[j] = *reinterpret_cast<const V*>(a.in + o);
-        if (ADJ) nxo[j] = *reinterpret_cast<const V*>(a.out_fwd + o);
+        if (TWO) nxo[j] = *reinterpret_cast<const V*>(a.out_fwd + o);
     };
 #pragma unroll
     for (int j = 0; j < U; ++j) fetch(j, j);
@@ -2018,9 +2109,9 @@ __global__ __launch_bounds__(256) void smooth_causal(CausalArgs a) {
     for (int j = 0; j < R; ++j) win[j] = zero;
     float vmax = -FLT_MAX;
     for (int q0 = 0; q0 < NQ; q0 += U) {
-        V cur[U], curo[ADJ ? U : 1];
+        V cur[U], curo[TWO ? U : 1];
 #pragma unroll
-        for (int j = 0; j < U; ++j) { cur[j] = nxt[j]; if (ADJ) curo[j] = nxo[j]; }
+        for (int j = 0; j < U; ++j) { cur[j] = nxt[j]; if (TWO) curo[j] = nxo[j]; }
 #pragma unroll
         for (int j = 0; j < U; ++j) fetch(j, q0 + U + j);
 #pragma unroll
@@ -2033,12 +2124,12 @@ __global__ __launch_bounds__(256) void smooth_causal(CausalArgs a) {
                 const bool inside = q < T;
 #pragma unroll
                 for (int c = 0; c < VW; ++c) {
-                    const float gg = vat<VW>(v, c), oo = vat<VW>(curo[j], c);
+                    const float gg = vat<VW>(v, c), oo = TWO ? vat<VW>(curo[TWO ? j : 0], c) : 0.f;
                     if (MODE == WALK_ADJS && ok && inside) {
                         sdot = fma((double)gg, (double)oo, sdot);
                         if (oo == 1.0f) note.add((long long)(off + (int64_t)q * S + c));
                     }
-                    const float xg = MODE == WALK_ADJX ? gg / m - (oo == 1.0f ? corr : 0.f) : gg / m;
+                    const float xg = MODE == WALK_ADJX ? gg / m - (oo == 1.0f ? corr : 0.f) : (MODE == WALK_ADJ ? gg : gg / m);
                     vat<VW>(v, c) = inside ? xg * iz : 0.f;
                 }
             }
@@ -2113,6 +2204,7 @@ static int launch_causal(int mode, CausalArgs ca, int radius, int64_t numel, int
         case WALK_RAW: launch_causal_m<WALK_RAW>(ca, radius, vw, st); break;
         case WALK_ADJX: launch_causal_m<WALK_ADJX>(ca, radius, vw, st); break;
         case WALK_ADJS: launch_causal_m<WALK_ADJS>(ca, radius, vw, st); break;
+        case WALK_ADJ: launch_causal_m<WALK_ADJ>(ca, radius, vw, st); break;
         default: return fail(KCCOT_EINVAL, "smooth: mode %d has no causal form", mode);
     }
     return launch_status("smooth_causal");
@@ -2574,4 +2666,272 @@ extern "C" int kccot_smooth_bwd_sharded_f32(const float* gout, const float* out,
     if (!(flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS)))
         return fail(KCCOT_EINVAL, "smooth_bwd_sharded: give KCCOT_SMOOTH_STATS_ONLY or KCCOT_SMOOTH_EXTERNAL_STATS");
     return smooth_bwd_impl(gout, out, max_in, stats_inout, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
+}
+
+// ---- the causal 3-D smoothing (include/kccot_smooth_causal3.h; NOT reference behaviour) ----------------------------------------
+//     a = causal T stencil of KCCOT_SMOOTH_CAUSAL_T;  s = H(W(a)) with the symmetric REFLECT stencils;  out = s / max(s)
+// Stage order T, W, H as in the symmetric 3-D call.  Two tiers, dispatched as there: the fused walks (smooth_fused3 /
+// smooth_fused3_adj with CAUSAL) where fused3_plan finds a tiling, else the chain -- smooth_causal in raw mode, the W stage the
+// symmetric chain would pick, the H walk as the last stage (maxima, then s / max), and for every other radius / shape the
+// per-element conv_axis stages around the same smooth_causal.  Backward: the normalisation's adjoint (two-pass or folded), H^T,
+// W^T, then the plain causal T^T (smooth_causal WALK_ADJ) as the last stage.
+static const unsigned SMOOTH3C_PROTOCOL = KCCOT_SMOOTH_NO_DIVIDE | KCCOT_SMOOTH_EXTERNAL_MAX | KCCOT_SMOOTH_STATS_ONLY |
+                                          KCCOT_SMOOTH_EXTERNAL_STATS;
+
+static int smooth3c_check(const char* who, const void* a, const void* b, int B, int H, int T, int W, int C, float sigma,
+                          int radius, unsigned flags) {
+    if (flags & ~SMOOTH3C_PROTOCOL)
+        return fail(KCCOT_EINVAL, "%s: flags 0x%x: the axes are fixed (causal T, symmetric H and W); only NO_DIVIDE, EXTERNAL_MAX, "
+                    "STATS_ONLY and EXTERNAL_STATS are accepted", who, flags);
+    if (!a || !b) return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0)
+        return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", who, B, H, T, W, C);
+    if (!(sigma > 0.f)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", who);
+    if (radius < 0 || radius > SM_MAXR) return fail(KCCOT_EUNSUPPORTED, "%s: radius %d > %d", who, radius, SM_MAXR);
+    // REFLECT padding along H and W needs pad < dim; T has no padding: any radius, radius >= T included
+    if (radius >= H || radius >= W) return fail(KCCOT_EINVAL, "%s: REFLECT padding needs radius < H and radius < W", who);
+    return 0;
+}
+
+// the W stage of the chain: the kernel the symmetric chain would pick, or 0 = none (the per-element stages serve)
+enum { W3C_NONE = 0, W3C_W1 = 1, W3C_PLANE = 2, W3C_ROW = 3 };
+static int smooth3c_wstage(int T, int W, int C, int radius, const void* a, const void* b) {
+    if (w1_eligible(W, C, radius, a, b) && !smooth_generic()) return W3C_W1;
+    if (plane_eligible(T, W, C, radius, 1) && !smooth_generic()) return W3C_PLANE;
+    if (wrow_eligible(W, C, radius)) return W3C_ROW;
+    return W3C_NONE;
+}
+
+static int smooth3c_launch_w(int kind, const float* in, float* out, const float* out_fwd, float* one, int64_t n, int B, int H, int T,
+                             int W, int C, int radius, bool adjoint, const Taps& tp, hipStream_t st) {
+    if (kind == W3C_W1) return launch_w1(in, out, n, W, radius, adjoint, tp, st);
+    if (kind == W3C_ROW) return launch_wrow(in, out, n, W, C, radius, adjoint, tp, st);
+    int rc;
+    hipLaunchKernelGGL(set_unit_scalars, dim3(1), dim3(1), 0, st, one);
+    if ((rc = launch_status("set_unit_scalars"))) return rc;
+    PlaneArgs pa{};
+    pa.in = in; pa.out_fwd = out_fwd; pa.out = out; pa.mx = one; pa.res = one + 1;     // max = 1, no ties: the plain stencil
+    pa.B = B; pa.H = H; pa.T = T; pa.W = W; pa.C = C; pa.axes = KCCOT_SMOOTH_W; pa.tp = tp; pa.hseg = plane_hseg(B, H, false);
+    return launch_plane(pa, radius, adjoint, dim3((H + pa.hseg - 1) / pa.hseg, B), st);
+}
+
+extern "C" int kccot_smooth_causal3_fwd_f32(const float* in, int B, int H, int T, int W, int C, float sigma, int radius,
+                                            unsigned flags, float* out, float* max_inout, void* ws, size_t ws_bytes,
+                                            kccot_stream_t stream) {
+    const char* who = "kccot_smooth_causal3_fwd_f32";
+    int rc = smooth3c_check(who, in, out, B, H, T, W, C, sigma, radius, flags);
+    if (rc) return rc;
+    if (!max_inout) return fail(KCCOT_EINVAL, "%s: null max pointer", who);
+    const bool ext = (flags & KCCOT_SMOOTH_EXTERNAL_MAX) != 0, nodiv = (flags & KCCOT_SMOOTH_NO_DIVIDE) != 0;
+    if (ext && nodiv) return fail(KCCOT_EINVAL, "%s: EXTERNAL_MAX and NO_DIVIDE are exclusive", who);
+    if (in == out) return fail(KCCOT_EINVAL, "%s: in-place convolution is not supported", who);
+    const size_t need = kccot_smooth_workspace_bytes(B, H, T, W, C);
+    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", who, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)B * H * T * W * C, WC = (int64_t)W * C;
+    const int64_t nb = (n + 255) / 256;
+    if (nb > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", who);
+    float* tmp = static_cast<float*>(ws);
+    float* bmax = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256));
+    float* one = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256) + 2 * smooth_blk_bytes(n));
+    const Taps tp = make_taps(sigma, radius);
+    const CausalTaps ct = make_causal_taps(sigma, radius);
+    const bool r34 = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM);
+    // (NO_DIVIDE and EXTERNAL_MAX take the same tier and the same kernels as the one-call form: see kccot_smooth_fwd_f32)
+    if (r34) {
+        const Fused3Plan fp = fused3_plan(B, H, T, W, C, radius, in, out);
+        if (fp.ok) {
+            Fused3Args fa{};
+            fa.in = in; fa.H = H; fa.T = T; fa.W = W; fa.wt = fp.wt; fa.ntw = W / fp.wt; fa.hseg = fp.hseg;
+            fa.nseg = (H + fp.hseg - 1) / fp.hseg; fa.tp = tp; fa.ct = ct;
+            if (!ext) {
+                fa.mode = 0; fa.blockmax = bmax;
+                if ((rc = launch_fused3(fp, fa, radius, C, st, true))) return rc;
+                if (!nodiv && fp.grid <= 4096) {
+                    fa.nblk = (int)fp.grid;       // the writing pass reduces the maxima itself (and stores the maximum)
+                } else {
+                    hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, fp.grid, max_inout);
+                    if ((rc = launch_status("reduce_blockmax"))) return rc;
+                }
+            }
+            fa.mode = nodiv ? 2 : 1; fa.out = out; fa.mx = max_inout; fa.mx_out = max_inout;
+            return launch_fused3(fp, fa, radius, C, st, true);
+        }
+    }
+    // T: in -> out (raw sums times 1 / Z_t)
+    CausalArgs ca{};
+    ca.ct = ct; ca.in = in; ca.out = out; ca.T = T; ca.S = WC;
+    if ((rc = launch_causal(WALK_RAW, ca, radius, n, causal_vw(WC, in, out, out), st))) return rc;
+    const AxisPlan ph = r34 ? axis_plan(H, (int64_t)T * WC, false, false, radius, tmp, out, out) : AxisPlan{AXIS_NONE, WalkPlan{0, 0}, 0};
+    const int wk = r34 ? smooth3c_wstage(T, W, C, radius, out, tmp) : W3C_NONE;
+    if (ph.kind != AXIS_NONE && wk != W3C_NONE) {
+        // W: out -> tmp (raw);  H: tmp -> maxima, then tmp -> out (s / max, or s)
+        if ((rc = smooth3c_launch_w(wk, out, tmp, nullptr, one, n, B, H, T, W, C, radius, false, tp, st))) return rc;
+        WalkArgs wa{};
+        wa.tp = tp; wa.in = tmp; wa.L = H; wa.S = (int64_t)T * WC;
+        const int64_t last_wgs = (n / H / ph.vw + 255) / 256;
+        if (!ext) {
+            wa.blockmax = bmax;
+            if ((rc = launch_axis(WALK_MAX, wa, radius, n, ph, st))) return rc;
+            if (!nodiv && last_wgs <= 4096) {
+                wa.nblk = (int)last_wgs;
+            } else {
+                hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, last_wgs, max_inout);
+                if ((rc = launch_status("reduce_blockmax"))) return rc;
+            }
+        }
+        wa.out = out; wa.mx = max_inout; wa.mx_out = max_inout;
+        if (wa.nblk == 0) wa.blockmax = nullptr;
+        return launch_axis(nodiv ? WALK_RAW : WALK_WRITE, wa, radius, n, ph, st);
+    }
+    // any radius, any shape: W out -> tmp, H tmp -> out per element, the maximum, the division in place
+    hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)out, tmp, n, W, (int64_t)C, tp, 0, (float*)nullptr);
+    if ((rc = launch_status("conv_axis"))) return rc;
+    hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)tmp, out, n, H, (int64_t)T * WC, tp, 0,
+                       ext ? (float*)nullptr : bmax);
+    if ((rc = launch_status("conv_axis"))) return rc;
+    if (!ext) {
+        hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, nb, max_inout);
+        if ((rc = launch_status("reduce_blockmax"))) return rc;
+    }
+    if (!nodiv) {
+        hipLaunchKernelGGL(divide_by, dim3((unsigned)nb), dim3(256), 0, st, (const float*)out, out, n, (const float*)max_inout);
+        if ((rc = launch_status("divide_by"))) return rc;
+    }
+    return 0;
+}
+
+static int smooth3c_bwd_impl(const char* who, const float* gout, const float* out, const float* max_in, float* stats_ext, int B,
+                             int H, int T, int W, int C, float sigma, int radius, unsigned flags, float* din, void* ws,
+                             size_t ws_bytes, kccot_stream_t stream) {
+    const bool stats_only = (flags & KCCOT_SMOOTH_STATS_ONLY) != 0, stats_in = (flags & KCCOT_SMOOTH_EXTERNAL_STATS) != 0;
+    int rc = smooth3c_check(who, gout, stats_only ? const_cast<float*>(gout) : din, B, H, T, W, C, sigma, radius, flags);
+    if (rc) return rc;
+    if (stats_only && stats_in) return fail(KCCOT_EINVAL, "%s: STATS_ONLY and EXTERNAL_STATS are exclusive", who);
+    if ((stats_only || stats_in) && !stats_ext) return fail(KCCOT_EINVAL, "%s: null stats pointer", who);
+    if (!out || !max_in) return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    const size_t need = kccot_smooth_workspace_bytes(B, H, T, W, C);
+    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", who, ws_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)B * H * T * W * C, WC = (int64_t)W * C;
+    const int64_t nb = (n + 255) / 256;
+    if (nb > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", who);
+    float* tmp = static_cast<float*>(ws);
+    char* p = static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256);
+    float* pdot = reinterpret_cast<float*>(p);
+    float* pcnt = reinterpret_cast<float*>(p + smooth_blk_bytes(n));
+    float* res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n));
+    float* scal = res;                                      // workspace scalars {dot, ties, .., .., 1, 0, 0, dense}
+    TieRec* recs = reinterpret_cast<TieRec*>(p + 2 * smooth_blk_bytes(n) + 256);
+    const Taps tp = make_taps(sigma, radius);
+    const CausalTaps ct = make_causal_taps(sigma, radius);
+    const bool wide = (n % 4 == 0) && ((uintptr_t)gout % 16 == 0) && ((uintptr_t)out % 16 == 0) && nb >= 2048;
+    const int64_t nparts = wide ? 2048 : nb;
+    const bool r34 = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM);
+    // the streaming chain: H^T (+ the normalisation's adjoint) gout -> din, W^T din -> tmp, causal T^T tmp -> din
+    AxisPlan ph{AXIS_NONE, WalkPlan{0, 0}, 0};
+    int wk = W3C_NONE;
+    if (r34 && !stats_only) {
+        ph = axis_plan(H, (int64_t)T * WC, true, true, radius, gout, out, din);
+        wk = smooth3c_wstage(T, W, C, radius, din, tmp);
+    }
+    const bool chain = ph.kind != AXIS_NONE && wk != W3C_NONE;
+    const int vwt = causal_vw(WC, tmp, din, din);
+    const int fold_opt = opt(OPT_SMOOTH_BWD_FOLD);
+    Fused3Plan fpa{};
+    if (chain && (stats_in || fold_opt != 0) && ((uintptr_t)out & 15) == 0) fpa = fused3_plan(B, H, T, W, C, radius, gout, din, true, !stats_in);
+    // one TieRec per workgroup of the stage that reads gout: where the H walk's grid would not fit the records of the workspace
+    // the two-pass form runs whatever the option says (fused3_plan never returns a tiling that does not fit)
+    int nrec = chain ? (int)((n / H / ph.vw + 255) / 256) : 0;
+    const bool fold = chain && !stats_in && (fold_opt == 2 || fpa.ok || (fold_opt == 1 && n >= ((int64_t)1 << 25))) &&
+                      (fpa.ok || nrec <= tie_rec_capacity(n));
+    if (fold) {     // no per-block partial sums: the records start at the per-block arrays, the scalars sit behind the records
+        recs = reinterpret_cast<TieRec*>(p);
+        scal = res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n) + smooth_rec_bytes(n));
+    }
+    Fused3AdjArgs fx{};
+    if (fpa.ok) {
+        fx.gout = gout; fx.out_fwd = out; fx.din = din; fx.mx = max_in; fx.H = H; fx.T = T; fx.W = W; fx.wt = fpa.wt;
+        fx.ntw = W / fpa.wt; fx.hseg = fpa.hseg; fx.nseg = (H + fpa.hseg - 1) / fpa.hseg; fx.tp = tp; fx.ct = ct;
+    }
+    if (stats_in && fpa.ok) {       // the batch-sharded caller: sums handed in, correction applied at the loads, nothing to fix up
+        fx.res = stats_ext;
+        return launch_fused3_adj(fpa, fx, C, true, st, true);
+    }
+    if (stats_in) {
+        res = stats_ext;
+    } else if (!fold) {
+        if (stats_only) res = stats_ext;
+        if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, pdot, pcnt);
+        else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, pdot, pcnt);
+        if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
+        hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)pdot, (const float*)pcnt, nparts, res);
+        if ((rc = launch_status("maxnorm_bwd_combine"))) return rc;
+        if (stats_only) return 0;
+    }
+    CausalArgs ca{};
+    ca.ct = ct; ca.in = tmp; ca.out = din; ca.T = T; ca.S = WC;
+    if (!chain) {
+        // any radius, any shape: the normalisation's adjoint gout -> tmp, H^T tmp -> din, W^T din -> tmp per element, causal T^T
+        hipLaunchKernelGGL(maxnorm_bwd_apply, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, max_in, (const float*)res, tmp);
+        if ((rc = launch_status("maxnorm_bwd_apply"))) return rc;
+        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)tmp, din, n, H, (int64_t)T * WC, tp, 1, (float*)nullptr);
+        if ((rc = launch_status("conv_axis(adjoint)"))) return rc;
+        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)din, tmp, n, W, (int64_t)C, tp, 1, (float*)nullptr);
+        if ((rc = launch_status("conv_axis(adjoint)"))) return rc;
+        return launch_causal(WALK_ADJ, ca, radius, n, vwt, st);
+    }
+    if (fold && fpa.ok) {           // all three adjoint stages in one pass, the statistics gathered on the way
+        fx.ties = recs;
+        if ((rc = launch_fused3_adj(fpa, fx, C, false, st, true))) return rc;
+        nrec = (int)fpa.grid;
+    } else {
+        WalkArgs wa{};
+        wa.tp = tp; wa.out_fwd = out; wa.mx = max_in; wa.res = res; wa.ties = recs;
+        wa.in = gout; wa.out = din; wa.L = H; wa.S = (int64_t)T * WC;
+        if ((rc = launch_axis(fold ? WALK_ADJS : WALK_ADJX, wa, radius, n, ph, st))) return rc;
+        if ((rc = smooth3c_launch_w(wk, din, tmp, out, scal + 4, n, B, H, T, W, C, radius, true, tp, st))) return rc;
+        if ((rc = launch_causal(WALK_ADJ, ca, radius, n, vwt, st))) return rc;
+    }
+    if (!fold) return 0;
+    // behind the folded first stage: the sparse fix-up, then the dense form that only runs when it found too many arg-max elements
+    int* dense = reinterpret_cast<int*>(scal + 7);
+    FixupArgs fa{};
+    fa.ties = recs; fa.nrec = nrec; fa.mx = max_in; fa.res = res; fa.dense = dense; fa.din = din; fa.na = 3; fa.tp = tp;
+    fa.len[0] = T; fa.stride[0] = WC; fa.len[1] = H; fa.stride[1] = (int64_t)T * WC; fa.len[2] = W; fa.stride[2] = C;
+    fa.causal = 1; fa.ct = ct;
+    hipLaunchKernelGGL(maxnorm_bwd_fixup, dim3(1), dim3(1024), 0, st, fa);
+    if ((rc = launch_status("maxnorm_bwd_fixup"))) return rc;
+    if (fpa.ok) {
+        fx.ties = nullptr; fx.res = res; fx.run_if = dense;
+        return launch_fused3_adj(fpa, fx, C, true, st, true);
+    }
+    WalkArgs wd{};
+    wd.tp = tp; wd.out_fwd = out; wd.mx = max_in; wd.res = res; wd.run_if = dense;
+    wd.in = gout; wd.out = din; wd.L = H; wd.S = (int64_t)T * WC;
+    if ((rc = launch_axis(WALK_ADJX, wd, radius, n, ph, st))) return rc;
+    hipLaunchKernelGGL(conv_axis_adjoint_if, dim3((unsigned)std::min<int64_t>(nb, 2048)), dim3(256), 0, st, (const float*)din, tmp, n,
+                       W, (int64_t)C, tp, (const int*)dense);
+    if ((rc = launch_status("conv_axis_adjoint_if"))) return rc;
+    ca.run_if = dense;
+    return launch_causal(WALK_ADJ, ca, radius, n, vwt, st);
+}
+
+extern "C" int kccot_smooth_causal3_bwd_f32(const float* gout, const float* out, const float* max_in, int B, int H, int T,
+                                            int W, int C, float sigma, int radius, unsigned flags, float* din, void* ws,
+                                            size_t ws_bytes, kccot_stream_t stream) {
+    const char* who = "kccot_smooth_causal3_bwd_f32";
+    if ((flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS)) && !(flags & ~SMOOTH3C_PROTOCOL))
+        return fail(KCCOT_EINVAL, "%s: the stats flags belong to kccot_smooth_causal3_bwd_sharded_f32", who);
+    return smooth3c_bwd_impl(who, gout, out, max_in, nullptr, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
+}
+
+extern "C" int kccot_smooth_causal3_bwd_sharded_f32(const float* gout, const float* out, const float* max_in,
+                                                    float* stats_inout, int B, int H, int T, int W, int C, float sigma,
+                                                    int radius, unsigned flags, float* din, void* ws, size_t ws_bytes,
+                                                    kccot_stream_t stream) {
+    const char* who = "kccot_smooth_causal3_bwd_sharded_f32";
+    if (!(flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS)) && !(flags & ~SMOOTH3C_PROTOCOL))
+        return fail(KCCOT_EINVAL, "%s: give KCCOT_SMOOTH_STATS_ONLY or KCCOT_SMOOTH_EXTERNAL_STATS", who);
+    return smooth3c_bwd_impl(who, gout, out, max_in, stats_inout, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
 }

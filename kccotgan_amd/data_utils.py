@@ -12,6 +12,16 @@ from ._lib import lib, check, ptr, stream_of, workspace
 __all__ = ["KernelSmoothing"]
 
 
+CAUSAL3 = "causal3"     # `axes` of the causal 3-D smoothing: its own entry points (include/kccot_smooth_causal3.h), protocol flags only
+
+
+def _entry(axes):
+    """(forward, backward, sharded backward, axis flags) for an `axes` value."""
+    if axes == CAUSAL3:
+        return lib.kccot_smooth_causal3_fwd_f32, lib.kccot_smooth_causal3_bwd_f32, lib.kccot_smooth_causal3_bwd_sharded_f32, 0
+    return lib.kccot_smooth_fwd_f32, lib.kccot_smooth_bwd_f32, lib.kccot_smooth_bwd_sharded_f32, axes
+
+
 class _Smooth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sigma, radius, axes):
@@ -19,8 +29,8 @@ class _Smooth(torch.autograd.Function):
         out = _lib.empty_like(x)
         mx = _lib.empty((1,), torch.float32, x.device)
         ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), x)
-        check(lib.kccot_smooth_fwd_f32(ptr(x), B, H, T, W, C, sigma, radius, axes, ptr(out), ptr(mx), ws, wsb,
-                                       stream_of(x)), "smooth_fwd")
+        fwd, _, _, bits = _entry(axes)
+        check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits, ptr(out), ptr(mx), ws, wsb, stream_of(x)), "smooth_fwd")
         ctx.save_for_backward(out, mx)
         ctx.cfg = (sigma, radius, axes)
         return out
@@ -33,8 +43,9 @@ class _Smooth(torch.autograd.Function):
         g = g.contiguous()
         din = _lib.empty_like(out)
         ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), out)
-        check(lib.kccot_smooth_bwd_f32(ptr(g), ptr(out), ptr(mx), B, H, T, W, C, sigma, radius, axes, ptr(din),
-                                       ws, wsb, stream_of(out)), "smooth_bwd")
+        _, bwd, _, bits = _entry(axes)
+        check(bwd(ptr(g), ptr(out), ptr(mx), B, H, T, W, C, sigma, radius, bits, ptr(din), ws, wsb, stream_of(out)),
+              "smooth_bwd")
         return din, None, None, None
 
 
@@ -52,11 +63,12 @@ class _SmoothSharded(torch.autograd.Function):
         out = _lib.empty_like(x)
         mx = _lib.empty((1,), torch.float32, x.device)
         ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), x)
-        check(lib.kccot_smooth_fwd_f32(ptr(x), B, H, T, W, C, sigma, radius, axes | _lib.SMOOTH_NO_DIVIDE, ptr(out), ptr(mx),
-                                       ws, wsb, stream_of(x)), "smooth_fwd")
+        fwd, _, _, bits = _entry(axes)
+        check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_NO_DIVIDE, ptr(out), ptr(mx), ws, wsb, stream_of(x)),
+              "smooth_fwd")
         _all_reduce(mx, dist.ReduceOp.MAX, group)
-        check(lib.kccot_smooth_fwd_f32(ptr(x), B, H, T, W, C, sigma, radius, axes | _lib.SMOOTH_EXTERNAL_MAX, ptr(out), ptr(mx),
-                                       ws, wsb, stream_of(x)), "smooth_fwd")
+        check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_EXTERNAL_MAX, ptr(out), ptr(mx), ws, wsb,
+                  stream_of(x)), "smooth_fwd")
         ctx.save_for_backward(out, mx)
         ctx.cfg = (sigma, radius, axes, group)
         return out
@@ -71,12 +83,12 @@ class _SmoothSharded(torch.autograd.Function):
         din = _lib.empty_like(out)
         stats = _lib.empty((2,), torch.float32, out.device)
         ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), out)
-        check(lib.kccot_smooth_bwd_sharded_f32(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius,
-                                               axes | _lib.SMOOTH_STATS_ONLY, None, ws, wsb, stream_of(out)), "smooth_bwd")
+        _, _, bwd, bits = _entry(axes)
+        check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_STATS_ONLY, None, ws,
+                  wsb, stream_of(out)), "smooth_bwd")
         _all_reduce(stats, dist.ReduceOp.SUM, group)
-        check(lib.kccot_smooth_bwd_sharded_f32(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius,
-                                               axes | _lib.SMOOTH_EXTERNAL_STATS, ptr(din), ws, wsb, stream_of(out)),
-              "smooth_bwd")
+        check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_EXTERNAL_STATS,
+                  ptr(din), ws, wsb, stream_of(out)), "smooth_bwd")
         return din, None, None, None, None
 
 
@@ -149,6 +161,14 @@ class KernelSmoothing:
         """data_utils.py:552-582: 3-D Gaussian over (T, H, W), all with the SPATIAL radius
         (data_utils.py:553,562-564), REFLECT borders, then / global max."""
         return self._apply(inputs, sigma, self.spatial_radius, _lib.SMOOTH_T | _lib.SMOOTH_H | _lib.SMOOTH_W)
+
+    def causal_gaussian_convolution3D(self, inputs, sigma):
+        """NOT reference behaviour.  gaussian_convolution3D above smooths symmetrically along T too, so frame t of its
+        output contains frames t+1 .. t+r.  This is its causal form (include/kccot_smooth_causal3.h): along T the past-only
+        stencil of causal_temporal_convolution (truncated, renormalised window, no padding, s[0] = x[0]), along W and H the
+        symmetric Gaussian with REFLECT borders, then / global max.  All three axes use the SPATIAL radius, as
+        gaussian_convolution3D does."""
+        return self._apply(inputs, sigma, self.spatial_radius, CAUSAL3)
 
     def annealing_sigma(self, init_sigma, step, decay_steps=500, decay_rate=0.975):
         """data_utils.py:584-586."""

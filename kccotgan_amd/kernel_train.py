@@ -187,6 +187,8 @@ class KCCOTTrainer:
             return self.gaussian_kernel.spatial_convolution(v, sigma)
         if self.kernel_choice == "3d":
             return self.gaussian_kernel.gaussian_convolution3D(v, sigma)
+        if self.kernel_choice == "3d_causal":                                    # not in the reference: causal along T, symmetric in space
+            return self.gaussian_kernel.causal_gaussian_convolution3D(v, sigma)
         return v
 
     def _forward_mixed(self, real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad=True):
