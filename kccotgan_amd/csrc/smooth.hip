@@ -2210,220 +2210,386 @@ static int launch_causal(int mode, CausalArgs ca, int radius, int64_t numel, int
     return launch_status("smooth_causal");
 }
 
-// Forward of KCCOT_SMOOTH_CAUSAL_T.  Two phases as the symmetric temporal call: block maxima without a store, then the same
-// kernel again writing s / max (reducing the block maxima itself when there are few), so that NO_DIVIDE and EXTERNAL_MAX
-// evaluate s with the kernel the one-call form uses and the arg-max element comes out as exactly 1.
-static int smooth_causal_fwd(const float* in, float* out, float* max_inout, float* bmax, int64_t n, int T, int64_t WC,
-                             float sigma, int radius, bool ext, bool nodiv, hipStream_t st) {
-    int rc;
-    const int vw = causal_vw(WC, in, out, out);
-    const int64_t wgs = causal_wgs(n, T, vw);
-    CausalArgs ca{};
-    ca.ct = make_causal_taps(sigma, radius);
-    ca.in = in; ca.T = T; ca.S = WC;
-    if (!ext) {
-        ca.blockmax = bmax;
-        if ((rc = launch_causal(WALK_MAX, ca, radius, n, vw, st))) return rc;
-        if (!nodiv && wgs <= 4096) {
-            ca.nblk = (int)wgs;
-        } else {
-            hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, wgs, max_inout);
-            if ((rc = launch_status("reduce_blockmax"))) return rc;
-        }
-    }
-    ca.out = out; ca.mx = max_inout; ca.mx_out = max_inout;
-    return launch_causal(nodiv ? WALK_RAW : WALK_WRITE, ca, radius, n, vw, st);
-}
-
 }  // namespace kccot
 
 using namespace kccot;
 
+// ---- host side: one driver per direction behind the seven kccot_smooth_* entry points -----------------------------------------
+
+// The workspace (layout: see smooth_blk_bytes): the tensor-sized ping-pong buffer, the two per-block arrays (forward: block
+// maxima; backward without the fold: the partial sums), 256 bytes of scalars, the record area.  Size and carving come from here
+// alone.  Scalar slots: {dot, ties, .., .., 1, 0, 0, dense}; the forward keeps its own {1, 0, 0} at slot 0.
+struct SmoothWs {
+    enum { UNIT_FWD = 0, UNIT_BWD = 4, DENSE = 7 };     // slots of `scal` (floats); {dot, ties} = scal[0], scal[1] is `res`
+    char* base;
+    size_t tensor, blk, rec, total;
+    float *tmp, *bmax, *pdot, *pcnt, *scal;             // bmax (forward) and pdot (backward) are the first per-block array
+    TieRec* recs;
+    SmoothWs(void* ws, int64_t n)
+        : base(static_cast<char*>(ws)), tensor(align_up((size_t)n * sizeof(float), 256)), blk(smooth_blk_bytes(n)),
+          rec(smooth_rec_bytes(n)), total(tensor + 2 * blk + 256 + rec) {
+        tmp = at<float>(0); bmax = pdot = at<float>(tensor); pcnt = at<float>(tensor + blk);
+        scal = at<float>(tensor + 2 * blk); recs = at<TieRec>(tensor + 2 * blk + 256);
+    }
+    template <typename P> P* at(size_t off) const { return base ? reinterpret_cast<P*>(base + off) : nullptr; }
+    // the folded backward has no per-block partial sums: the records start at the per-block arrays (tie_rec_capacity), the
+    // scalars sit behind the record area
+    void fold() { recs = at<TieRec>(tensor); scal = at<float>(tensor + 2 * blk + rec); }
+    float* unit(int slot) const { return scal + slot; }
+    int* dense() const { return reinterpret_cast<int*>(scal + DENSE); }
+};
+
 extern "C" size_t kccot_smooth_workspace_bytes(int B, int H, int T, int W, int C) {
     if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return 0;
-    const size_t n = (size_t)B * H * T * W * C;
-    // one tensor-sized ping-pong buffer + two per-block reduction arrays + scalars + the backward's per-workgroup tie
-    // records (a line kernel's workgroup covers >= 256 lines of >= 4 elements; the folded backward also lays records over
-    // the per-block arrays: tie_rec_capacity)
-    return align_up(n * sizeof(float), 256) + 2 * smooth_blk_bytes((int64_t)n) + 256 + smooth_rec_bytes((int64_t)n);
+    return SmoothWs(nullptr, (int64_t)((size_t)B * H * T * W * C)).total;
 }
 
-static int smooth_check(const char* who, const void* a, const void* b, int B, int H, int T, int W, int C, float sigma,
-                        int radius, unsigned flags) {
-    if (!a || !b) return fail(KCCOT_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0)
-        return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", who, B, H, T, W, C);
-    if (radius < 0 || radius > SM_MAXR) return fail(KCCOT_EUNSUPPORTED, "%s: radius %d > %d", who, radius, SM_MAXR);
-    if (!(sigma > 0.f)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", who);
-    if (flags & KCCOT_SMOOTH_CAUSAL_T) {    // the one-sided T stencil: T alone; no padding, so any radius up to SM_MAXR
-        if ((flags & (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W)) != KCCOT_SMOOTH_T)
-            return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_CAUSAL_T goes with KCCOT_SMOOTH_T alone (no H, no W)", who);
-        return 0;
-    }
-    // REFLECT padding needs pad < dim (tf.pad rejects it otherwise)
-    if (((flags & KCCOT_SMOOTH_T) && radius >= T) || ((flags & KCCOT_SMOOTH_H) && radius >= H) ||
-        ((flags & KCCOT_SMOOTH_W) && radius >= W))
-        return fail(KCCOT_EINVAL, "%s: REFLECT padding needs radius < axis length", who);
+static const unsigned SMOOTH_AXES = KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W;
+static const unsigned SMOOTH3C_PROTOCOL = KCCOT_SMOOTH_NO_DIVIDE | KCCOT_SMOOTH_EXTERNAL_MAX | KCCOT_SMOOTH_STATS_ONLY |
+                                          KCCOT_SMOOTH_EXTERNAL_STATS;
+
+// One call of either family.  causal3: the causal 3-D entry points (include/kccot_smooth_causal3.h; NOT reference behaviour):
+//     a = causal T stencil of KCCOT_SMOOTH_CAUSAL_T;  s = H(W(a)) with the symmetric REFLECT stencils;  out = s / max(s)
+// -- all three axes always, no axis flags.  Otherwise the flags name the axes, and KCCOT_SMOOTH_CAUSAL_T makes a lone T causal.
+struct SmoothCall {
+    const char* who;        // prefix of the entry point's messages
+    bool causal3;
+    int B, H, T, W, C;
+    float sigma;
+    int radius;
+    unsigned flags;
+    void* ws;
+    size_t ws_bytes;
+    hipStream_t st;
+    unsigned axes() const { return causal3 ? SMOOTH_AXES : flags & SMOOTH_AXES; }
+    bool tcausal() const { return causal3 || (flags & KCCOT_SMOOTH_CAUSAL_T); }
+    int64_t n() const { return (int64_t)B * H * T * W * C; }
+};
+
+// Where one call is wrong in two ways, which check comes first decides the error code, and the two families have always
+// ordered some checks differently: those orders are kept (marked below), the codes are part of the ABI.
+static int smooth_check(const SmoothCall& c, const void* a, const void* b) {
+    if (c.causal3 && (c.flags & ~SMOOTH3C_PROTOCOL))
+        return fail(KCCOT_EINVAL, "%s: flags 0x%x: the axes are fixed (causal T, symmetric H and W); only NO_DIVIDE, EXTERNAL_MAX, "
+                    "STATS_ONLY and EXTERNAL_STATS are accepted", c.who, c.flags);
+    if (!a || !b) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
+    if (c.B <= 0 || c.H <= 0 || c.T <= 0 || c.W <= 0 || c.C <= 0)
+        return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", c.who, c.B, c.H, c.T, c.W, c.C);
+    const bool bad_radius = c.radius < 0 || c.radius > SM_MAXR, bad_sigma = !(c.sigma > 0.f);
+    // (order: the flag-driven entry points report a bad radius ahead of a bad sigma, the causal-3 ones the sigma first)
+    if (bad_sigma && (c.causal3 || !bad_radius)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", c.who);
+    if (bad_radius) return fail(KCCOT_EUNSUPPORTED, "%s: radius %d > %d", c.who, c.radius, SM_MAXR);
+    const unsigned ax = c.axes();
+    if ((c.flags & KCCOT_SMOOTH_CAUSAL_T) && ax != KCCOT_SMOOTH_T)
+        return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_CAUSAL_T goes with KCCOT_SMOOTH_T alone (no H, no W)", c.who);
+    // REFLECT padding needs pad < dim (tf.pad rejects it otherwise); a causal T has no padding: any radius, radius >= T included
+    if (((ax & KCCOT_SMOOTH_T) && !c.tcausal() && c.radius >= c.T) || ((ax & KCCOT_SMOOTH_H) && c.radius >= c.H) ||
+        ((ax & KCCOT_SMOOTH_W) && c.radius >= c.W))
+        return fail(KCCOT_EINVAL, "%s: REFLECT padding needs radius < the length of every symmetric axis", c.who);
     return 0;
 }
 
-extern "C" int kccot_smooth_fwd_f32(const float* in, int B, int H, int T, int W, int C, float sigma, int radius,
-                                    unsigned flags, float* out, float* max_inout, void* ws, size_t ws_bytes,
-                                    kccot_stream_t stream) {
-    int rc = smooth_check("smooth_fwd", in, out, B, H, T, W, C, sigma, radius, flags);
+static int smooth_check_ws(const SmoothCall& c) {
+    const size_t need = kccot_smooth_workspace_bytes(c.B, c.H, c.T, c.W, c.C);
+    if (!c.ws || c.ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", c.who, c.ws_bytes, need);
+    if ((c.n() + 255) / 256 > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", c.who);
+    return 0;
+}
+
+static int smooth_fwd_prologue(const SmoothCall& c, const float* in, const float* out, const float* max_inout) {
+    int rc = smooth_check(c, in, out);
     if (rc) return rc;
-    if (!max_inout) return fail(KCCOT_EINVAL, "smooth_fwd: null max pointer");
-    const size_t need = kccot_smooth_workspace_bytes(B, H, T, W, C);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "smooth_fwd: workspace %zu < required %zu", ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = (int64_t)B * H * T * W * C;
+    if (!max_inout) return fail(KCCOT_EINVAL, "%s: null max pointer", c.who);
+    auto modes = [&]() -> int {
+        if ((c.flags & KCCOT_SMOOTH_EXTERNAL_MAX) && (c.flags & KCCOT_SMOOTH_NO_DIVIDE))
+            return fail(KCCOT_EINVAL, "%s: EXTERNAL_MAX and NO_DIVIDE are exclusive", c.who);
+        if (c.axes() && in == out) return fail(KCCOT_EINVAL, "%s: in-place convolution is not supported", c.who);
+        return 0;
+    };
+    // (order: the causal-3 entry points look at the modes ahead of the workspace, the flag-driven ones behind it)
+    if (c.causal3 && (rc = modes())) return rc;
+    if ((rc = smooth_check_ws(c))) return rc;
+    return c.causal3 ? 0 : modes();
+}
+
+static int smooth_bwd_prologue(const SmoothCall& c, const float* gout, const float* out, const float* max_in,
+                               const float* stats_ext, const float* din) {
+    const bool stats_only = (c.flags & KCCOT_SMOOTH_STATS_ONLY) != 0, stats_in = (c.flags & KCCOT_SMOOTH_EXTERNAL_STATS) != 0;
+    auto stats = [&]() -> int {
+        if (stats_only && stats_in) return fail(KCCOT_EINVAL, "%s: STATS_ONLY and EXTERNAL_STATS are exclusive", c.who);
+        if ((stats_only || stats_in) && !stats_ext) return fail(KCCOT_EINVAL, "%s: null stats pointer", c.who);
+        return 0;
+    };
+    int rc;
+    // (order: the flag-driven entry points look at the stats flags ahead of the arguments, the causal-3 ones behind them)
+    if (!c.causal3 && (rc = stats())) return rc;
+    if ((rc = smooth_check(c, gout, stats_only ? gout : din))) return rc;
+    if (c.causal3 && (rc = stats())) return rc;
+    if (!out || !max_in) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
+    return smooth_check_ws(c);      // (the symmetric backward went without the "tensor too large" check until this driver)
+}
+
+// ---- the stages every form shares --------------------------------------------------------------------------------------------
+
+static int smooth_reduce_max(const float* bmax, int64_t count, float* mx, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, bmax, count, mx);
+    return launch_status("reduce_blockmax");
+}
+
+// Normalising through a last stage that can run without a store: block maxima first (WALK_MAX), then the same kernel again
+// writing s / max (WALK_WRITE) -- reducing the block maxima itself when there are few, else behind a reduce_blockmax launch --
+// or the raw sums s (WALK_RAW, NO_DIVIDE).  stage(mode, nblk) launches the stage; the modes of Fused3Args are the same numbers.
+// EVERY form comes through here, because NO_DIVIDE, EXTERNAL_MAX and the one-call form must evaluate s with the SAME kernels
+// (NO_DIVIDE runs the fast tiers too, since round 2): both phases of the batch-sharded protocol -- local maximum, then the
+// division by the all-reduced one -- would otherwise disagree by an ulp, the arg-max element comes out as 0.99999994 instead of
+// exactly 1 and the adjoint's `out == 1` tie detection finds nothing: found by the RCCL world-size-1 test, where phase 1 took
+// the per-axis chain and phase 2 the streamed walks.
+template <typename Stage>
+static int smooth_normalise(bool ext, bool nodiv, int64_t grid, float* bmax, float* mx, hipStream_t st, Stage&& stage) {
+    int rc, nblk = 0;
+    if (!ext) {
+        if ((rc = stage(WALK_MAX, 0))) return rc;
+        if (!nodiv && grid <= 4096) nblk = (int)grid;       // the writing pass reduces the block maxima itself (and stores the maximum)
+        else if ((rc = smooth_reduce_max(bmax, grid, mx, st))) return rc;
+    }
+    return stage(nodiv ? WALK_RAW : WALK_WRITE, nblk);
+}
+
+// The normalisation adjoint's two batch sums {sum(g * out), #(out == 1)} in two passes, unless they are handed in (stats_in) or
+// the first adjoint stage gathers them itself (fold).  *res = where the stages behind read them.
+static int smooth_bwd_stats(const float* gout, const float* out, int64_t n, const SmoothWs& w, bool stats_only, bool stats_in,
+                            bool fold, float* stats_ext, hipStream_t st, float** res) {
+    *res = (stats_only || stats_in) ? stats_ext : w.scal;
+    if (stats_in || fold) return 0;
+    int rc;
     const int64_t nb = (n + 255) / 256;
-    if (nb > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "smooth_fwd: tensor too large");
-    float* tmp = static_cast<float*>(ws);
-    float* bmax = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256));
-    Axis ax[3];
-    const int na = collect_axes(H, T, W, C, flags, ax);
-    const bool ext = (flags & KCCOT_SMOOTH_EXTERNAL_MAX) != 0, nodiv = (flags & KCCOT_SMOOTH_NO_DIVIDE) != 0;
-    if (ext && nodiv) return fail(KCCOT_EINVAL, "smooth_fwd: EXTERNAL_MAX and NO_DIVIDE are exclusive");
-    if (na > 0 && in == out) return fail(KCCOT_EINVAL, "smooth_fwd: in-place convolution is not supported");
-    if (flags & KCCOT_SMOOTH_CAUSAL_T)
-        return smooth_causal_fwd(in, out, max_inout, bmax, n, T, (int64_t)W * C, sigma, radius, ext, nodiv, st);
-    const Taps tp = make_taps(sigma, radius);
-    const unsigned axes = flags & (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W);
-    const bool r34 = radius == 3 || radius == 4;
-    float* one = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256) +
-                                          2 * align_up((size_t)nb * sizeof(float), 256));   // scalar slots: {1, 0, 0}
-    // (NO_DIVIDE runs here too, since round 2: both phases of the batch-sharded protocol -- local maximum, then the
-    // division by the all-reduced one -- must evaluate s with the SAME kernels, or the arg-max element comes out as
-    // 0.99999994 instead of exactly 1 and the adjoint's `out == 1` tie detection finds nothing: found by the RCCL
-    // world-size-1 test, where phase 1 took the per-axis chain and phase 2 the streamed walks)
-    if (r34 && opt(OPT_SMOOTH_STREAM) && axes == (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W)) {
+    const bool wide = (n % 4 == 0) && ((uintptr_t)gout % 16 == 0) && ((uintptr_t)out % 16 == 0) && nb >= 2048;
+    if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, w.pdot, w.pcnt);
+    else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, w.pdot, w.pcnt);
+    if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
+    hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)w.pdot, (const float*)w.pcnt,
+                       wide ? (int64_t)2048 : nb, *res);
+    return launch_status("maxnorm_bwd_combine");
+}
+
+// What follows the last stage when the statistics were folded into the first: the sparse fix-up over the nrec records, then the
+// dense form, dense(run_if), which only runs when the fix-up found too many arg-max elements (decided on the device).
+// ax[0..na) = the smoothed axes; ct = the causal taps of axis 0, or null.
+template <typename Dense>
+static int smooth_bwd_fixup(const SmoothWs& w, int64_t nrec, const float* max_in, float* din, const Axis* ax, int na, const Taps& tp,
+                            const CausalTaps* ct, hipStream_t st, Dense&& dense) {
+    FixupArgs fa{};
+    fa.ties = w.recs; fa.nrec = (int)nrec; fa.mx = max_in; fa.res = w.scal; fa.dense = w.dense(); fa.din = din; fa.na = na; fa.tp = tp;
+    for (int i = 0; i < na; ++i) { fa.len[i] = ax[i].len; fa.stride[i] = ax[i].stride; }
+    if (ct) { fa.causal = 1; fa.ct = *ct; }
+    hipLaunchKernelGGL(maxnorm_bwd_fixup, dim3(1), dim3(1024), 0, st, fa);
+    const int rc = launch_status("maxnorm_bwd_fixup");
+    return rc ? rc : dense(w.dense());
+}
+
+// the geometry of the fused walks from their plan
+template <typename Args>
+static Args fused3_geometry(const Fused3Plan& fp, int H, int T, int W, const Taps& tp, const CausalTaps& ct) {
+    Args fa{};
+    fa.H = H; fa.T = T; fa.W = W; fa.wt = fp.wt; fa.ntw = W / fp.wt; fa.hseg = fp.hseg; fa.nseg = (H + fp.hseg - 1) / fp.hseg;
+    fa.tp = tp; fa.ct = ct;
+    return fa;
+}
+
+// the W stage of a chain (W is the contiguous axis): smooth_w1, else the plane kernel on W alone, else LDS rows; WSTAGE_NONE =
+// none of them serves
+enum { WSTAGE_NONE = 0, WSTAGE_W1 = 1, WSTAGE_PLANE = 2, WSTAGE_ROW = 3 };
+static int smooth_wstage(int T, int W, int C, int radius, const void* a, const void* b) {
+    if (w1_eligible(W, C, radius, a, b) && !smooth_generic()) return WSTAGE_W1;
+    if (plane_eligible(T, W, C, radius, 1) && !smooth_generic()) return WSTAGE_PLANE;
+    if (wrow_eligible(W, C, radius)) return WSTAGE_ROW;
+    return WSTAGE_NONE;
+}
+
+// one = three scalar slots of the workspace for the plane kernel's {1, 0, 0}
+static int smooth_launch_w(int kind, const SmoothCall& c, const float* in, float* out, const float* out_fwd, float* one, bool adjoint,
+                           const Taps& tp) {
+    if (kind == WSTAGE_W1) return launch_w1(in, out, c.n(), c.W, c.radius, adjoint, tp, c.st);
+    if (kind == WSTAGE_ROW) return launch_wrow(in, out, c.n(), c.W, c.C, c.radius, adjoint, tp, c.st);
+    int rc;
+    hipLaunchKernelGGL(set_unit_scalars, dim3(1), dim3(1), 0, c.st, one);
+    if ((rc = launch_status("set_unit_scalars"))) return rc;
+    PlaneArgs pa{};
+    pa.in = in; pa.out_fwd = out_fwd; pa.out = out; pa.mx = one; pa.res = one + 1;     // max = 1, no ties: the plain stencil
+    pa.B = c.B; pa.H = c.H; pa.T = c.T; pa.W = c.W; pa.C = c.C; pa.axes = KCCOT_SMOOTH_W; pa.tp = tp; pa.hseg = plane_hseg(c.B, c.H, false);
+    return launch_plane(pa, c.radius, adjoint, dim3((c.H + pa.hseg - 1) / pa.hseg, c.B), c.st);
+}
+
+// ---- KCCOT_SMOOTH_CAUSAL_T: the causal T stencil alone -----------------------------------------------------------------------
+
+static int smooth_causal_fwd(const SmoothCall& c, const float* in, float* out, float* max_inout, const SmoothWs& w, bool ext,
+                             bool nodiv) {
+    const int64_t n = c.n(), WC = (int64_t)c.W * c.C;
+    const int vw = causal_vw(WC, in, out, out);
+    CausalArgs ca{};
+    ca.ct = make_causal_taps(c.sigma, c.radius);
+    ca.in = in; ca.T = c.T; ca.S = WC;
+    return smooth_normalise(ext, nodiv, causal_wgs(n, c.T, vw), w.bmax, max_inout, c.st, [&](int mode, int nblk) {
+        ca.nblk = nblk;
+        if (mode == WALK_MAX) ca.blockmax = w.bmax; else { ca.out = out; ca.mx = max_inout; ca.mx_out = max_inout; }
+        return launch_causal(mode, ca, c.radius, n, vw, c.st);
+    });
+}
+
+// Two-pass (the sums first, then the adjoint walk with the normalisation's adjoint at its loads) or folded (the walk gathers
+// TieRecs, then the sparse fix-up, then the guarded dense walk), by the same option and threshold as the symmetric temporal call.
+// One TieRec per workgroup: where the grid would exceed the records of the workspace (T of one or two frames) the two-pass form
+// runs whatever the option says.
+static int smooth_causal_bwd(const SmoothCall& c, const float* gout, const float* out, const float* max_in, float* stats_ext,
+                             float* din, SmoothWs& w, bool stats_only, bool stats_in) {
+    const int64_t n = c.n(), WC = (int64_t)c.W * c.C;
+    const int vw = causal_vw(WC, gout, out, stats_only ? nullptr : din);
+    const int64_t nrec = causal_wgs(n, c.T, vw);
+    const int fold_opt = opt(OPT_SMOOTH_BWD_FOLD);
+    const bool fold = !stats_only && !stats_in && (fold_opt == 2 || (fold_opt == 1 && n >= ((int64_t)1 << 22))) &&
+                      nrec <= tie_rec_capacity(n);
+    if (fold) w.fold();
+    float* res;
+    int rc = smooth_bwd_stats(gout, out, n, w, stats_only, stats_in, fold, stats_ext, c.st, &res);
+    if (rc || stats_only) return rc;
+    CausalArgs ca{};
+    ca.ct = make_causal_taps(c.sigma, c.radius);
+    ca.in = gout; ca.out_fwd = out; ca.out = din; ca.mx = max_in; ca.res = res; ca.ties = w.recs; ca.T = c.T; ca.S = WC;
+    if ((rc = launch_causal(fold ? WALK_ADJS : WALK_ADJX, ca, c.radius, n, vw, c.st)) || !fold) return rc;
+    const Axis ax{c.T, WC};
+    return smooth_bwd_fixup(w, nrec, max_in, din, &ax, 1, Taps{}, &ca.ct, c.st, [&](const int* run_if) {
+        ca.run_if = run_if;
+        return launch_causal(WALK_ADJX, ca, c.radius, n, vw, c.st);
+    });
+}
+
+// ---- the forward driver ------------------------------------------------------------------------------------------------------
+// Stage order T, W, H in the streaming tiers.  Tiers: the fused walk (smooth_fused3, all three axes) where fused3_plan finds a
+// tiling; the chain (T alone, or T, W and H-last) for radius 3 / 4; the plane kernel; the per-element conv_axis stages for every
+// other radius / shape / axis set.  c.causal3 replaces the T stage by smooth_causal (fused walk: its CAUSAL instance) and nothing
+// else: each place where the two forms differ is a branch on tcausal below.
+static int smooth_fwd_impl(const SmoothCall& c, const float* in, float* out, float* max_inout) {
+    int rc = smooth_fwd_prologue(c, in, out, max_inout);
+    if (rc) return rc;
+    const int B = c.B, H = c.H, T = c.T, W = c.W, C = c.C, radius = c.radius;
+    hipStream_t st = c.st;
+    const int64_t n = c.n(), nb = (n + 255) / 256, WC = (int64_t)W * C;
+    const SmoothWs w(c.ws, n);
+    float* const tmp = w.tmp;
+    const bool ext = (c.flags & KCCOT_SMOOTH_EXTERNAL_MAX) != 0, nodiv = (c.flags & KCCOT_SMOOTH_NO_DIVIDE) != 0;
+    if (!c.causal3 && c.tcausal()) return smooth_causal_fwd(c, in, out, max_inout, w, ext, nodiv);
+    const bool tcausal = c.causal3;
+    const unsigned axes = c.axes();
+    Axis ax[3] = {};
+    const int na = collect_axes(H, T, W, C, axes, ax);
+    const Taps tp = make_taps(c.sigma, radius);
+    const CausalTaps ct = tcausal ? make_causal_taps(c.sigma, radius) : CausalTaps{};
+    const bool r34 = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM);
+    const bool three = axes == SMOOTH_AXES;     // (always, for the causal form: it consults fused3_plan without an axes condition)
+    if (r34 && three) {
         const Fused3Plan fp = fused3_plan(B, H, T, W, C, radius, in, out);
         if (fp.ok) {
-            Fused3Args fa{};
-            fa.in = in; fa.H = H; fa.T = T; fa.W = W; fa.wt = fp.wt; fa.ntw = W / fp.wt; fa.hseg = fp.hseg;
-            fa.nseg = (H + fp.hseg - 1) / fp.hseg; fa.tp = tp;
-            if (!ext) {
-                fa.mode = 0; fa.blockmax = bmax;
+            Fused3Args fa = fused3_geometry<Fused3Args>(fp, H, T, W, tp, ct);
+            fa.in = in;
+            return smooth_normalise(ext, nodiv, fp.grid, w.bmax, max_inout, st, [&](int mode, int nblk) {
+                fa.mode = mode; fa.nblk = nblk;
+                if (mode == WALK_MAX) fa.blockmax = w.bmax; else { fa.out = out; fa.mx = max_inout; fa.mx_out = max_inout; }
 #ifdef KCCOT_DIAG
-                if (const char* e = getenv("KCCOT_F3_ABLATE")) fa.mode |= (atoi(e) & (7 | 128 | 256 | 512)) << 8;
-                if (!(getenv("KCCOT_F3_ABLATE") && (atoi(getenv("KCCOT_F3_ABLATE")) & 64)))     // bit 6: writing pass only
-#endif
-                if ((rc = launch_fused3(fp, fa, radius, C, st))) return rc;
-                fa.mode = 0;
-                if (!nodiv && fp.grid <= 4096) {
-                    fa.nblk = (int)fp.grid;       // the writing pass reduces the maxima itself (and stores the maximum)
-                } else {
-                    hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, fp.grid, max_inout);
-                    if ((rc = launch_status("reduce_blockmax"))) return rc;
+                // KCCOT_F3_ABLATE (tools/micro/f3_ablate.sh): bits for the kernel ride above the mode; bit 6: writing pass only,
+                // bit 5: maxima pass only.  The symmetric form's experiment; the causal form has never read it.
+                if (const char* e = tcausal ? nullptr : getenv("KCCOT_F3_ABLATE")) {
+                    const int bits = atoi(e);
+                    fa.mode |= (mode == WALK_MAX ? bits & (7 | 128 | 256 | 512) : bits) << 8;
+                    if (bits & (mode == WALK_MAX ? 64 : 32)) return 0;
                 }
-            }
-            fa.mode = nodiv ? 2 : 1; fa.out = out; fa.mx = max_inout; fa.mx_out = max_inout;
-#ifdef KCCOT_DIAG
-            if (const char* e = getenv("KCCOT_F3_ABLATE")) {
-                fa.mode |= atoi(e) << 8;
-                if (atoi(e) & 32) return 0;         // bit 5: maxima pass only
-            }
 #endif
-            return launch_fused3(fp, fa, radius, C, st);
+                return launch_fused3(fp, fa, radius, C, st, tcausal);
+            });
         }
     }
-    if (r34 && opt(OPT_SMOOTH_STREAM) && (axes == KCCOT_SMOOTH_T || axes == (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W))) {
-        const int64_t WC = (int64_t)W * C;
-        const bool three = axes != KCCOT_SMOOTH_T;
+    if (tcausal) {
+        // the causal form launches its T stage, in -> out (raw sums times 1 / Z_t), BEFORE it knows the tier of W and H; the
+        // symmetric form launches nothing until it does (its T stage may fuse with W, or the plane tier may take everything)
+        CausalArgs ca{};
+        ca.ct = ct; ca.in = in; ca.out = out; ca.T = T; ca.S = WC;
+        if ((rc = launch_causal(WALK_RAW, ca, radius, n, causal_vw(WC, in, out, out), st))) return rc;
+    }
+    if (r34 && (three || axes == KCCOT_SMOOTH_T)) {
         // the last stage runs twice (maxima, then recompute + write s / max); earlier stages write raw sums
-        AxisPlan pt = axis_plan(T, WC, false, false, radius, in, out, three ? tmp : out);
+        AxisPlan pt{AXIS_LINE, WalkPlan{1, 32}, 1};
+        if (!tcausal) pt = axis_plan(T, WC, false, false, radius, in, out, three ? tmp : out);      // (causal: T is done)
         // temporal-only call: 8-byte pieces (twice the threads) are 4-6 % faster than 16-byte ones on both passes at every
         // BASELINE shape (22.2 -> 20.8 us, 101 -> 97 us, 227 -> 216 us); the 3-D call keeps 16-byte pieces for the T+W fusion
         if (!three && pt.kind == AXIS_LINE && pt.wp.vw == 4) { pt.wp.vw = 2; pt.vw = 2; }
         const AxisPlan ph = three ? axis_plan(H, (int64_t)T * WC, false, false, radius, tmp, out, out) : AxisPlan{AXIS_LINE, WalkPlan{1, 32}, 1};
-        const bool w1 = three && w1_eligible(W, C, radius, out, tmp) && !smooth_generic();
-        const bool wplane = three && !w1 && plane_eligible(T, W, C, radius, 1) && !smooth_generic();
-        const bool wrow = three && !w1 && !wplane && wrow_eligible(W, C, radius);
-        if (pt.kind != AXIS_NONE && ph.kind != AXIS_NONE && (!three || w1 || wplane || wrow || tw_plane_eligible(T, W, C, radius, false, in, tmp))) {
+        const int wk = three ? smooth_wstage(T, W, C, radius, out, tmp) : WSTAGE_NONE;
+        // T and W in one launch with the (b, h) plane staged in LDS (smooth_tw_plane): there is no causal instance of it
+        const bool twp_ok = three && !tcausal && tw_plane_eligible(T, W, C, radius, false, in, tmp);
+        if (pt.kind != AXIS_NONE && ph.kind != AXIS_NONE && (!three || wk != WSTAGE_NONE || twp_ok)) {
             WalkArgs wa{};
-            wa.tp = tp;
-            const float* last_in = in;
-            AxisPlan last = pt;
-            wa.L = T; wa.S = WC;
+            wa.tp = tp; wa.in = in; wa.L = T; wa.S = WC;
             if (three) {
-                // T: in -> out (raw);  W: out -> tmp (raw; the axis is contiguous: smooth_w1 / LDS rows);  H: tmp -> out
-                // -- or T and W in one launch, in -> tmp (WALK_RAW_TW), when a row of W is W/4 lanes of a wave
-                const int W4 = W >> 2;
-                const bool tw = w1 && pt.kind == AXIS_LINE && pt.vw == 4 && W4 <= 64 && (W4 & (W4 - 1)) == 0 && opt(OPT_SMOOTH_FUSED_TW);
-                // -- or, for any channel count, with the (b, h) plane staged in LDS (smooth_tw_plane)
-                const bool twp = !tw && tw_plane_eligible(T, W, C, radius, false, in, tmp);
-                if (twp) {
-                    if ((rc = launch_tw_plane(in, tmp, n, T, W, C, radius, false, tp, st))) return rc;
-                } else {
-                    wa.in = in; wa.out = tw ? tmp : out;
-                    if ((rc = launch_axis(tw ? WALK_RAW_TW : WALK_RAW, wa, radius, n, pt, st))) return rc;
+                // T: in -> out (raw);  W: out -> tmp (raw);  H: tmp -> out
+                bool tw_done = false;
+                if (!tcausal) {
+                    // -- or T and W in one launch, in -> tmp (WALK_RAW_TW), when a row of W is W/4 lanes of a wave (no causal
+                    // instance either), or through smooth_tw_plane for any channel count
+                    const int W4 = W >> 2;
+                    const bool tw = wk == WSTAGE_W1 && pt.kind == AXIS_LINE && pt.vw == 4 && W4 <= 64 && (W4 & (W4 - 1)) == 0 &&
+                                    opt(OPT_SMOOTH_FUSED_TW);
+                    tw_done = tw || twp_ok;
+                    if (!tw && twp_ok) {
+                        if ((rc = launch_tw_plane(in, tmp, n, T, W, C, radius, false, tp, st))) return rc;
+                    } else {
+                        wa.out = tw ? tmp : out;
+                        if ((rc = launch_axis(tw ? WALK_RAW_TW : WALK_RAW, wa, radius, n, pt, st))) return rc;
+                    }
                 }
-                if (tw || twp) {
-                } else if (w1) {
-                    if ((rc = launch_w1(out, tmp, n, W, radius, false, tp, st))) return rc;
-                } else if (wrow) {
-                    if ((rc = launch_wrow(out, tmp, n, W, C, radius, false, tp, st))) return rc;
-                } else {
-                    hipLaunchKernelGGL(set_unit_scalars, dim3(1), dim3(1), 0, st, one);
-                    if ((rc = launch_status("set_unit_scalars"))) return rc;
-                    PlaneArgs pa{};
-                    pa.in = out; pa.out = tmp; pa.mx = one; pa.B = B; pa.H = H; pa.T = T; pa.W = W; pa.C = C;
-                    pa.axes = KCCOT_SMOOTH_W; pa.tp = tp; pa.hseg = plane_hseg(B, H, false);
-                    if ((rc = launch_plane(pa, radius, false, dim3((H + pa.hseg - 1) / pa.hseg, B), st))) return rc;
-                }
-                last_in = tmp; last = ph;
-                wa.L = H; wa.S = (int64_t)T * WC;
+                if (!tw_done && (rc = smooth_launch_w(wk, c, out, tmp, nullptr, w.unit(SmoothWs::UNIT_FWD), false, tp))) return rc;
+                wa.in = tmp; wa.L = H; wa.S = (int64_t)T * WC;
             }
-            wa.in = last_in;
-            const int64_t last_wgs = (n / wa.L / last.vw + 255) / 256;
-            wa.nblk = 0;
-            if (!ext) {
-                wa.out = nullptr; wa.blockmax = bmax;
-                if ((rc = launch_axis(WALK_MAX, wa, radius, n, last, st))) return rc;
-                if (!nodiv && last_wgs <= 4096) {
-                    wa.nblk = (int)last_wgs;      // the writing pass reduces the block maxima itself (and stores the maximum)
-                } else {
-                    hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, last_wgs, max_inout);
-                    if ((rc = launch_status("reduce_blockmax"))) return rc;
-                }
-            }
-            wa.out = out; wa.mx = max_inout; wa.mx_out = max_inout;
-            if (wa.nblk == 0) wa.blockmax = nullptr;
-            return launch_axis(nodiv ? WALK_RAW : WALK_WRITE, wa, radius, n, last, st);   // NO_DIVIDE: the raw sums
+            wa.out = nullptr;
+            const AxisPlan& last = three ? ph : pt;
+            return smooth_normalise(ext, nodiv, (n / wa.L / last.vw + 255) / 256, w.bmax, max_inout, st, [&](int mode, int nblk) {
+                wa.nblk = nblk;
+                wa.blockmax = (mode == WALK_MAX || nblk) ? w.bmax : nullptr;
+                if (mode != WALK_MAX) { wa.out = out; wa.mx = max_inout; wa.mx_out = max_inout; }
+                return launch_axis(mode, wa, radius, n, last, st);
+            });
         }
     }
-    if (plane_eligible(T, W, C, radius, na) && !nodiv) {
+    // the plane tier (legacy; the symmetric form only: smooth_plane has no causal T)
+    if (!tcausal && plane_eligible(T, W, C, radius, na) && !nodiv) {
         PlaneArgs pa{};
-        pa.in = in; pa.B = B; pa.H = H; pa.T = T; pa.W = W; pa.C = C; pa.axes = flags; pa.tp = tp;
-        pa.hseg = plane_hseg(B, H, (flags & KCCOT_SMOOTH_H) != 0);
+        pa.in = in; pa.B = B; pa.H = H; pa.T = T; pa.W = W; pa.C = C; pa.axes = c.flags; pa.tp = tp;
+        pa.hseg = plane_hseg(B, H, (c.flags & KCCOT_SMOOTH_H) != 0);
         const dim3 grid((H + pa.hseg - 1) / pa.hseg, B);
         if (!ext) {   // pass 1: maxima only
-            pa.out = nullptr; pa.blockmax = bmax;
+            pa.out = nullptr; pa.blockmax = w.bmax;
             if ((rc = launch_plane(pa, radius, false, grid, st))) return rc;
-            hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, (int64_t)grid.x * grid.y, max_inout);
-            if ((rc = launch_status("reduce_blockmax"))) return rc;
+            if ((rc = smooth_reduce_max(w.bmax, (int64_t)grid.x * grid.y, max_inout, st))) return rc;
         }
         pa.out = out; pa.blockmax = nullptr; pa.mx = max_inout;   // pass 2: recompute, write s / max
         return launch_plane(pa, radius, false, grid, st);
     }
-    const float* src = in;
-    for (int i = 0; i < na; ++i) {
-        float* dst = ((na - 1 - i) % 2 == 0) ? out : tmp;
-        const bool last = (i == na - 1);
-        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, src, dst, n, ax[i].len, ax[i].stride, tp, 0,
-                           (last && !ext) ? bmax : (float*)nullptr);
+    // any radius, any shape, per element: the stages ping-pong so that the last one writes `out`, then the maximum, then the
+    // division in place.  Symmetric: the axes in collect_axes order from `in`; causal: W, then H behind the T stage's `out`.
+    const Axis causal_rest[2] = {ax[2], ax[1]};
+    const Axis* stage = tcausal ? causal_rest : ax;
+    const int ns = tcausal ? 2 : na;
+    const float* src = tcausal ? out : in;
+    for (int i = 0; i < ns; ++i) {
+        float* dst = ((ns - 1 - i) % 2 == 0) ? out : tmp;
+        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, src, dst, n, stage[i].len, stage[i].stride, tp, 0,
+                           (i == ns - 1 && !ext) ? w.bmax : (float*)nullptr);
         if ((rc = launch_status("conv_axis"))) return rc;
         src = dst;
     }
     if (na == 0 && !ext) {   // max (and copy) only
-        hipLaunchKernelGGL(copy_with_blockmax, dim3((unsigned)nb), dim3(256), 0, st, in, out, n, bmax);
+        hipLaunchKernelGGL(copy_with_blockmax, dim3((unsigned)nb), dim3(256), 0, st, in, out, n, w.bmax);
         if ((rc = launch_status("copy_with_blockmax"))) return rc;
     }
-    if (!ext) {
-        hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, nb, max_inout);
-        if ((rc = launch_status("reduce_blockmax"))) return rc;
-    }
+    if (!ext && (rc = smooth_reduce_max(w.bmax, nb, max_inout, st))) return rc;
     if (!nodiv) {
         const float* dsrc = (na == 0 && ext) ? in : out;
         hipLaunchKernelGGL(divide_by, dim3((unsigned)nb), dim3(256), 0, st, dsrc, out, n, (const float*)max_inout);
@@ -2432,94 +2598,45 @@ extern "C" int kccot_smooth_fwd_f32(const float* in, int B, int H, int T, int W,
     return 0;
 }
 
+// ---- the backward driver -----------------------------------------------------------------------------------------------------
 // stats_ext: null = the normalisation adjoint's two batch sums {sum(g * out), #(out == 1)} are computed and used
 // here; with KCCOT_SMOOTH_STATS_ONLY they are written to stats_ext and nothing else happens; with
 // KCCOT_SMOOTH_EXTERNAL_STATS they are READ from stats_ext (the batch-sharded caller has all-reduced(SUM) them).
-static int smooth_bwd_impl(const float* gout, const float* out, const float* max_in, float* stats_ext, int B, int H, int T,
-                           int W, int C, float sigma, int radius, unsigned flags, float* din, void* ws,
-                           size_t ws_bytes, kccot_stream_t stream) {
-    const bool stats_only = (flags & KCCOT_SMOOTH_STATS_ONLY) != 0, stats_in = (flags & KCCOT_SMOOTH_EXTERNAL_STATS) != 0;
-    if (stats_only && stats_in) return fail(KCCOT_EINVAL, "smooth_bwd: STATS_ONLY and EXTERNAL_STATS are exclusive");
-    if ((stats_only || stats_in) && !stats_ext) return fail(KCCOT_EINVAL, "smooth_bwd: null stats pointer");
-    int rc = smooth_check("smooth_bwd", gout, stats_only ? const_cast<float*>(gout) : din, B, H, T, W, C, sigma, radius, flags);
+// Adjoint stages in reverse order -- H^T, W^T, T^T -- the first one also applying the adjoint of the max-normalisation (two-pass)
+// or gathering its statistics (folded).  c.causal3: the last stage is the plain causal T^T (smooth_causal WALK_ADJ); the other
+// differences are branches on tcausal below.
+static int smooth_bwd_impl(const SmoothCall& c, const float* gout, const float* out, const float* max_in, float* stats_ext,
+                           float* din) {
+    int rc = smooth_bwd_prologue(c, gout, out, max_in, stats_ext, din);
     if (rc) return rc;
-    if (!out || !max_in) return fail(KCCOT_EINVAL, "smooth_bwd: null pointer");
-    const size_t need = kccot_smooth_workspace_bytes(B, H, T, W, C);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "smooth_bwd: workspace %zu < required %zu", ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = (int64_t)B * H * T * W * C;
-    const int64_t nb = (n + 255) / 256;
-    float* tmp = static_cast<float*>(ws);
-    char* p = static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256);
-    float* pdot = reinterpret_cast<float*>(p);
-    float* pcnt = reinterpret_cast<float*>(p + align_up((size_t)nb * sizeof(float), 256));
-    float* res = reinterpret_cast<float*>(p + 2 * align_up((size_t)nb * sizeof(float), 256));
-    Axis ax[3];
-    const int na = collect_axes(H, T, W, C, flags, ax);
-    const Taps tp = make_taps(sigma, radius);
-    // ds goes where the adjoint chain wants its first source: (na passes) ... -> din
-    float* ds = (na % 2 == 0) ? din : tmp;
-    const bool wide = (n % 4 == 0) && ((uintptr_t)gout % 16 == 0) && ((uintptr_t)out % 16 == 0) && nb >= 2048;
-    const int64_t nparts = wide ? 2048 : nb;
-    float* scal = reinterpret_cast<float*>(p + 2 * align_up((size_t)nb * sizeof(float), 256));   // workspace scalars {dot, ties, .., .., 1, 0, 0, dense}
-    TieRec* recs = reinterpret_cast<TieRec*>(p + 2 * align_up((size_t)nb * sizeof(float), 256) + 256);
-    if (flags & KCCOT_SMOOTH_CAUSAL_T) {
-        // The one-sided T stencil on the same statistics / fix-up machinery: two-pass (the sums first, then the adjoint walk with
-        // the normalisation's adjoint at its loads) or folded (the walk gathers TieRecs, then the sparse fix-up, then the guarded
-        // dense walk), by the same option and threshold as the symmetric temporal call.  One TieRec per workgroup: where the
-        // grid would exceed the records of the workspace (T of one or two frames) the two-pass form runs whatever the option says.
-        const int64_t WC = (int64_t)W * C;
-        const int vw = causal_vw(WC, gout, out, stats_only ? nullptr : din);
-        const int64_t nrec = causal_wgs(n, T, vw);
-        const int fold_opt = opt(OPT_SMOOTH_BWD_FOLD);
-        const bool fold = !stats_only && !stats_in && (fold_opt == 2 || (fold_opt == 1 && n >= ((int64_t)1 << 22))) &&
-                          nrec <= tie_rec_capacity(n);
-        if (fold) {
-            recs = reinterpret_cast<TieRec*>(p);
-            scal = res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n) + smooth_rec_bytes(n));
-        } else if (stats_in) {
-            res = stats_ext;
-        } else {
-            if (stats_only) res = stats_ext;
-            if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, pdot, pcnt);
-            else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, pdot, pcnt);
-            if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
-            hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)pdot, (const float*)pcnt, nparts, res);
-            if ((rc = launch_status("maxnorm_bwd_combine"))) return rc;
-            if (stats_only) return 0;
-        }
-        CausalArgs ca{};
-        ca.ct = make_causal_taps(sigma, radius);
-        ca.in = gout; ca.out_fwd = out; ca.out = din; ca.mx = max_in; ca.res = res; ca.ties = recs; ca.T = T; ca.S = WC;
-        if ((rc = launch_causal(fold ? WALK_ADJS : WALK_ADJX, ca, radius, n, vw, st)) || !fold) return rc;
-        int* dense = reinterpret_cast<int*>(scal + 7);
-        FixupArgs fa{};
-        fa.ties = recs; fa.nrec = (int)nrec; fa.mx = max_in; fa.res = res; fa.dense = dense; fa.din = din; fa.na = 1;
-        fa.len[0] = T; fa.stride[0] = WC; fa.causal = 1; fa.ct = ca.ct;
-        hipLaunchKernelGGL(maxnorm_bwd_fixup, dim3(1), dim3(1024), 0, st, fa);
-        if ((rc = launch_status("maxnorm_bwd_fixup"))) return rc;
-        ca.run_if = dense;
-        return launch_causal(WALK_ADJX, ca, radius, n, vw, st);
-    }
-    const unsigned axes = flags & (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W);
+    const int B = c.B, H = c.H, T = c.T, W = c.W, C = c.C, radius = c.radius;
+    hipStream_t st = c.st;
+    const int64_t n = c.n(), nb = (n + 255) / 256, WC = (int64_t)W * C;
+    SmoothWs w(c.ws, n);
+    float* const tmp = w.tmp;
+    const bool stats_only = (c.flags & KCCOT_SMOOTH_STATS_ONLY) != 0, stats_in = (c.flags & KCCOT_SMOOTH_EXTERNAL_STATS) != 0;
+    if (!c.causal3 && c.tcausal()) return smooth_causal_bwd(c, gout, out, max_in, stats_ext, din, w, stats_only, stats_in);
+    const bool tcausal = c.causal3;
+    const unsigned axes = c.axes();
+    Axis ax[3] = {};
+    const int na = collect_axes(H, T, W, C, axes, ax);
+    const Taps tp = make_taps(c.sigma, radius);
+    const CausalTaps ct = tcausal ? make_causal_taps(c.sigma, radius) : CausalTaps{};
     // The streaming chains (temporal only / all three axes, radius 3 or 4).  Decided in front of the statistics: with the
     // option "smooth_bwd_fold" the chain's first stage gathers them itself (WALK_ADJS) and the pass below is skipped.
-    const int64_t WC = (int64_t)W * C;
-    const bool three = axes != KCCOT_SMOOTH_T;
-    bool chain = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM) && !stats_only &&
-                 (axes == KCCOT_SMOOTH_T || axes == (KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W));
-    AxisPlan ph{AXIS_LINE, WalkPlan{1, 32}, 1}, pt{AXIS_NONE, WalkPlan{0, 0}, 0};
-    bool w1 = false, wplane = false, wrow = false, twp = false;
+    const bool three = axes == SMOOTH_AXES;
+    bool chain = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM) && !stats_only && (three || axes == KCCOT_SMOOTH_T);
+    AxisPlan ph{AXIS_LINE, WalkPlan{1, 32}, 1}, pt = ph;
+    int wk = WSTAGE_NONE;
+    bool twp = false;
     if (chain) {
-        // adjoint stages in reverse order; the first one also applies the adjoint of the max-normalisation
         if (three) ph = axis_plan(H, (int64_t)T * WC, true, true, radius, gout, out, din);
-        pt = axis_plan(T, WC, !three, true, radius, three ? (const void*)tmp : (const void*)gout, out, din);
-        w1 = three && w1_eligible(W, C, radius, din, tmp) && !smooth_generic();
-        wplane = three && !w1 && plane_eligible(T, W, C, radius, 1) && !smooth_generic();
-        wrow = three && !w1 && !wplane && wrow_eligible(W, C, radius);
-        twp = three && tw_plane_eligible(T, W, C, radius, true, tmp, din);
-        chain = pt.kind != AXIS_NONE && ph.kind != AXIS_NONE && (!three || w1 || wplane || wrow || twp);
+        if (!tcausal) pt = axis_plan(T, WC, !three, true, radius, three ? (const void*)tmp : (const void*)gout, out, din);
+        if (three) wk = smooth_wstage(T, W, C, radius, din, tmp);
+        twp = three && !tcausal && tw_plane_eligible(T, W, C, radius, true, tmp, din);      // W^T and T^T in one pass: symmetric T only
+        chain = pt.kind != AXIS_NONE && ph.kind != AXIS_NONE && (!three || wk != WSTAGE_NONE || twp);
     }
+    const int vwt = tcausal ? causal_vw(WC, tmp, din, din) : 0;
     // Folding trades two tensor reads for two (temporal) / four (3-D) more launches of ~5 us each behind the chain (the
     // fix-up and the guarded dense chain, dependent launches on one stream).  Measured: temporal 17.7 -> 22.0 us at 2 M
     // elements, 33.9 -> 32.8 us at 7.9 M, 350 -> 254 us at 94 M; 3-D 37.8 -> 61.1 us at 2 M, 65.4 -> 79.0 us at 7.9 M,
@@ -2529,401 +2646,145 @@ static int smooth_bwd_impl(const float* gout, const float* out, const float* max
     // 3.5 M elements on for the 3-D call -- the plan decides.
     Fused3Plan fpa{};
     if (chain && three && (stats_in || fold_opt != 0) && ((uintptr_t)out & 15) == 0) fpa = fused3_plan(B, H, T, W, C, radius, gout, din, true, !stats_in);
-    const bool fold = chain && !stats_in && (fold_opt == 2 || fpa.ok || (fold_opt == 1 && n >= (three ? (int64_t)1 << 25 : (int64_t)1 << 22)));
-    if (fold) {     // no per-block partial sums: the records start at the per-block arrays, the scalars sit behind the records
-        recs = reinterpret_cast<TieRec*>(p);
-        scal = res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n) + smooth_rec_bytes(n));
+    const AxisPlan& p1 = three ? ph : pt;               // the stage that reads gout and the forward output
+    // one TieRec per workgroup of that stage (fused3_plan never returns a tiling that does not fit the records)
+    int64_t nrec = chain ? (n / (three ? H : T) / p1.vw + 255) / 256 : 0;
+    bool fold = chain && !stats_in && (fold_opt == 2 || fpa.ok || (fold_opt == 1 && n >= (three ? (int64_t)1 << 25 : (int64_t)1 << 22)));
+    if (fold && nrec > tie_rec_capacity(n)) {
+        // where that grid would not fit the records of the workspace the causal form runs two-pass whatever the option says (as
+        // KCCOT_SMOOTH_CAUSAL_T does); the symmetric form has always refused, even with a fused plan that would fit
+        if (!tcausal) return fail(KCCOT_EUNSUPPORTED, "%s: %lld tie records > %lld in the workspace", c.who, (long long)nrec, (long long)tie_rec_capacity(n));
+        fold = fpa.ok;
+    }
+    if (fold) w.fold();
+    Fused3AdjArgs fx{};
+    if (fpa.ok) {
+        fx = fused3_geometry<Fused3AdjArgs>(fpa, H, T, W, tp, ct);
+        fx.gout = gout; fx.out_fwd = out; fx.din = din; fx.mx = max_in;
     }
     if (stats_in && fpa.ok) {       // the batch-sharded caller: sums handed in, correction applied at the loads, nothing to fix up
-        Fused3AdjArgs fa{};
-        fa.gout = gout; fa.out_fwd = out; fa.din = din; fa.mx = max_in; fa.res = stats_ext;
-        fa.H = H; fa.T = T; fa.W = W; fa.wt = fpa.wt; fa.ntw = W / fpa.wt; fa.hseg = fpa.hseg; fa.nseg = (H + fpa.hseg - 1) / fpa.hseg; fa.tp = tp;
-        return launch_fused3_adj(fpa, fa, C, true, st);
+        fx.res = stats_ext;
+        return launch_fused3_adj(fpa, fx, C, true, st, tcausal);
     }
-    if (stats_in) {
-        res = stats_ext;                                       // the global sums: every kernel below reads res[0], res[1]
-    } else if (!fold) {
-        if (stats_only) res = stats_ext;
-        if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, pdot, pcnt);
-        else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, pdot, pcnt);
-        if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
-        hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)pdot, (const float*)pcnt, nparts, res);
-        if ((rc = launch_status("maxnorm_bwd_combine"))) return rc;
-        if (stats_only) return 0;
+    float* res;
+    rc = smooth_bwd_stats(gout, out, n, w, stats_only, stats_in, fold, stats_ext, st, &res);
+    if (rc || stats_only) return rc;
+    if (!chain) {
+        // any radius, any shape, per element: the normalisation's adjoint gout -> ds, then the stages in reverse, ping-ponging so
+        // that the last one writes din.  Symmetric: collect_axes order reversed; causal: H^T, W^T, then the causal T^T tmp -> din.
+        const Axis causal_rest[2] = {ax[2], ax[1]};
+        const Axis* stage = tcausal ? causal_rest : ax;
+        const int ns = tcausal ? 2 : na;
+        float* ds = ((ns + (tcausal ? 1 : 0)) % 2 == 0) ? din : tmp;
+        hipLaunchKernelGGL(maxnorm_bwd_apply, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, max_in, (const float*)res, ds);
+        if ((rc = launch_status("maxnorm_bwd_apply"))) return rc;
+        const float* src = ds;
+        for (int i = ns - 1; i >= 0; --i) {
+            float* dst = (src == tmp) ? din : tmp;
+            hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, src, dst, n, stage[i].len, stage[i].stride, tp, 1,
+                               (float*)nullptr);
+            if ((rc = launch_status("conv_axis(adjoint)"))) return rc;
+            src = dst;
+        }
+        if (!tcausal) return 0;
+        CausalArgs ca{};
+        ca.ct = ct; ca.in = tmp; ca.out = din; ca.T = T; ca.S = WC;
+        return launch_causal(WALK_ADJ, ca, radius, n, vwt, st);
     }
-    if (chain) {
-        {
-            WalkArgs wa{};
-            wa.tp = tp; wa.out_fwd = out; wa.mx = max_in; wa.res = res; wa.ties = recs;
-            const int first = fold ? WALK_ADJS : WALK_ADJX;
-            const AxisPlan& p1 = three ? ph : pt;               // the stage that reads gout and the forward output
-            int nrec = (int)((n / (three ? H : T) / p1.vw + 255) / 256);
-            // what follows the last stage when the statistics were folded into the first: the sparse fix-up, then the
-            // dense chain that only runs when the fix-up found too many arg-max elements
-            auto finish = [&](const Fused3Plan* fused = nullptr) -> int {
-                if (!fold) return 0;
-                int* dense = reinterpret_cast<int*>(scal + 7);
-                FixupArgs fa{};
-                fa.ties = recs; fa.nrec = nrec; fa.mx = max_in; fa.res = res; fa.dense = dense; fa.din = din; fa.na = na; fa.tp = tp;
-                for (int i = 0; i < na; ++i) { fa.len[i] = ax[i].len; fa.stride[i] = ax[i].stride; }
-                hipLaunchKernelGGL(maxnorm_bwd_fixup, dim3(1), dim3(1024), 0, st, fa);
-                int rc2 = launch_status("maxnorm_bwd_fixup");
-                if (rc2) return rc2;
-                if (fused) {    // dense fallback of the fused walk: the same walk once more, guarded, with the sums the fix-up has just
-                                // written and the correction applied at the loads (one guarded launch instead of three)
-                    Fused3AdjArgs fx{};
-                    fx.gout = gout; fx.out_fwd = out; fx.din = din; fx.mx = max_in; fx.res = res; fx.run_if = dense;
-                    fx.H = H; fx.T = T; fx.W = W; fx.wt = fused->wt; fx.ntw = W / fused->wt; fx.hseg = fused->hseg;
-                    fx.nseg = (H + fused->hseg - 1) / fused->hseg; fx.tp = tp;
-                    return launch_fused3_adj(*fused, fx, C, true, st);
-                }
-                // the round-2 chain with the sums the fix-up has just written: H^T (+ normalisation adjoint) gout -> din,
-                // W^T din -> tmp, T^T tmp -> din;  temporal only: T^T (+ normalisation adjoint) gout -> din
-                WalkArgs wd{};
-                wd.tp = tp; wd.out_fwd = out; wd.mx = max_in; wd.res = res; wd.run_if = dense;
-                wd.in = gout; wd.out = din; wd.L = three ? H : T; wd.S = three ? (int64_t)T * WC : WC;
-                if ((rc2 = launch_axis(WALK_ADJX, wd, radius, n, p1, st))) return rc2;
-                if (!three) return 0;
-                hipLaunchKernelGGL(conv_axis_adjoint_if, dim3((unsigned)std::min<int64_t>(nb, 2048)), dim3(256), 0, st,
-                                   (const float*)din, tmp, n, W, (int64_t)C, tp, (const int*)dense);
-                if ((rc2 = launch_status("conv_axis_adjoint_if"))) return rc2;
-                wd.in = tmp; wd.out = din; wd.L = T; wd.S = WC;
-                if ((rc2 = launch_axis(WALK_ADJ, wd, radius, n, pt, st))) return rc2;
-                return 0;
-            };
-            if (fold && nrec > tie_rec_capacity(n))
-                return fail(KCCOT_EUNSUPPORTED, "smooth_bwd: %d tie records > %lld in the workspace", nrec, (long long)tie_rec_capacity(n));
-            if (!three) {
-                wa.in = gout; wa.out = din; wa.L = T; wa.S = WC;
-                if ((rc = launch_axis(first, wa, radius, n, pt, st))) return rc;
-                return finish();
-            }
-            {               // all three adjoint stages in one pass (smooth_fused3_adj), the statistics gathered on the way
-                const Fused3Plan& fp = fpa;
-                if (fp.ok) {
-                    if (fp.grid > tie_rec_capacity(n))      // (fused3_plan never returns such a plan; checked where the records are written)
-                        return fail(KCCOT_EUNSUPPORTED, "smooth_bwd: %lld tie records > %lld in the workspace", (long long)fp.grid,
-                                    (long long)tie_rec_capacity(n));
-                    Fused3AdjArgs fa{};
-                    fa.gout = gout; fa.out_fwd = out; fa.din = din; fa.mx = max_in; fa.ties = recs;
-                    fa.H = H; fa.T = T; fa.W = W; fa.wt = fp.wt; fa.ntw = W / fp.wt; fa.hseg = fp.hseg;
-                    fa.nseg = (H + fp.hseg - 1) / fp.hseg; fa.tp = tp;
-                    if ((rc = launch_fused3_adj(fp, fa, C, false, st))) return rc;
-                    nrec = (int)fp.grid;
-                    return finish(&fp);
-                }
-            }
-            // H^T (+ normalisation adjoint): gout -> din;  W^T: din -> tmp;  T^T: tmp -> din
-            wa.in = gout; wa.out = twp ? tmp : din; wa.L = H; wa.S = (int64_t)T * WC;
-            if ((rc = launch_axis(first, wa, radius, n, ph, st))) return rc;
-            if (twp) {                                              // W^T and T^T in one pass: tmp -> din
-                if ((rc = launch_tw_plane(tmp, din, n, T, W, C, radius, true, tp, st))) return rc;
-                return finish();
-            }
-            if (w1) {
-                if ((rc = launch_w1(din, tmp, n, W, radius, true, tp, st))) return rc;
-            } else if (wrow) {
-                if ((rc = launch_wrow(din, tmp, n, W, C, radius, true, tp, st))) return rc;
-            } else {
-                float* one = scal + 4;                          // scalar slots behind {dot, ties}: {1, 0, 0}
-                hipLaunchKernelGGL(set_unit_scalars, dim3(1), dim3(1), 0, st, one);
-                if ((rc = launch_status("set_unit_scalars"))) return rc;
-                PlaneArgs pa{};
-                pa.in = din; pa.out_fwd = out; pa.out = tmp; pa.mx = one; pa.res = one + 1;   // max = 1, no ties: plain W^T
-                pa.B = B; pa.H = H; pa.T = T; pa.W = W; pa.C = C; pa.axes = KCCOT_SMOOTH_W; pa.tp = tp;
-                pa.hseg = plane_hseg(B, H, false);
-                if ((rc = launch_plane(pa, radius, true, dim3((H + pa.hseg - 1) / pa.hseg, B), st))) return rc;
-            }
-            wa.in = tmp; wa.out = din; wa.L = T; wa.S = WC;
-            if ((rc = launch_axis(WALK_ADJ, wa, radius, n, pt, st))) return rc;
-            return finish();
+    // the last stage of the 3-D chain, tmp -> din: the walk along T, or the plain causal T^T
+    auto t_adjoint = [&](WalkArgs wa) -> int {
+        if (tcausal) {
+            CausalArgs ca{};
+            ca.ct = ct; ca.in = tmp; ca.out = din; ca.T = T; ca.S = WC; ca.run_if = wa.run_if;
+            return launch_causal(WALK_ADJ, ca, radius, n, vwt, st);
+        }
+        wa.in = tmp; wa.out = din; wa.L = T; wa.S = WC;
+        return launch_axis(WALK_ADJ, wa, radius, n, pt, st);
+    };
+    WalkArgs wa{};
+    wa.tp = tp; wa.out_fwd = out; wa.mx = max_in; wa.res = res; wa.ties = w.recs;
+    wa.in = gout; wa.out = din; wa.L = three ? H : T; wa.S = three ? (int64_t)T * WC : WC;
+    if (fold && fpa.ok) {           // all three adjoint stages in one pass (smooth_fused3_adj), the statistics gathered on the way
+        if (fpa.grid > tie_rec_capacity(n))      // (fused3_plan never returns such a plan; checked where the records are written)
+            return fail(KCCOT_EUNSUPPORTED, "%s: %lld tie records > %lld in the workspace", c.who, (long long)fpa.grid, (long long)tie_rec_capacity(n));
+        fx.ties = w.recs;
+        if ((rc = launch_fused3_adj(fpa, fx, C, false, st, tcausal))) return rc;
+        nrec = fpa.grid;
+    } else {
+        // temporal only: T^T (+ normalisation adjoint) gout -> din.  3-D: H^T (+ normalisation adjoint) gout -> din;  W^T din -> tmp;
+        // T^T tmp -> din -- or H^T gout -> tmp and W^T with T^T in one pass, tmp -> din (smooth_tw_plane)
+        if (twp) wa.out = tmp;
+        if ((rc = launch_axis(fold ? WALK_ADJS : WALK_ADJX, wa, radius, n, p1, st))) return rc;
+        if (twp) {
+            if ((rc = launch_tw_plane(tmp, din, n, T, W, C, radius, true, tp, st))) return rc;
+        } else if (three) {
+            if ((rc = smooth_launch_w(wk, c, din, tmp, out, w.unit(SmoothWs::UNIT_BWD), true, tp))) return rc;
+            if ((rc = t_adjoint(wa))) return rc;
         }
     }
-    hipLaunchKernelGGL(maxnorm_bwd_apply, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, max_in, (const float*)res, ds);
-    if ((rc = launch_status("maxnorm_bwd_apply"))) return rc;
-    const float* src = ds;
-    for (int i = na - 1; i >= 0; --i) {
-        float* dst = (src == tmp) ? din : tmp;
-        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, src, dst, n, ax[i].len, ax[i].stride, tp, 1,
-                           (float*)nullptr);
-        if ((rc = launch_status("conv_axis(adjoint)"))) return rc;
-        src = dst;
-    }
-    return 0;
+    if (!fold) return 0;
+    return smooth_bwd_fixup(w, nrec, max_in, din, ax, na, tp, tcausal ? &ct : nullptr, st, [&](const int* run_if) -> int {
+        if (fpa.ok) {   // dense fallback of the fused walk: the same walk once more, guarded, with the sums the fix-up has just
+                        // written and the correction applied at the loads (one guarded launch instead of three)
+            fx.ties = nullptr; fx.res = res; fx.run_if = run_if;
+            return launch_fused3_adj(fpa, fx, C, true, st, tcausal);
+        }
+        // the round-2 chain with the sums the fix-up has just written: H^T (+ normalisation adjoint) gout -> din,
+        // W^T din -> tmp, T^T tmp -> din;  temporal only: T^T (+ normalisation adjoint) gout -> din
+        WalkArgs wd{};
+        wd.tp = tp; wd.out_fwd = out; wd.mx = max_in; wd.res = res; wd.run_if = run_if;
+        wd.in = gout; wd.out = din; wd.L = three ? H : T; wd.S = three ? (int64_t)T * WC : WC;
+        int rc2 = launch_axis(WALK_ADJX, wd, radius, n, p1, st);
+        if (rc2 || !three) return rc2;
+        hipLaunchKernelGGL(conv_axis_adjoint_if, dim3((unsigned)std::min<int64_t>(nb, 2048)), dim3(256), 0, st, (const float*)din, tmp,
+                           n, W, (int64_t)C, tp, run_if);
+        if ((rc2 = launch_status("conv_axis_adjoint_if"))) return rc2;
+        return t_adjoint(wd);
+    });
+}
+
+// ---- the entry points --------------------------------------------------------------------------------------------------------
+
+static const unsigned SMOOTH_STATS_FLAGS = KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS;
+
+extern "C" int kccot_smooth_fwd_f32(const float* in, int B, int H, int T, int W, int C, float sigma, int radius,
+                                    unsigned flags, float* out, float* max_inout, void* ws, size_t ws_bytes,
+                                    kccot_stream_t stream) {
+    return smooth_fwd_impl(SmoothCall{"smooth_fwd", false, B, H, T, W, C, sigma, radius, flags, ws, ws_bytes, (hipStream_t)stream}, in, out, max_inout);
 }
 
 extern "C" int kccot_smooth_bwd_f32(const float* gout, const float* out, const float* max_in, int B, int H, int T,
                                     int W, int C, float sigma, int radius, unsigned flags, float* din, void* ws,
                                     size_t ws_bytes, kccot_stream_t stream) {
-    if (flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS))
-        return fail(KCCOT_EINVAL, "smooth_bwd: the stats flags belong to kccot_smooth_bwd_sharded_f32");
-    return smooth_bwd_impl(gout, out, max_in, nullptr, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
+    if (flags & SMOOTH_STATS_FLAGS) return fail(KCCOT_EINVAL, "smooth_bwd: the stats flags belong to kccot_smooth_bwd_sharded_f32");
+    return smooth_bwd_impl(SmoothCall{"smooth_bwd", false, B, H, T, W, C, sigma, radius, flags, ws, ws_bytes, (hipStream_t)stream}, gout, out, max_in,
+                           nullptr, din);
 }
 
 extern "C" int kccot_smooth_bwd_sharded_f32(const float* gout, const float* out, const float* max_in, float* stats_inout,
                                             int B, int H, int T, int W, int C, float sigma, int radius, unsigned flags,
                                             float* din, void* ws, size_t ws_bytes, kccot_stream_t stream) {
-    if (!(flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS)))
+    if (!(flags & SMOOTH_STATS_FLAGS))
         return fail(KCCOT_EINVAL, "smooth_bwd_sharded: give KCCOT_SMOOTH_STATS_ONLY or KCCOT_SMOOTH_EXTERNAL_STATS");
-    return smooth_bwd_impl(gout, out, max_in, stats_inout, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
-}
-
-// ---- the causal 3-D smoothing (include/kccot_smooth_causal3.h; NOT reference behaviour) ----------------------------------------
-//     a = causal T stencil of KCCOT_SMOOTH_CAUSAL_T;  s = H(W(a)) with the symmetric REFLECT stencils;  out = s / max(s)
-// Stage order T, W, H as in the symmetric 3-D call.  Two tiers, dispatched as there: the fused walks (smooth_fused3 /
-// smooth_fused3_adj with CAUSAL) where fused3_plan finds a tiling, else the chain -- smooth_causal in raw mode, the W stage the
-// symmetric chain would pick, the H walk as the last stage (maxima, then s / max), and for every other radius / shape the
-// per-element conv_axis stages around the same smooth_causal.  Backward: the normalisation's adjoint (two-pass or folded), H^T,
-// W^T, then the plain causal T^T (smooth_causal WALK_ADJ) as the last stage.
-static const unsigned SMOOTH3C_PROTOCOL = KCCOT_SMOOTH_NO_DIVIDE | KCCOT_SMOOTH_EXTERNAL_MAX | KCCOT_SMOOTH_STATS_ONLY |
-                                          KCCOT_SMOOTH_EXTERNAL_STATS;
-
-static int smooth3c_check(const char* who, const void* a, const void* b, int B, int H, int T, int W, int C, float sigma,
-                          int radius, unsigned flags) {
-    if (flags & ~SMOOTH3C_PROTOCOL)
-        return fail(KCCOT_EINVAL, "%s: flags 0x%x: the axes are fixed (causal T, symmetric H and W); only NO_DIVIDE, EXTERNAL_MAX, "
-                    "STATS_ONLY and EXTERNAL_STATS are accepted", who, flags);
-    if (!a || !b) return fail(KCCOT_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0)
-        return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", who, B, H, T, W, C);
-    if (!(sigma > 0.f)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", who);
-    if (radius < 0 || radius > SM_MAXR) return fail(KCCOT_EUNSUPPORTED, "%s: radius %d > %d", who, radius, SM_MAXR);
-    // REFLECT padding along H and W needs pad < dim; T has no padding: any radius, radius >= T included
-    if (radius >= H || radius >= W) return fail(KCCOT_EINVAL, "%s: REFLECT padding needs radius < H and radius < W", who);
-    return 0;
-}
-
-// the W stage of the chain: the kernel the symmetric chain would pick, or 0 = none (the per-element stages serve)
-enum { W3C_NONE = 0, W3C_W1 = 1, W3C_PLANE = 2, W3C_ROW = 3 };
-static int smooth3c_wstage(int T, int W, int C, int radius, const void* a, const void* b) {
-    if (w1_eligible(W, C, radius, a, b) && !smooth_generic()) return W3C_W1;
-    if (plane_eligible(T, W, C, radius, 1) && !smooth_generic()) return W3C_PLANE;
-    if (wrow_eligible(W, C, radius)) return W3C_ROW;
-    return W3C_NONE;
-}
-
-static int smooth3c_launch_w(int kind, const float* in, float* out, const float* out_fwd, float* one, int64_t n, int B, int H, int T,
-                             int W, int C, int radius, bool adjoint, const Taps& tp, hipStream_t st) {
-    if (kind == W3C_W1) return launch_w1(in, out, n, W, radius, adjoint, tp, st);
-    if (kind == W3C_ROW) return launch_wrow(in, out, n, W, C, radius, adjoint, tp, st);
-    int rc;
-    hipLaunchKernelGGL(set_unit_scalars, dim3(1), dim3(1), 0, st, one);
-    if ((rc = launch_status("set_unit_scalars"))) return rc;
-    PlaneArgs pa{};
-    pa.in = in; pa.out_fwd = out_fwd; pa.out = out; pa.mx = one; pa.res = one + 1;     // max = 1, no ties: the plain stencil
-    pa.B = B; pa.H = H; pa.T = T; pa.W = W; pa.C = C; pa.axes = KCCOT_SMOOTH_W; pa.tp = tp; pa.hseg = plane_hseg(B, H, false);
-    return launch_plane(pa, radius, adjoint, dim3((H + pa.hseg - 1) / pa.hseg, B), st);
+    return smooth_bwd_impl(SmoothCall{"smooth_bwd", false, B, H, T, W, C, sigma, radius, flags, ws, ws_bytes, (hipStream_t)stream}, gout, out, max_in,
+                           stats_inout, din);
 }
 
 extern "C" int kccot_smooth_causal3_fwd_f32(const float* in, int B, int H, int T, int W, int C, float sigma, int radius,
                                             unsigned flags, float* out, float* max_inout, void* ws, size_t ws_bytes,
                                             kccot_stream_t stream) {
-    const char* who = "kccot_smooth_causal3_fwd_f32";
-    int rc = smooth3c_check(who, in, out, B, H, T, W, C, sigma, radius, flags);
-    if (rc) return rc;
-    if (!max_inout) return fail(KCCOT_EINVAL, "%s: null max pointer", who);
-    const bool ext = (flags & KCCOT_SMOOTH_EXTERNAL_MAX) != 0, nodiv = (flags & KCCOT_SMOOTH_NO_DIVIDE) != 0;
-    if (ext && nodiv) return fail(KCCOT_EINVAL, "%s: EXTERNAL_MAX and NO_DIVIDE are exclusive", who);
-    if (in == out) return fail(KCCOT_EINVAL, "%s: in-place convolution is not supported", who);
-    const size_t need = kccot_smooth_workspace_bytes(B, H, T, W, C);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", who, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = (int64_t)B * H * T * W * C, WC = (int64_t)W * C;
-    const int64_t nb = (n + 255) / 256;
-    if (nb > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", who);
-    float* tmp = static_cast<float*>(ws);
-    float* bmax = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256));
-    float* one = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256) + 2 * smooth_blk_bytes(n));
-    const Taps tp = make_taps(sigma, radius);
-    const CausalTaps ct = make_causal_taps(sigma, radius);
-    const bool r34 = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM);
-    // (NO_DIVIDE and EXTERNAL_MAX take the same tier and the same kernels as the one-call form: see kccot_smooth_fwd_f32)
-    if (r34) {
-        const Fused3Plan fp = fused3_plan(B, H, T, W, C, radius, in, out);
-        if (fp.ok) {
-            Fused3Args fa{};
-            fa.in = in; fa.H = H; fa.T = T; fa.W = W; fa.wt = fp.wt; fa.ntw = W / fp.wt; fa.hseg = fp.hseg;
-            fa.nseg = (H + fp.hseg - 1) / fp.hseg; fa.tp = tp; fa.ct = ct;
-            if (!ext) {
-                fa.mode = 0; fa.blockmax = bmax;
-                if ((rc = launch_fused3(fp, fa, radius, C, st, true))) return rc;
-                if (!nodiv && fp.grid <= 4096) {
-                    fa.nblk = (int)fp.grid;       // the writing pass reduces the maxima itself (and stores the maximum)
-                } else {
-                    hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, fp.grid, max_inout);
-                    if ((rc = launch_status("reduce_blockmax"))) return rc;
-                }
-            }
-            fa.mode = nodiv ? 2 : 1; fa.out = out; fa.mx = max_inout; fa.mx_out = max_inout;
-            return launch_fused3(fp, fa, radius, C, st, true);
-        }
-    }
-    // T: in -> out (raw sums times 1 / Z_t)
-    CausalArgs ca{};
-    ca.ct = ct; ca.in = in; ca.out = out; ca.T = T; ca.S = WC;
-    if ((rc = launch_causal(WALK_RAW, ca, radius, n, causal_vw(WC, in, out, out), st))) return rc;
-    const AxisPlan ph = r34 ? axis_plan(H, (int64_t)T * WC, false, false, radius, tmp, out, out) : AxisPlan{AXIS_NONE, WalkPlan{0, 0}, 0};
-    const int wk = r34 ? smooth3c_wstage(T, W, C, radius, out, tmp) : W3C_NONE;
-    if (ph.kind != AXIS_NONE && wk != W3C_NONE) {
-        // W: out -> tmp (raw);  H: tmp -> maxima, then tmp -> out (s / max, or s)
-        if ((rc = smooth3c_launch_w(wk, out, tmp, nullptr, one, n, B, H, T, W, C, radius, false, tp, st))) return rc;
-        WalkArgs wa{};
-        wa.tp = tp; wa.in = tmp; wa.L = H; wa.S = (int64_t)T * WC;
-        const int64_t last_wgs = (n / H / ph.vw + 255) / 256;
-        if (!ext) {
-            wa.blockmax = bmax;
-            if ((rc = launch_axis(WALK_MAX, wa, radius, n, ph, st))) return rc;
-            if (!nodiv && last_wgs <= 4096) {
-                wa.nblk = (int)last_wgs;
-            } else {
-                hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, last_wgs, max_inout);
-                if ((rc = launch_status("reduce_blockmax"))) return rc;
-            }
-        }
-        wa.out = out; wa.mx = max_inout; wa.mx_out = max_inout;
-        if (wa.nblk == 0) wa.blockmax = nullptr;
-        return launch_axis(nodiv ? WALK_RAW : WALK_WRITE, wa, radius, n, ph, st);
-    }
-    // any radius, any shape: W out -> tmp, H tmp -> out per element, the maximum, the division in place
-    hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)out, tmp, n, W, (int64_t)C, tp, 0, (float*)nullptr);
-    if ((rc = launch_status("conv_axis"))) return rc;
-    hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)tmp, out, n, H, (int64_t)T * WC, tp, 0,
-                       ext ? (float*)nullptr : bmax);
-    if ((rc = launch_status("conv_axis"))) return rc;
-    if (!ext) {
-        hipLaunchKernelGGL(reduce_blockmax, dim3(1), dim3(1024), 0, st, (const float*)bmax, nb, max_inout);
-        if ((rc = launch_status("reduce_blockmax"))) return rc;
-    }
-    if (!nodiv) {
-        hipLaunchKernelGGL(divide_by, dim3((unsigned)nb), dim3(256), 0, st, (const float*)out, out, n, (const float*)max_inout);
-        if ((rc = launch_status("divide_by"))) return rc;
-    }
-    return 0;
+    return smooth_fwd_impl(SmoothCall{"kccot_smooth_causal3_fwd_f32", true, B, H, T, W, C, sigma, radius, flags, ws, ws_bytes, (hipStream_t)stream}, in,
+                           out, max_inout);
 }
 
-static int smooth3c_bwd_impl(const char* who, const float* gout, const float* out, const float* max_in, float* stats_ext, int B,
-                             int H, int T, int W, int C, float sigma, int radius, unsigned flags, float* din, void* ws,
-                             size_t ws_bytes, kccot_stream_t stream) {
-    const bool stats_only = (flags & KCCOT_SMOOTH_STATS_ONLY) != 0, stats_in = (flags & KCCOT_SMOOTH_EXTERNAL_STATS) != 0;
-    int rc = smooth3c_check(who, gout, stats_only ? const_cast<float*>(gout) : din, B, H, T, W, C, sigma, radius, flags);
-    if (rc) return rc;
-    if (stats_only && stats_in) return fail(KCCOT_EINVAL, "%s: STATS_ONLY and EXTERNAL_STATS are exclusive", who);
-    if ((stats_only || stats_in) && !stats_ext) return fail(KCCOT_EINVAL, "%s: null stats pointer", who);
-    if (!out || !max_in) return fail(KCCOT_EINVAL, "%s: null pointer", who);
-    const size_t need = kccot_smooth_workspace_bytes(B, H, T, W, C);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", who, ws_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = (int64_t)B * H * T * W * C, WC = (int64_t)W * C;
-    const int64_t nb = (n + 255) / 256;
-    if (nb > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", who);
-    float* tmp = static_cast<float*>(ws);
-    char* p = static_cast<char*>(ws) + align_up((size_t)n * sizeof(float), 256);
-    float* pdot = reinterpret_cast<float*>(p);
-    float* pcnt = reinterpret_cast<float*>(p + smooth_blk_bytes(n));
-    float* res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n));
-    float* scal = res;                                      // workspace scalars {dot, ties, .., .., 1, 0, 0, dense}
-    TieRec* recs = reinterpret_cast<TieRec*>(p + 2 * smooth_blk_bytes(n) + 256);
-    const Taps tp = make_taps(sigma, radius);
-    const CausalTaps ct = make_causal_taps(sigma, radius);
-    const bool wide = (n % 4 == 0) && ((uintptr_t)gout % 16 == 0) && ((uintptr_t)out % 16 == 0) && nb >= 2048;
-    const int64_t nparts = wide ? 2048 : nb;
-    const bool r34 = (radius == 3 || radius == 4) && opt(OPT_SMOOTH_STREAM);
-    // the streaming chain: H^T (+ the normalisation's adjoint) gout -> din, W^T din -> tmp, causal T^T tmp -> din
-    AxisPlan ph{AXIS_NONE, WalkPlan{0, 0}, 0};
-    int wk = W3C_NONE;
-    if (r34 && !stats_only) {
-        ph = axis_plan(H, (int64_t)T * WC, true, true, radius, gout, out, din);
-        wk = smooth3c_wstage(T, W, C, radius, din, tmp);
-    }
-    const bool chain = ph.kind != AXIS_NONE && wk != W3C_NONE;
-    const int vwt = causal_vw(WC, tmp, din, din);
-    const int fold_opt = opt(OPT_SMOOTH_BWD_FOLD);
-    Fused3Plan fpa{};
-    if (chain && (stats_in || fold_opt != 0) && ((uintptr_t)out & 15) == 0) fpa = fused3_plan(B, H, T, W, C, radius, gout, din, true, !stats_in);
-    // one TieRec per workgroup of the stage that reads gout: where the H walk's grid would not fit the records of the workspace
-    // the two-pass form runs whatever the option says (fused3_plan never returns a tiling that does not fit)
-    int nrec = chain ? (int)((n / H / ph.vw + 255) / 256) : 0;
-    const bool fold = chain && !stats_in && (fold_opt == 2 || fpa.ok || (fold_opt == 1 && n >= ((int64_t)1 << 25))) &&
-                      (fpa.ok || nrec <= tie_rec_capacity(n));
-    if (fold) {     // no per-block partial sums: the records start at the per-block arrays, the scalars sit behind the records
-        recs = reinterpret_cast<TieRec*>(p);
-        scal = res = reinterpret_cast<float*>(p + 2 * smooth_blk_bytes(n) + smooth_rec_bytes(n));
-    }
-    Fused3AdjArgs fx{};
-    if (fpa.ok) {
-        fx.gout = gout; fx.out_fwd = out; fx.din = din; fx.mx = max_in; fx.H = H; fx.T = T; fx.W = W; fx.wt = fpa.wt;
-        fx.ntw = W / fpa.wt; fx.hseg = fpa.hseg; fx.nseg = (H + fpa.hseg - 1) / fpa.hseg; fx.tp = tp; fx.ct = ct;
-    }
-    if (stats_in && fpa.ok) {       // the batch-sharded caller: sums handed in, correction applied at the loads, nothing to fix up
-        fx.res = stats_ext;
-        return launch_fused3_adj(fpa, fx, C, true, st, true);
-    }
-    if (stats_in) {
-        res = stats_ext;
-    } else if (!fold) {
-        if (stats_only) res = stats_ext;
-        if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, pdot, pcnt);
-        else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, pdot, pcnt);
-        if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
-        hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)pdot, (const float*)pcnt, nparts, res);
-        if ((rc = launch_status("maxnorm_bwd_combine"))) return rc;
-        if (stats_only) return 0;
-    }
-    CausalArgs ca{};
-    ca.ct = ct; ca.in = tmp; ca.out = din; ca.T = T; ca.S = WC;
-    if (!chain) {
-        // any radius, any shape: the normalisation's adjoint gout -> tmp, H^T tmp -> din, W^T din -> tmp per element, causal T^T
-        hipLaunchKernelGGL(maxnorm_bwd_apply, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, max_in, (const float*)res, tmp);
-        if ((rc = launch_status("maxnorm_bwd_apply"))) return rc;
-        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)tmp, din, n, H, (int64_t)T * WC, tp, 1, (float*)nullptr);
-        if ((rc = launch_status("conv_axis(adjoint)"))) return rc;
-        hipLaunchKernelGGL(conv_axis, dim3((unsigned)nb), dim3(256), 0, st, (const float*)din, tmp, n, W, (int64_t)C, tp, 1, (float*)nullptr);
-        if ((rc = launch_status("conv_axis(adjoint)"))) return rc;
-        return launch_causal(WALK_ADJ, ca, radius, n, vwt, st);
-    }
-    if (fold && fpa.ok) {           // all three adjoint stages in one pass, the statistics gathered on the way
-        fx.ties = recs;
-        if ((rc = launch_fused3_adj(fpa, fx, C, false, st, true))) return rc;
-        nrec = (int)fpa.grid;
-    } else {
-        WalkArgs wa{};
-        wa.tp = tp; wa.out_fwd = out; wa.mx = max_in; wa.res = res; wa.ties = recs;
-        wa.in = gout; wa.out = din; wa.L = H; wa.S = (int64_t)T * WC;
-        if ((rc = launch_axis(fold ? WALK_ADJS : WALK_ADJX, wa, radius, n, ph, st))) return rc;
-        if ((rc = smooth3c_launch_w(wk, din, tmp, out, scal + 4, n, B, H, T, W, C, radius, true, tp, st))) return rc;
-        if ((rc = launch_causal(WALK_ADJ, ca, radius, n, vwt, st))) return rc;
-    }
-    if (!fold) return 0;
-    // behind the folded first stage: the sparse fix-up, then the dense form that only runs when it found too many arg-max elements
-    int* dense = reinterpret_cast<int*>(scal + 7);
-    FixupArgs fa{};
-    fa.ties = recs; fa.nrec = nrec; fa.mx = max_in; fa.res = res; fa.dense = dense; fa.din = din; fa.na = 3; fa.tp = tp;
-    fa.len[0] = T; fa.stride[0] = WC; fa.len[1] = H; fa.stride[1] = (int64_t)T * WC; fa.len[2] = W; fa.stride[2] = C;
-    fa.causal = 1; fa.ct = ct;
-    hipLaunchKernelGGL(maxnorm_bwd_fixup, dim3(1), dim3(1024), 0, st, fa);
-    if ((rc = launch_status("maxnorm_bwd_fixup"))) return rc;
-    if (fpa.ok) {
-        fx.ties = nullptr; fx.res = res; fx.run_if = dense;
-        return launch_fused3_adj(fpa, fx, C, true, st, true);
-    }
-    WalkArgs wd{};
-    wd.tp = tp; wd.out_fwd = out; wd.mx = max_in; wd.res = res; wd.run_if = dense;
-    wd.in = gout; wd.out = din; wd.L = H; wd.S = (int64_t)T * WC;
-    if ((rc = launch_axis(WALK_ADJX, wd, radius, n, ph, st))) return rc;
-    hipLaunchKernelGGL(conv_axis_adjoint_if, dim3((unsigned)std::min<int64_t>(nb, 2048)), dim3(256), 0, st, (const float*)din, tmp, n,
-                       W, (int64_t)C, tp, (const int*)dense);
-    if ((rc = launch_status("conv_axis_adjoint_if"))) return rc;
-    ca.run_if = dense;
-    return launch_causal(WALK_ADJ, ca, radius, n, vwt, st);
-}
-
+// (an axis bit or an unknown one is reported by the argument check, ahead of a misplaced stats flag)
 extern "C" int kccot_smooth_causal3_bwd_f32(const float* gout, const float* out, const float* max_in, int B, int H, int T,
                                             int W, int C, float sigma, int radius, unsigned flags, float* din, void* ws,
                                             size_t ws_bytes, kccot_stream_t stream) {
     const char* who = "kccot_smooth_causal3_bwd_f32";
-    if ((flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS)) && !(flags & ~SMOOTH3C_PROTOCOL))
+    if ((flags & SMOOTH_STATS_FLAGS) && !(flags & ~SMOOTH3C_PROTOCOL))
         return fail(KCCOT_EINVAL, "%s: the stats flags belong to kccot_smooth_causal3_bwd_sharded_f32", who);
-    return smooth3c_bwd_impl(who, gout, out, max_in, nullptr, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
+    return smooth_bwd_impl(SmoothCall{who, true, B, H, T, W, C, sigma, radius, flags, ws, ws_bytes, (hipStream_t)stream}, gout, out, max_in, nullptr, din);
 }
 
 extern "C" int kccot_smooth_causal3_bwd_sharded_f32(const float* gout, const float* out, const float* max_in,
@@ -2931,7 +2792,7 @@ extern "C" int kccot_smooth_causal3_bwd_sharded_f32(const float* gout, const flo
                                                     int radius, unsigned flags, float* din, void* ws, size_t ws_bytes,
                                                     kccot_stream_t stream) {
     const char* who = "kccot_smooth_causal3_bwd_sharded_f32";
-    if (!(flags & (KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS)) && !(flags & ~SMOOTH3C_PROTOCOL))
+    if (!(flags & SMOOTH_STATS_FLAGS) && !(flags & ~SMOOTH3C_PROTOCOL))
         return fail(KCCOT_EINVAL, "%s: give KCCOT_SMOOTH_STATS_ONLY or KCCOT_SMOOTH_EXTERNAL_STATS", who);
-    return smooth3c_bwd_impl(who, gout, out, max_in, stats_inout, B, H, T, W, C, sigma, radius, flags, din, ws, ws_bytes, stream);
+    return smooth_bwd_impl(SmoothCall{who, true, B, H, T, W, C, sigma, radius, flags, ws, ws_bytes, (hipStream_t)stream}, gout, out, max_in, stats_inout, din);
 }
