@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include "../../include/kccot.h"
 #include "../../include/kccot_weighted.h"
+#include "../../include/kccot_conditional.h"
 
 #define KCCOT_WAVE 64
 
@@ -152,6 +153,17 @@ int sinkhorn_divergence_weighted_fwd(const float* C3, const float* w_real, const
 int sinkhorn_divergence_weighted_bwd(const float* C3, const float* w_real, const float* w_fake, const float* u_hist,
                                      const float* v_hist, const int32_t* nits, int n, float eps, int L, const float* gloss,
                                      float* gc3, float* dC3, void* ws, size_t ws_bytes, hipStream_t st);
+
+// sinkhorn.hip: the 3 Q solves / reverse sweeps of the conditional loss (kccot_conditional.h) on ONE shared C3 [3,n,n]:
+// problem p = 3 q + k reads cost matrix k and weight row q of w [Q,n]; histories, costs, counts, gcost [3 Q] and dC
+// [3 Q,n,n] are indexed by p.  ws (n > 128 only): sinkhorn_gen_conditional_workspace_bytes(Q, n) bytes (sinkhorn_gen.hip).
+size_t sinkhorn_gen_conditional_workspace_bytes(int Q, int n);
+int sinkhorn_conditional_solve_fwd(const float* C3, const float* w, int Q, int n, float eps, int L, int Lmin, float thresh,
+                                   float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, void* ws,
+                                   size_t ws_bytes, hipStream_t st);
+int sinkhorn_conditional_solve_bwd(const float* C3, const float* w, const float* u_hist, const float* v_hist,
+                                   const int32_t* nits, int Q, int n, float eps, int L, const float* gcost, float* dC,
+                                   void* ws, size_t ws_bytes, hipStream_t st);
 
 // cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) over the whole batch.  bicausal selects the
 // feature-gradient jobs of the bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake,

@@ -73,6 +73,8 @@ struct SinkArgs {
     // weighted marginals (the _w kernels only; an extension, not reference behaviour): strictly positive finite weights,
     // log taken once per lane before the loop.  w_div = 0: wa, wb are [nprob,n], problem p reads row p.  w_div = 1: wa =
     // w_real [n], wb = w_fake [n] and the three problems of the divergence read (a,b), (a,a), (b,b).  NULL: mu = nu = 1/n.
+    // w_div = 2 (conditional mode, include/kccot_conditional.h): C is ONE shared C3 [3,n,n], wa = wb = w [Q,n]; problem
+    // p = 3 q + k reads cost matrix k and weight row q for both marginals, everything else stays indexed by p.
     const float* wa;
     const float* wb;
     int w_div;
@@ -80,6 +82,7 @@ struct SinkArgs {
 
 // the marginal weights of problem p (see SinkArgs::wa)
 __device__ __forceinline__ const float* weights_of(const float* wa, const float* wb, int w_div, int p, int n, bool rows) {
+    if (w_div == 2) return wa + (int64_t)(p / 3) * n;
     if (w_div) return rows ? (p == 2 ? wb : wa) : (p == 1 ? wa : wb);
     return (rows ? wa : wb) + (int64_t)p * n;
 }
@@ -177,7 +180,9 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, line = t / LPR, q = t % LPR;
     const bool active = line < n;
-    const float* C = a.C + (int64_t)p * n * n;
+    int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
+    if constexpr (WEIGHTED) { if (a.w_div == 2) pc = p % 3; }
+    const float* C = a.C + (int64_t)pc * n * n;
     const float k2 = a.inv_eps * LOG2E;
 
     float crow[EPT], ccol[EPT];
@@ -411,7 +416,7 @@ struct SinkBwdArgs {
     int n, L;
     float eps, inv_eps;
     int div_weights;      // 1: gcost[p] = {2,-1,-1}[p] * gcost[0]   (d(2 xy - xx - yy), gan_utils.py:225)
-    const float* wa;      // weighted marginals as in SinkArgs (sinkhorn_bwd_reg_w only)
+    const float* wa;      // weighted marginals as in SinkArgs (sinkhorn_bwd_reg_w only); w_div = 2: C is the shared C3
     const float* wb;
     int w_div;
 };
@@ -436,7 +441,9 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, line = t / LPR, q = t % LPR;
     const bool active = line < n;
-    const float* C = a.C + (int64_t)p * n * n;
+    int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
+    if constexpr (WEIGHTED) { if (a.w_div == 2) pc = p % 3; }
+    const float* C = a.C + (int64_t)pc * n * n;
     const float k2 = a.inv_eps * LOG2E;
     const float g = a.div_weights ? (p == 0 ? 2.0f : -1.0f) * a.gcost[0] : a.gcost[p];
     const int nits = a.nits[p];
@@ -966,7 +973,8 @@ static int sinkhorn_fwd(const float* C, int nprob, int n, float eps, int L, int 
                         const float* wa = nullptr, const float* wb = nullptr, int w_div = 0) {
     if (!C || !cost_out || !nits_out) return fail(KCCOT_EINVAL, "sinkhorn_fwd: null pointer");
     if ((wa == nullptr) != (wb == nullptr)) return fail(KCCOT_EINVAL, "sinkhorn_fwd: give both weight vectors or neither");
-    if (w_div && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_fwd: the divergence's weights need nprob = 3");
+    if (w_div == 1 && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_fwd: the divergence's weights need nprob = 3");
+    if (w_div == 2 && nprob % 3) return fail(KCCOT_EINVAL, "sinkhorn_fwd: the conditional mode needs nprob = 3 Q");
     if (nprob <= 0 || n <= 0 || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "sinkhorn_fwd: bad arguments nprob=%d n=%d L=%d eps=%g", nprob, n, L, (double)eps);
     if ((u_hist == nullptr) != (v_hist == nullptr))
@@ -1030,7 +1038,8 @@ static int sinkhorn_bwd(const float* C, const float* u_hist, const float* v_hist
     if (!C || !u_hist || !v_hist || !nits || !gcost || !dC_out)
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: null pointer");
     if ((wa == nullptr) != (wb == nullptr)) return fail(KCCOT_EINVAL, "sinkhorn_bwd: give both weight vectors or neither");
-    if (w_div && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_bwd: the divergence's weights need nprob = 3");
+    if (w_div == 1 && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_bwd: the divergence's weights need nprob = 3");
+    if (w_div == 2 && nprob % 3) return fail(KCCOT_EINVAL, "sinkhorn_bwd: the conditional mode needs nprob = 3 Q");
     if (nprob <= 0 || n <= 0 || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: bad arguments nprob=%d n=%d L=%d eps=%g", nprob, n, L, (double)eps);
     if (n > SK_MAXN)
@@ -1219,4 +1228,21 @@ int kccot::sinkhorn_divergence_weighted_bwd(const float* C3, const float* w_real
         return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gc3, dC3, ws, ws_bytes, st, 0, w_real, w_fake, 1);
     }
     return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3, ws, ws_bytes, st, 1, w_real, w_fake, 1);
+}
+
+// ---- conditional mode (include/kccot_conditional.h, conditional.hip) ------------------------------------------------------
+// The 3 Q solves / reverse sweeps of the kernel-conditional loss on ONE shared C3 [3,n,n]: the weighted kernels with
+// w_div = 2, one workgroup per problem p = 3 q + k.  No in-kernel combination (conditional.hip combines in a fixed order).
+int kccot::sinkhorn_conditional_solve_fwd(const float* C3, const float* w, int Q, int n, float eps, int L, int Lmin,
+                                          float thresh, float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out,
+                                          void* ws, size_t ws_bytes, hipStream_t st) {
+    return sinkhorn_fwd(C3, 3 * Q, n, eps, L, Lmin, thresh, KCCOT_STOP_COUNT, u_hist, v_hist, cost_out, nits_out, nullptr, ws,
+                        ws_bytes, st, nullptr, nullptr, w, w, 2);
+}
+
+// gcost [3 Q]: the upstream gradient of every problem's cost; dC [3 Q,n,n]: the per-problem gradients
+int kccot::sinkhorn_conditional_solve_bwd(const float* C3, const float* w, const float* u_hist, const float* v_hist,
+                                          const int32_t* nits, int Q, int n, float eps, int L, const float* gcost, float* dC,
+                                          void* ws, size_t ws_bytes, hipStream_t st) {
+    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3 * Q, n, eps, L, gcost, dC, ws, ws_bytes, st, 0, w, w, 2);
 }

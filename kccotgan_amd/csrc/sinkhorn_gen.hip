@@ -85,13 +85,15 @@ struct SinkGenArgs {
     float* pi_out;
     // weighted marginals (the <true> instantiations only; an extension, not reference behaviour).  w_div = 0: wa, wb are
     // [nprob,n], problem p reads row p; w_div = 1: wa = w_real [n], wb = w_fake [n] and the three problems of the
-    // divergence read (a,b), (a,a), (b,b).  NULL: mu = nu = 1/n.
+    // divergence read (a,b), (a,a), (b,b).  NULL: mu = nu = 1/n.  w_div = 2 (conditional mode, kccot_conditional.h): C and
+    // CT are ONE shared [3,n,n] each, wa = wb = w [Q,n]; problem p = 3 q + k reads matrix k and weight row q.
     const float* wa;
     const float* wb;
     int w_div;
 };
 
 __device__ __forceinline__ const float* gen_weights_of(const float* wa, const float* wb, int w_div, int p, int n, bool rows) {
+    if (w_div == 2) return wa + (int64_t)(p / 3) * n;
     if (w_div) return rows ? (p == 2 ? wb : wa) : (p == 1 ? wa : wb);
     return (rows ? wa : wb) + (int64_t)p * n;
 }
@@ -118,8 +120,10 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen(SinkGenArgs a) {
     __shared__ float la_s[W ? SG_MAXN : 1], lb_s[W ? SG_MAXN : 1];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
-    const float* C = a.C + (int64_t)p * n * n;
-    const float* CT = a.CT + (int64_t)p * n * n;
+    int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
+    if constexpr (W) { if (a.w_div == 2) pc = p % 3; }
+    const float* C = a.C + (int64_t)pc * n * n;
+    const float* CT = a.CT + (int64_t)pc * n * n;
     const float eps = a.eps, inv_eps = a.inv_eps;
     for (int i = t; i < n; i += SG_THREADS) { u_s[i] = 0.f; v_s[i] = 0.f; }
     __syncthreads();
@@ -235,8 +239,10 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen4(SinkGenArgs a) {
     __shared__ float red[16];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
-    const float* C = a.C + (int64_t)p * n * n;
-    const float* CT = a.CT + (int64_t)p * n * n;
+    int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
+    if constexpr (W) { if (a.w_div == 2) pc = p % 3; }
+    const float* C = a.C + (int64_t)pc * n * n;
+    const float* CT = a.CT + (int64_t)pc * n * n;
     const float eps = a.eps, inv_eps = a.inv_eps;
     for (int i = t; i < SG_MAXN; i += SG_THREADS) { u_s[i] = 0.f; v_s[i] = 0.f; }
     __syncthreads();
@@ -349,8 +355,10 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_fwd_gen16(SinkGenArgs a) 
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
     const int q = lane & 15, sub = lane >> 4;
-    const float* C = a.C + (int64_t)p * n * n;
-    const float* CT = a.CT + (int64_t)p * n * n;
+    int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
+    if constexpr (W) { if (a.w_div == 2) pc = p % 3; }
+    const float* C = a.C + (int64_t)pc * n * n;
+    const float* CT = a.CT + (int64_t)pc * n * n;
     const float eps = a.eps, inv_eps = a.inv_eps;
     for (int i = t; i < SG_MAXN; i += SG_THREADS) { u_s[i] = 0.f; v_s[i] = 0.f; }
     __syncthreads();
@@ -452,8 +460,10 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
     __shared__ float ea_s[W ? SG_MAXN : 1], eb_s[W ? SG_MAXN : 1];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
-    const float* C = a.C + (int64_t)p * n * n;
-    const float* CT = a.CT + (int64_t)p * n * n;
+    int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
+    if constexpr (W) { if (a.w_div == 2) pc = p % 3; }
+    const float* C = a.C + (int64_t)pc * n * n;
+    const float* CT = a.CT + (int64_t)pc * n * n;
     float* dC = a.dC + (int64_t)p * n * n;
     float* dCT = a.dCT + (int64_t)p * n * n;
     const float eps = a.eps, inv_eps = a.inv_eps, g = a.gcost[p];
@@ -541,6 +551,11 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
 size_t sinkhorn_gen_workspace_bytes(int nprob, int n) {
     return 2 * align_up((size_t)nprob * n * n * sizeof(float), 256);
 }
+// conditional mode: the transposed copy of the shared C3 [3,n,n], then the column-pass accumulators of the 3 Q problems
+static size_t gen_cond_ct_bytes(int n) { return align_up((size_t)3 * n * n * sizeof(float), 256); }
+size_t sinkhorn_gen_conditional_workspace_bytes(int Q, int n) {
+    return gen_cond_ct_bytes(n) + align_up((size_t)3 * Q * n * n * sizeof(float), 256);
+}
 
 // sinkhorn_coop.hip
 constexpr int SK_COOP_MAX_L = 500000;
@@ -555,13 +570,13 @@ int launch_sinkhorn_fwd_gen(const float* C, int nprob, int n, float eps, int L, 
                             float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* pi_out, void* ws,
                             size_t ws_bytes, hipStream_t st, const float* wa, const float* wb, int w_div) {
     if (n > SG_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fwd: n=%d > %d", n, SG_MAXN);
-    const size_t need = sinkhorn_gen_workspace_bytes(nprob, n);
+    const size_t need = w_div == 2 ? sinkhorn_gen_conditional_workspace_bytes(nprob / 3, n) : sinkhorn_gen_workspace_bytes(nprob, n);
     if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "sinkhorn_fwd: workspace %zu < required %zu", ws_bytes, need);
     // (the multi-CU solver is not weighted: weighted solves stay on the single-workgroup kernels below)
     if (!wa && sinkhorn_coop_eligible(nprob, n) && L < SK_COOP_MAX_L)     // the exchange tags hold 2 L + 2 half-steps in 20 bits
         return launch_sinkhorn_fwd_coop(C, nprob, n, eps, L, Lmin, thresh, stop_mode, u_hist, v_hist, cost_out, nits_out, pi_out, ws, st);
     float* CT = static_cast<float*>(ws);
-    dim3 tg((n + 31) / 32, (n + 31) / 32, nprob);
+    dim3 tg((n + 31) / 32, (n + 31) / 32, w_div == 2 ? 3 : nprob);      // conditional mode: the shared C3, once
     hipLaunchKernelGGL(transpose_batched, tg, dim3(256), 0, st, C, CT, n);
     int rc = launch_status("transpose_batched");
     if (rc) return rc;
@@ -586,14 +601,15 @@ int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_
                             float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st,
                             const float* wa, const float* wb, int w_div) {
     if (n > SG_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_bwd: n=%d > %d", n, SG_MAXN);
-    const size_t need = sinkhorn_gen_workspace_bytes(nprob, n);
+    const size_t need = w_div == 2 ? sinkhorn_gen_conditional_workspace_bytes(nprob / 3, n) : sinkhorn_gen_workspace_bytes(nprob, n);
     if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "sinkhorn_bwd: workspace %zu < required %zu", ws_bytes, need);
     if (!wa && sinkhorn_coop_eligible(nprob, n) && L < SK_COOP_MAX_L)     // the exchange tags hold 2 L + 2 half-steps in 20 bits
         return launch_sinkhorn_bwd_coop(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC, ws, st);
     float* CT = static_cast<float*>(ws);
-    float* dCT = reinterpret_cast<float*>(static_cast<char*>(ws) + need / 2);
+    float* dCT = reinterpret_cast<float*>(static_cast<char*>(ws) + (w_div == 2 ? gen_cond_ct_bytes(n) : need / 2));
     dim3 tg((n + 31) / 32, (n + 31) / 32, nprob);
-    hipLaunchKernelGGL(transpose_batched, tg, dim3(256), 0, st, C, CT, n);
+    dim3 tc((n + 31) / 32, (n + 31) / 32, w_div == 2 ? 3 : nprob);      // conditional mode: the shared C3, once
+    hipLaunchKernelGGL(transpose_batched, tc, dim3(256), 0, st, C, CT, n);
     int rc = launch_status("transpose_batched");
     if (rc) return rc;
     SinkGenBwdArgs a{C, CT, u_hist, v_hist, nits, gcost, dC, dCT, n, L, eps, (float)(1.0 / (double)eps), wa, wb, w_div};

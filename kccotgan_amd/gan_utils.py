@@ -18,7 +18,8 @@ from ._lib import lib, check, ptr, stream_of, workspace
 __all__ = ["cost_xy", "modified_cost", "bi_causal_modified_cost", "benchmark_sinkhorn",
            "compute_sinkhorn", "compute_N", "scale_invariante_martingale_regularization",
            "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "compute_bicausal_sinkhorn_loss",
-           "compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
+           "compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss", "kernel_conditional_weights",
+           "compute_conditional_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
 
 # executed Sinkhorn iteration counts (device int32 tensors, no host sync) of the latest calls;
 # the reference keeps them in a local (gan_utils.py:148,158) although its docstring promises them
@@ -507,6 +508,70 @@ class _WeightedSinkhornLoss(torch.autograd.Function):
         return (None,) * 8 + (dfake, *dfeats)
 
 
+class _ConditionalSinkhornLoss(torch.autograd.Function):
+    """The kernel-conditional loss as ONE library call each way (kccot_conditional_sinkhorn_loss_fwd_f32 / _bwd_f32),
+    modelled on _WeightedSinkhornLoss: w [Q,B] weight rows, omega [Q] query weights or None (1/Q)."""
+
+    @staticmethod
+    def forward(ctx, tag, sc, eps, L, Lmin, w, omega, real, fake, *feats):
+        B, K = real.shape
+        Q = w.shape[0]
+        if fake.shape != real.shape:
+            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        for t in feats:
+            if t.shape != (B, T, J):
+                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
+        need = ctx.needs_input_grad[7:]                                             # real, fake, *feats
+        if need[0]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+        dev = real.device
+        keep = any(need[1:])
+        Lh = max(int(L), 1)
+        nc, nh = _pad64(3 * B * B), _pad64(3 * Q * Lh * B)
+        small = _lib.empty((3 * Q + 1,), torch.float32, dev)                         # costs [Q,3] | loss
+        nits = _lib.empty((6 * Q,), torch.int32, dev)       # [reference-equivalent counts | iterations executed], [Q,3] each
+        st = stream_of(real)
+        ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q), real, st)
+        state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)      # C3 | u_hist | v_hist
+        uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
+        loss = small[3 * Q:]
+        check(lib.kccot_conditional_sinkhorn_loss_fwd_f32(
+            ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
+            ptr(w), ptr(omega), Q, ptr(state), uh, vh, ptr(small), ptr(nits), ptr(loss), ws, wsb, st),
+            "conditional_sinkhorn_loss_fwd")
+        last_info[tag], last_info[tag + "_executed"] = nits[:3 * Q].view(Q, 3), nits[3 * Q:].view(Q, 3)
+        last_info[tag + "_costs"] = small[:3 * Q].view(Q, 3)
+        last_info[tag + "_C3"] = state[:3 * B * B].view(3, B, B)
+        last_info[tag + "_fused_sweep"] = False
+        last_info[tag + "_path"] = _weighted_path(B)
+        if keep:
+            ctx.save_for_backward(real, fake, *feats, w, omega, state, nits)
+        ctx.cfg = (float(sc), float(eps), Lh)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        real, fake, *feats, w, omega, state, nits = ctx.saved_tensors
+        sc, eps, Lh = ctx.cfg
+        B, K = real.shape
+        Q = w.shape[0]
+        T, J = feats[0].shape[1], feats[0].shape[2]
+        nc, nh = _pad64(3 * B * B), _pad64(3 * Q * Lh * B)
+        need = ctx.needs_input_grad[8:]                                             # fake, *feats
+        g = g.reshape(1).contiguous().float()
+        dfake = _lib.empty_like(fake) if need[0] else None
+        df = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[1:]) else None
+        dfeats = [(df[i] if need[1 + i] else None) for i in range(4)]
+        st = stream_of(real)
+        ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q), real, st)
+        check(lib.kccot_conditional_sinkhorn_loss_bwd_f32(
+            ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w), ptr(omega), Q, ptr(state),
+            ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ws, wsb, st),
+            "conditional_sinkhorn_loss_bwd")
+        return (None,) * 8 + (dfake, *dfeats)
+
+
 class _MixedDivergence(torch.autograd.Function):
     """loss = 2*W_xy - W_xx - W_yy (gan_utils.py:225) as one launch each way."""
 
@@ -721,6 +786,85 @@ def compute_weighted_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
                                        *feats)
 
 
+def kernel_conditional_weights(context, bandwidth, queries=None):
+    """Gaussian-kernel estimate of the conditional law, one row per query: EXTENSION, not reference behaviour (the
+    weights compute_conditional_sinkhorn_loss takes).  ``context``: [B, ...] on the device, read as [B, Kc]; ``queries``:
+    an index tensor of Q samples of the batch (default: all B, in order).  With D[q,i] = |c_q - c_i|^2 (cost_xy with
+    scaling_coef = 1) row q is
+
+        w[q,i] = max(softmax_i(-D[q,i] / (2 bandwidth^2)), 2^-100)      (kccot_conditional_weights_f32)
+
+    -- the floor keeps a peaked kernel from handing the solver a zero weight; rows are not renormalised after it.  Returns
+    [Q, B] fp32.  The weights are not differentiated: a context that requires a gradient raises NotImplementedError."""
+    if not torch.is_tensor(context) or context.dim() < 2:
+        raise ValueError("context must be a tensor [batch, ...]")
+    if context.requires_grad:
+        raise NotImplementedError("kernel_conditional_weights does not differentiate w.r.t. the context; detach it")
+    if not float(bandwidth) > 0.0:
+        raise ValueError("bandwidth must be > 0 (got %r)" % (bandwidth,))
+    c = _flat2(context)
+    B = c.shape[0]
+    if B > 1024:
+        raise NotImplementedError("kernel_conditional_weights: B=%d > 1024" % B)
+    cq = c
+    if queries is not None:
+        queries = torch.as_tensor(queries, device=c.device)
+        if queries.dim() != 1 or queries.numel() < 1 or queries.dtype not in (torch.int32, torch.int64):
+            raise ValueError("queries must be a non-empty 1-D integer index tensor")
+        cq = c.index_select(0, queries.long()).contiguous()
+    with torch.no_grad():
+        D = cost_xy(cq, c, 1.0).contiguous()
+    Q = D.shape[0]
+    w = _lib.empty((Q, B), torch.float32, c.device)
+    check(lib.kccot_conditional_weights_f32(ptr(D), Q, B, float(bandwidth), ptr(w), stream_of(D)), "conditional_weights")
+    return w
+
+
+def compute_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
+                                      m_fake, weights, query_weights=None, video=True):
+    """The kernel-conditional causal loss: Q weighted solves of the one-batch loss on ONE shared set of cost matrices,
+
+        loss = sum_q omega_q (2 W(C_xy; w_q, w_q) - W(C_xx; w_q, w_q) - W(C_yy; w_q, w_q)),
+
+    with the three cost matrices of compute_sinkhorn_loss, W the weighted Sinkhorn cost (compute_weighted_sinkhorn),
+    w_q = ``weights[q]`` the estimate of the conditional law given the context of query q (kernel_conditional_weights; real
+    sample i and fake sample i share context i, so both marginals of all three problems are w_q) and omega =
+    ``query_weights`` ([Q]; None: 1/Q).  EXTENSION, not reference behaviour: the reference evaluates the loss with uniform
+    marginals only.  One library call each way (include/kccot_conditional.h): the cost matrices are assembled once, the
+    3 Q solves run as one launch (one workgroup each), loss and gradient are accumulated in double in ascending q.
+
+    ``sinkhorn_eps`` and ``sinkhorn_l`` ARE applied, as in compute_weighted_sinkhorn_loss.  ``weights``: [Q, B] device
+    tensor, strictly positive and finite, rows normalised by the caller.  Differentiable w.r.t. the fake videos and the
+    four features; a real video or a weight tensor that requires a gradient raises NotImplementedError.  Records
+    last_info["compute_conditional_sinkhorn_loss"] (counts [Q,3]; a negative row = a bad weight poisoned that query: its
+    costs, the loss and the gradients are NaN), ``..._executed`` [Q,3], ``..._costs`` [Q,3], ``..._C3`` [3,B,B],
+    ``..._path`` ("register" for B <= 128, "streaming" above) and ``..._fused_sweep`` (False)."""
+    for name, t in (("weights", weights), ("query_weights", query_weights)):
+        if t is not None and not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor" % name)
+        if t is not None and t.requires_grad:
+            raise NotImplementedError("%s: the conditional Sinkhorn loss does not differentiate w.r.t. the weights" % name)
+    if torch.is_tensor(f_real) and f_real.requires_grad:
+        raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+    if weights.dim() != 2 or weights.shape[0] < 1:
+        raise ValueError("weights must be [Q, B] with Q >= 1, got %s" % (tuple(weights.shape),))
+    Q = weights.shape[0]
+    if query_weights is not None and tuple(query_weights.shape) != (Q,):
+        raise ValueError("query_weights must be [%d], got %s" % (Q, tuple(query_weights.shape)))
+    vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l, True)
+    B = vids[0].shape[0]
+    if weights.shape[1] != B:
+        raise ValueError("weights must be [Q, %d], got %s" % (B, tuple(weights.shape)))
+    _lib.require_gpu(weights)
+    w = (weights if weights.dtype == torch.float32 else weights.float()).contiguous()
+    omega = None
+    if query_weights is not None:
+        _lib.require_gpu(query_weights)
+        omega = (query_weights if query_weights.dtype == torch.float32 else query_weights.float()).contiguous()
+    return _ConditionalSinkhornLoss.apply("compute_conditional_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, w, omega,
+                                          *vids, *feats)
+
+
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
     """Synchronising status check of the solves recorded under ``tags`` in ``last_info`` (``kccot_sinkhorn_status``): raises
     ``KccotError`` if a multi-CU Sinkhorn solve gave up (negative iteration count; its cost and gradients are NaN).  The
@@ -728,17 +872,21 @@ def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
     solve is reported as what it is and not as an exploded loss.  Default: the loss the trainer just evaluated (the
     single-GPU and the batch-sharded path both record their counts under "compute_sinkhorn_loss"); pass
     ``("compute_sinkhorn",)`` / ``("benchmark_sinkhorn",)`` after a direct call of those.  Under the tags of the weighted
-    solver ("compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss") a negative count means a weight that was <= 0
-    or not finite, and the error says so.  A checked entry is dropped, so a stale record of an earlier call can never be
+    solver ("compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss") and of the conditional loss
+    ("compute_conditional_sinkhorn_loss", counts [Q,3]) a negative count means a weight that was <= 0 or not finite, and
+    the error says so.  A checked entry is dropped, so a stale record of an earlier call can never be
     blamed for a later NaN."""
     for tag in tags:
         nits = last_info.pop(tag, None)
         if nits is None or not torch.is_tensor(nits) or not nits.is_cuda:
             continue
-        nits = nits.contiguous()
-        rc = lib.kccot_sinkhorn_status(ptr(nits), int(nits.numel()), stream_of(nits))
+        nits = nits.contiguous().reshape(-1)
+        rc = 0
+        for lo in range(0, int(nits.numel()), 4096):      # kccot_sinkhorn_status reads at most 4096 counts per call
+            part = nits[lo:lo + 4096]
+            rc = rc or lib.kccot_sinkhorn_status(ptr(part), int(part.numel()), stream_of(nits))
         if rc == _lib.EABORTED:
-            if tag.startswith("compute_weighted_"):     # the weighted solver never runs multi-CU: the only cause
+            if tag.startswith(("compute_weighted_", "compute_conditional_")):     # never multi-CU: the only cause
                 raise _lib.KccotError("%s: a marginal weight of a problem was <= 0 or not finite; its cost and gradients "
                                       "are NaN (counts %s)" % (tag, nits.tolist()))
             raise _lib.KccotError("%s: %s" % (tag, lib.kccot_last_error().decode("utf-8", "replace")))

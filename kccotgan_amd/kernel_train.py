@@ -16,6 +16,8 @@ each rank holds the partial derivative through its own samples).  ``bi_causal=Tr
 (``dist.sharded_bicausal_sinkhorn_loss``, GPU devices only).  ``mixed_sinkhorn=True`` with a ``group`` is still
 refused: the loss itself has a batch-sharded form (``dist.sharded_mixed_sinkhorn_loss``, ``dist.sharded_mixed_loss_step``),
 but the trainer does not call it yet -- its second real minibatch and the eight differentiated shards are not wired.
+``conditional_bandwidth`` (the kernel-conditional loss, an extension) is single-process only: neither the weighted nor the
+conditional loss has a batch-sharded form.
 
 ``sample`` is the test-time autoregressive loop (kernel_train.py:340-347), ``fit`` the loop body around the two
 steps (:295-330): per-iteration sigma (annealed or fixed, :308-311), the scalar log ``pM`` / ``Sinkhorn Loss``
@@ -91,7 +93,7 @@ class KCCOTTrainer:
                  g_state_size=8, d_state_size=8, g_filter_size=8, d_filter_size=8, z_channels=128, bn=True,
                  lr=5e-4, warmup=10000, sinkhorn_eps=0.8, sinkhorn_l=100, scaling_coef=15.0, reg_penalty=1.0,
                  kernel="none", device="cuda", seed=1, group=None, mixed_sinkhorn=False,
-                 bi_causal=False):
+                 bi_causal=False, conditional_bandwidth=None):
         # defaults = kernel_train.py:363-409
         # mixed_sinkhorn=True: the loss is COT-GAN's mixed Sinkhorn divergence over two minibatches
         # (gan_utils.compute_mixed_sinkhorn_loss) -- what the reference's --mixed_sinkhorn flag (:393) names but never runs
@@ -107,6 +109,22 @@ class KCCOTTrainer:
             # the batch-sharded bi-causal loss (dist.sharded_bicausal_sinkhorn_loss) runs on the HIP library only
             raise NotImplementedError("bi_causal=True with data parallelism: the sharded bi-causal loss runs on the GPU only "
                                       "(device %r)" % (device,))
+        # conditional_bandwidth=bw (EXTENSION, not in the reference): the kernel-conditional loss
+        # (gan_utils.compute_conditional_sinkhorn_loss).  Every sample is a query; its weights are the Gaussian-kernel estimate
+        # of the conditional law given its own UNSMOOTHED context frames, with bandwidth bw * sqrt(Kc) over the Kc numbers
+        # of a context -- bw is then a per-pixel RMS distance, independent of the frame size
+        if conditional_bandwidth is not None:
+            if not float(conditional_bandwidth) > 0.0:
+                raise ValueError("conditional_bandwidth must be > 0 (got %r)" % (conditional_bandwidth,))
+            if mixed_sinkhorn or bi_causal:
+                raise ValueError("conditional_bandwidth is exclusive with mixed_sinkhorn=True and bi_causal=True: there is no "
+                                 "mixed or bi-causal conditional loss")
+            if data_parallel:
+                raise NotImplementedError("conditional_bandwidth with data parallelism: the batch-sharded losses are "
+                                          "dist.sharded_sinkhorn_loss, sharded_mixed_sinkhorn_loss and "
+                                          "sharded_bicausal_sinkhorn_loss; the weighted and the conditional loss have no "
+                                          "sharded form")
+        self.conditional_bandwidth = None if conditional_bandwidth is None else float(conditional_bandwidth)
         self.mixed_sinkhorn = bool(mixed_sinkhorn)
         self.bi_causal = bool(bi_causal)
         torch.manual_seed(seed)
@@ -162,7 +180,14 @@ class KCCOTTrainer:
         h_real = self.discriminator_h(real)
         m_real = self.discriminator_m(real)
         m_fake = self.discriminator_m(fake)
-        if self.bi_causal and self._world() > 1:
+        if self.conditional_bandwidth is not None:
+            with torch.no_grad():       # once per forward; the weights are never differentiated
+                kc = real_in[0].numel()
+                weights = gan_utils.kernel_conditional_weights(real_in, self.conditional_bandwidth * math.sqrt(kc))
+            loss = gan_utils.compute_conditional_sinkhorn_loss(real.detach(), fake, self.scaling_coef, self.sinkhorn_eps,
+                                                               self.sinkhorn_l, h_fake, m_real, h_real, m_fake, weights,
+                                                               video=True)
+        elif self.bi_causal and self._world() > 1:
             from . import dist as kd
             loss = kd.sharded_bicausal_sinkhorn_loss(real.detach(), fake, self.scaling_coef, h_fake, m_real, h_real, m_fake,
                                                      group=self.group)
@@ -220,6 +245,8 @@ class KCCOTTrainer:
         """the gan_utils.last_info tag of the loss this trainer evaluates"""
         if self.mixed_sinkhorn:
             return "compute_mixed_sinkhorn_loss"
+        if self.conditional_bandwidth is not None:
+            return "compute_conditional_sinkhorn_loss"
         return "compute_bicausal_sinkhorn_loss" if self.bi_causal else "compute_sinkhorn_loss"
 
     def _world(self):
