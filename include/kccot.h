@@ -94,6 +94,11 @@ const char* kccot_last_error(void);
  *   sinkhorn_fused            1        0: kccot_sinkhorn_fused_eligible reports 0 (solve and reverse sweep as two launches)
  *   sinkhorn_fused_max_n      64       largest n the fused solve + sweep launch accepts (<= 128; above 64 it spills registers)
  *   sinkhorn_lanes_per_line   0        4 / 8 / 16 lanes per matrix line for 32 < n <= 64 (0: forward 8, reverse sweep 16)
+ *   sinkhorn_fused_roles      1        1: the fused solve + sweep launch runs the row and the column orientation on separate waves
+ *                                      (twice the workgroup: while one role is on a half-step's dependent chain the other
+ *                                      evaluates its next transport plan) where both fit 1024 threads -- n <= 32, or n <= 64 at
+ *                                      8 or 4 lanes per line (kccot_sinkhorn_fused_roles_eligible); same bits, 136.5 -> 127.2 us
+ *                                      at three 64 x 64 problems; 0: every wave runs both orientations (sinkhorn_fused_reg)
  *   sinkhorn_coop             1        0: 128 < n <= 1024 on the one-workgroup streaming solver instead of the multi-CU one
  *   sinkhorn_coop_xcd         1        1: the multi-CU solver lays one problem out per XCD (1-D grid dealt round-robin) and, after
  *                                      an in-kernel check that all workgroups of a problem really share an XCD, exchanges the
@@ -354,8 +359,12 @@ int kccot_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const flo
  * kernel's lane grid (entries per lane x lanes per line), fits 144 KB of LDS; configs[0] and configs[1] are.
  * dC3_unit [3,n,n] = d loss / d C3 at dLoss = 1; the backward multiplies by the upstream scalar `gloss` (one device
  * float) while building its coefficients.  Costs, iteration counts and loss are bit-identical to the two-launch form.
- * Option "sinkhorn_fused" = 0 reports "not eligible". */
+ * Option "sinkhorn_fused" = 0 reports "not eligible".
+ * kccot_sinkhorn_fused_roles_eligible: 1 when that launch would run its role-split form (option "sinkhorn_fused_roles",
+ * the launch eligible, and two roles of ceil64(n x lanes per line) threads within a 1024-thread workgroup); every output
+ * is bit-identical between the two forms. */
 int kccot_sinkhorn_fused_eligible(int n, int L);
+int kccot_sinkhorn_fused_roles_eligible(int n, int L);
 int kccot_sinkhorn_divergence_fused_f32(const float* C3, int n, float eps, int L, int Lmin, float thresh,
                                         float* cost3_out, int32_t* nits_out, float* loss_out, int32_t* ticket,
                                         float* dC3_unit, kccot_stream_t stream);

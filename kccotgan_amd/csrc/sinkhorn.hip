@@ -43,9 +43,10 @@ __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_log
 #ifndef KCCOT_DIAG_IT
 #define KCCOT_DIAG_IT 50
 #endif
-#define KCCOT_STAMP(SLOT)                                                                         \
+#define KCCOT_STAMP(SLOT) KCCOT_STAMP_IF(it == KCCOT_DIAG_IT, SLOT)
+#define KCCOT_STAMP_IF(COND, SLOT)                                                                \
     do {                                                                                          \
-        if (a.diag && it == KCCOT_DIAG_IT) {                                                                 \
+        if (a.diag && (COND)) {                                                                   \
             unsigned long long tt_;                                                               \
             __builtin_amdgcn_sched_barrier(0);                                                    \
             asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt_)::"memory");          \
@@ -55,6 +56,7 @@ __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_log
     } while (0)
 #else
 #define KCCOT_STAMP(SLOT) do {} while (0)
+#define KCCOT_STAMP_IF(COND, SLOT) do {} while (0)
 #endif
 
 struct SinkArgs {
@@ -626,6 +628,7 @@ struct SinkFusedArgs {
     int* ticket;          // zero on entry, left zero
     float* dC;            // [nprob,n,n]
     float w[SK_FUSED_MAXPROB];   // loss weights (w[p] = +-1 or 2: every product below is exact)
+    unsigned long long* diag;    // diagnostic build only (kccot_diag_fused_stamps); null otherwise
 };
 
 template <int EPT, int LPR, bool SHORTCUT, int NPROB>
@@ -669,7 +672,9 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     int nits = 0;
     float ui = 0.f, vj = 0.f;
     // ---------------------------------------------------------------- forward (see sinkhorn_fwd_body)
+    KCCOT_STAMP_IF(true, 11);                                  // 11 .. 12: the whole forward loop
     for (int it = 0; it < L; ++it) {
+        KCCOT_STAMP(9);
         const float un = half_step<EPT, LPR, true>(crow, ui, hv + it * NS, q, lw2);
         const float du = (active && q == 0) ? fabsf(un - ui) : 0.f;
         int bits = 0;
@@ -698,6 +703,7 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         vj = vn;
         if (active && q == 0) hv[(it + 1) * NS + line] = vn;
         lds_barrier();
+        KCCOT_STAMP(10);
         nits = it + 1;
         ++computed;
         if (nits >= a.Lmin && it + 1 < L) {                   // gan_utils.py:157-160
@@ -735,6 +741,7 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         }
     }
 
+    KCCOT_STAMP_IF(true, 12);
     // gan_utils.py:162-164: pi = exp((-C + u + v^T)/eps); cost = sum(pi * C)
     const float* Vn = hv + nits * NS;
     const float* Un = hu + nits * NS;
@@ -829,13 +836,16 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
 #pragma unroll
         for (int m = 0; m < EPT; ++m) pb[m] = __builtin_amdgcn_exp2f((ou[m] - ccol[m]) + vv);
     };
+    KCCOT_STAMP_IF(true, 13);                                  // 13 .. 14: the whole sweep loop
     if (nits >= 1) plan_a(nits);
     for (int it = nits; it >= 1; --it) {
         {   // (A) through v_t: row pass with Q_t
+            KCCOT_STAMP(0);
             float og[EPT];
             load_other<EPT>(og, gv, q);
             plan_b(it);
             __builtin_amdgcn_sched_barrier(0);          // keep the exp2 of the next pass in the shadow of the gv read
+            KCCOT_STAMP(1);
             float sa = 0.f;
 #pragma unroll
             for (int m = 0; m < EPT; ++m) {
@@ -844,14 +854,18 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
                 sa += w;
             }
             sa = seg_sum<LPR>(sa);
+            KCCOT_STAMP(2);
             if (active && q == 0) gu[line] = (it == nits ? gu[line] : 0.f) - sa;
+            KCCOT_STAMP(3);
         }
         lds_barrier();
         {   // (B) through u_t: column pass with P_t
+            KCCOT_STAMP(4);
             float og[EPT];
             load_other<EPT>(og, gu, q);
             if (it > 1) plan_a(it - 1);
             __builtin_amdgcn_sched_barrier(0);
+            KCCOT_STAMP(5);
             float r = 0.f;
 #pragma unroll
             for (int m = 0; m < EPT; ++m) {
@@ -860,10 +874,14 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
                 r += w;
             }
             r = seg_sum<LPR>(r);
+            KCCOT_STAMP(6);
             if (active && q == 0) gv[line] = -r;
+            KCCOT_STAMP(7);
         }
         lds_barrier();
+        KCCOT_STAMP(8);
     }
+    KCCOT_STAMP_IF(true, 14);
     // dC = row-layout part + (column-layout part)^T
     float* dC = a.dC + (int64_t)p * n * n;
     if (active) {
@@ -882,6 +900,282 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
             if (idx < n) dC[(int64_t)idx * n + line] += dcol[m];
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// sinkhorn_fused_roles: sinkhorn_fused_reg with the two orientations on SEPARATE waves (option "sinkhorn_fused_roles").
+//
+// In sinkhorn_fused_reg every wave holds the costs in both orientations and runs both passes of every iteration, so in
+// the reverse sweep the plan of the NEXT pass (8 packed adds + 8 exp2 per lane, independent of the running gradients) is
+// issued by the very wave whose multiply-add chain the workgroup is waiting for.  Here the workgroup is 2 TR threads,
+// TR = ceil64(n LPR): threads [0, TR) are the ROW role (row orientation: ui, pass A, plan_a), threads [TR, 2 TR) the
+// COLUMN role (column orientation: vj, pass B, plan_b).  The role is wave-uniform.  While one role is on the chain the
+// other evaluates its next plan, then both meet at the barrier that was there anyway: same two barriers per iteration,
+// same gu / gv and history exchange through LDS, nothing else shared.
+//
+// Bit-identical to sinkhorn_fused_reg: lane (line, q) of a role executes, on the same operands and in the same order, the
+// instructions that lane (line, q) of the one-role kernel executes for that orientation; the plans never leave the
+// registers of the wave that consumes them; the block sums (stop rule, cost) add the waves in order and the column waves
+// contribute trailing + 0.0f terms to a sum that starts at + 0.0f.  Every wave executes the same number of barriers on
+// every path (both roles run the same loop with the same wave-uniform trip counts; only the work between barriers differs).
+// Host: taken when 2 TR <= 1024 (kccot_sinkhorn_fused_roles_eligible); otherwise sinkhorn_fused_reg runs.
+// ------------------------------------------------------------------------------------------
+template <int EPT, int LPR, bool SHORTCUT, int NPROB, bool COL>
+__device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* hist, float* gu, float* gv, float* red,
+                                                 int* mis, const int TR) {
+    constexpr int NS = EPT * LPR;
+    const int p = blockIdx.x, n = a.n, L = a.L;
+    const int t = threadIdx.x, tr = t - (COL ? TR : 0), line = tr / LPR, q = tr % LPR;
+    const bool active = line < n;
+    const float* C = a.C + (int64_t)p * n * n;
+    const float k2 = a.inv_eps * LOG2E;
+    float* hu = hist;
+    float* hv = hist + (size_t)(L + 1) * NS;
+    // this role's duals and the other role's: the row role owns U (reads V), the column role owns V (reads U)
+    float* hs = COL ? hv : hu;
+    const float* ho = COL ? hu : hv;
+
+    float c2[EPT];                                             // C * k2 in this role's orientation (load_costs)
+#pragma unroll
+    for (int m = 0; m < EPT; ++m) {
+        const int idx = q * EPT + m;
+        const bool ok = line < n && idx < n;
+        c2[m] = ok ? C[COL ? (int64_t)idx * n + line : (int64_t)line * n + idx] * k2 : INFINITY;
+    }
+    for (int i = t; i < NS; i += blockDim.x) { hu[i] = 0.f; hv[i] = 0.f; }
+    if (NS > n) {
+        const int padw = NS - n;
+        for (int e = t; e < L * padw; e += blockDim.x) {
+            const int k = 1 + e / padw, i = n + e % padw;
+            hu[k * NS + i] = 0.f; hv[k * NS + i] = 0.f;
+        }
+    }
+    for (int i = t; i < SK_MAXN + 16 * 16; i += blockDim.x) { gu[i] = 0.f; gv[i] = 0.f; }
+    if (t < 4) mis[t] = 0;
+    __syncthreads();
+
+    const float lw2 = __builtin_amdgcn_logf(1.0f / (float)n);
+    const float err_scale = a.eps * LN2;
+    bool detect = SHORTCUT;
+    int computed = 0;
+    int mprev = ~0;
+    float p2 = 0.f, p3 = 0.f, p4 = 0.f;
+    int nits = 0;
+    float self = 0.f;                                          // ui (row role) / vj (column role)
+    // one half-step of this role: the dual, its history row (the next half-step's exchange array) and the shortcut's
+    // mismatch bits, OR-ed into mis[] per wave (both roles do, each with its own half of sinkhorn_fused_reg's `bits`)
+    auto own_half_step = [&](int it, float& du) {
+        const float sn = half_step<EPT, LPR, !COL>(c2, self, ho + (COL ? it + 1 : it) * NS, q, lw2);
+        du = (active && q == 0) ? fabsf(sn - self) : 0.f;
+        if (active && q == 0) hs[(it + 1) * NS + line] = sn;
+        if (SHORTCUT && detect) {
+            const unsigned b = __float_as_uint(sn);
+            int bits = (b != __float_as_uint(self) ? 2 : 0) | (b != __float_as_uint(p2) ? 4 : 0) |
+                       (b != __float_as_uint(p3) ? 8 : 0) | (b != __float_as_uint(p4) ? 16 : 0);
+            p4 = p3; p3 = p2; p2 = self;
+            if (!active) bits = 0;
+            int wb = 0;
+#pragma unroll
+            for (int pp = 1; pp <= 4; ++pp)
+                if (__builtin_amdgcn_ballot_w64((bits >> pp) & 1)) wb |= 1 << pp;
+            if ((t & 63) == 0 && wb) atomicOr(&mis[it & 3], wb);
+        }
+        self = sn;
+    };
+    // ---------------------------------------------------------------- forward
+    KCCOT_STAMP_IF(true, 11);
+    for (int it = 0; it < L; ++it) {
+        KCCOT_STAMP(9);
+        float du = 0.f;
+        if constexpr (!COL) own_half_step(it, du);
+        lds_barrier();
+        if constexpr (COL) { float dv; own_half_step(it, dv); }
+        lds_barrier();
+        KCCOT_STAMP(10);
+        nits = it + 1;
+        ++computed;
+        if (nits >= a.Lmin && it + 1 < L) {                   // gan_utils.py:157-160 (sum over the row role's du)
+            const float err = block_sum(du, red) * err_scale;
+            if (a.thresh > err) break;
+        }
+        if (SHORTCUT && detect) {
+            const int mcur = mis[it & 3];
+            if (t == 0) mis[(it + 2) & 3] = 0;
+            int per = 0;
+#pragma unroll
+            for (int pp = 4; pp >= 1; --pp)
+                if (it - 1 >= pp && !((mprev >> pp) & 1)) per = pp;
+            mprev = mcur;
+            if (per) {
+                detect = false;
+                int first_stop = a.Lmin < 1 ? 1 : a.Lmin;
+                const int K1 = (L < first_stop ? L : first_stop) - 1;
+                if (K1 > nits) {
+                    const int lo = nits - per + 1;
+                    for (int e = t; e < (K1 - nits) * n; e += blockDim.x) {
+                        const int k = nits + 1 + e / n, i = e % n;
+                        const int src = lo + (k - lo) % per;
+                        hu[k * NS + i] = hu[src * NS + i];
+                        hv[k * NS + i] = hv[src * NS + i];
+                    }
+                    __syncthreads();
+                    self = hs[K1 * NS + (active ? line : 0)];
+                    nits = K1;
+                    it = K1 - 1;
+                }
+            }
+        }
+    }
+
+    KCCOT_STAMP_IF(true, 12);
+    // gan_utils.py:162-164: pi = exp((-C + u + v^T)/eps); cost = sum(pi * C): the row role's lanes, zeros from the others
+    const float* Vn = hv + nits * NS;
+    const float* Un = hu + nits * NS;
+    float part = 0.f;
+    if constexpr (!COL) {
+        if (active) {
+#pragma unroll
+            for (int m = 0; m < EPT; ++m) {
+                const int idx = q * EPT + m;
+                if (idx < n) {
+                    const float pi = __builtin_amdgcn_exp2f((self - c2[m]) + Vn[idx]);
+                    part += pi * C[(int64_t)line * n + idx];
+                }
+            }
+        }
+    }
+    const float cost = block_sum(part, red);
+    if constexpr (!COL) {
+        if (t == 0) {
+            // (fence-free hand-off as in sinkhorn_fwd_body / sinkhorn_fused_reg: agent-scope store, drained, then the ticket)
+            __hip_atomic_store(a.cost_out + p, cost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.nits_out[p] = nits;
+            a.nits_out[gridDim.x + p] = computed;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const int tk = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tk == (int)gridDim.x - 1) {
+                float c[NPROB];
+                if constexpr (NPROB == 3) {
+#pragma unroll
+                    for (int pp = 0; pp < 3; ++pp) c[pp] = __hip_atomic_load(a.cost_out + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    float o[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        o[k] = __hip_atomic_load(a.cost_out + ((p + 1 + k) & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+                    for (int pp = 0; pp < 4; ++pp) {
+                        const int k = (pp - p - 1) & 3;
+                        c[pp] = k == 0 ? o[0] : k == 1 ? o[1] : k == 2 ? o[2] : cost;
+                    }
+                }
+                float l = a.w[0] * c[0];
+#pragma unroll
+                for (int pp = 1; pp < NPROB; ++pp) l += a.w[pp] * c[pp];
+                a.loss_out[0] = l;
+                __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+
+    // ---------------------------------------------------------------- reverse sweep
+    const float g = a.w[p];
+    const int lsafe = active ? line : 0;
+    float d[EPT];                                              // drow (row role) / dcol (column role)
+    {
+        const float sf = (COL ? Vn : Un)[lsafe];
+        float oo[EPT];
+        load_other<EPT>(oo, COL ? Un : Vn, q);
+        float ss = 0.f;
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) {
+            const bool ok = active && (q * EPT + m) < n;
+            const float cc = ok ? c2[m] : 0.f;
+            const float pv = ok ? __builtin_amdgcn_exp2f(COL ? ((oo[m] - cc) + sf) : ((sf - cc) + oo[m])) : 0.f;
+            d[m] = COL ? 0.f : g * pv * (1.f - cc * LN2);
+            ss += pv * cc;
+        }
+        ss = seg_sum<LPR>(ss);
+        if (active && q == 0) (COL ? gv : gu)[line] = g * ss * LN2;
+    }
+    __syncthreads();
+    float pl[EPT];                                             // Q_t (row role, plan_a) / P_t (column role, plan_b)
+    auto plan = [&](int it) {
+        // row:    Q_it[line][q*EPT+m] = exp2((U_it,line - lw2 - c) + V_it,col)
+        // column: P_it[q*EPT+m][line] = exp2((U_it,row - c) + V_{it-1,line} - lw2)
+        const float sv = hs[(COL ? it - 1 : it) * NS + lsafe] - lw2;
+        float oo[EPT];
+        load_other<EPT>(oo, ho + it * NS, q);
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) pl[m] = __builtin_amdgcn_exp2f(COL ? ((oo[m] - c2[m]) + sv) : ((sv - c2[m]) + oo[m]));
+    };
+    // this role's pass: the gradients the other role wrote -> multiply-adds -> DPP sum -> this role's gradients
+    auto chain = [&](int it) {
+        float og[EPT];
+        load_other<EPT>(og, COL ? gu : gv, q);
+        KCCOT_STAMP(COL ? 5 : 1);
+        float s = 0.f;
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) {
+            const float w = pl[m] * og[m];
+            d[m] += w;
+            s += w;
+        }
+        s = seg_sum<LPR>(s);
+        KCCOT_STAMP(COL ? 6 : 2);
+        if (active && q == 0) {
+            if constexpr (COL) gv[line] = -s;
+            else gu[line] = (it == nits ? gu[line] : 0.f) - s;
+        }
+        KCCOT_STAMP(COL ? 7 : 3);
+    };
+    KCCOT_STAMP_IF(true, 13);
+    if constexpr (!COL) { if (nits >= 1) plan(nits); }
+    for (int it = nits; it >= 1; --it) {
+        KCCOT_STAMP(0);
+        if constexpr (COL) { plan(it); KCCOT_STAMP(1); } else chain(it);              // (A) through v_t
+        lds_barrier();
+        KCCOT_STAMP(4);
+        if constexpr (COL) chain(it); else { if (it > 1) plan(it - 1); KCCOT_STAMP(5); }   // (B) through u_t
+        lds_barrier();
+        KCCOT_STAMP(8);
+    }
+    KCCOT_STAMP_IF(true, 14);
+    // dC = row-layout part + (column-layout part)^T
+    float* dC = a.dC + (int64_t)p * n * n;
+    if constexpr (!COL) {
+        if (active) {
+#pragma unroll
+            for (int m = 0; m < EPT; ++m) {
+                const int idx = q * EPT + m;
+                if (idx < n) dC[(int64_t)line * n + idx] = d[m];
+            }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if constexpr (COL) {
+        if (active) {
+#pragma unroll
+            for (int m = 0; m < EPT; ++m) {
+                const int idx = q * EPT + m;
+                if (idx < n) dC[(int64_t)idx * n + line] += d[m];
+            }
+        }
+    }
+}
+
+template <int EPT, int LPR, bool SHORTCUT, int NPROB>
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_fused_roles(SinkFusedArgs a) {
+    static_assert(NPROB == 3 || NPROB == 4, "three (compute_sinkhorn_loss) or four (mixed, two minibatches) problems");
+    extern __shared__ __attribute__((aligned(16))) float hist[];
+    __shared__ __attribute__((aligned(16))) float gu[SK_MAXN + 16 * 16];
+    __shared__ __attribute__((aligned(16))) float gv[SK_MAXN + 16 * 16];
+    __shared__ float red[16];
+    __shared__ int mis[4];
+    const int TR = blockDim.x >> 1;                            // threads per role, a multiple of 64: the role is wave-uniform
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >= TR)) fused_roles_body<EPT, LPR, SHORTCUT, NPROB, true>(a, hist, gu, gv, red, mis, TR);
+    else fused_roles_body<EPT, LPR, SHORTCUT, NPROB, false>(a, hist, gu, gv, red, mis, TR);
 }
 
 // gan_utils.py:225: loss = 2.0 * loss_xy - loss_xx - loss_yy, evaluated left to right in fp32
@@ -1076,6 +1370,11 @@ extern "C" int kccot_mixed_divergence_bwd_f32(const float* gloss, float* gcost3_
 }
 
 // ---- fused solve + reverse sweep (sinkhorn_fused_reg) -------------------------------------------------
+#ifdef KCCOT_DIAG
+// diagnostic twin only (tools/diag_sinkhorn.py): the device buffer [nprob,16 waves,16 slots] that the fused kernels stamp
+static unsigned long long* g_fused_stamps = nullptr;
+extern "C" void kccot_diag_fused_stamps(void* buf) { g_fused_stamps = static_cast<unsigned long long*>(buf); }
+#endif
 static size_t fused_hist_bytes(int n, int L) {
     const SinkGeom g = sink_geom(n, true);
     return (size_t)2 * ((size_t)L + 1) * g.lpr * g.ept * sizeof(float);
@@ -1091,8 +1390,31 @@ extern "C" int kccot_sinkhorn_fused_eligible(int n, int L) {
     return fused_hist_bytes(n, L) <= (size_t)144 * 1024;  // + ~4 KB of static LDS, inside the CU's 160 KB
 }
 
+// The role-split kernel (sinkhorn_fused_roles) doubles the workgroup: it is taken where option "sinkhorn_fused_roles" is set,
+// the one-role kernel is eligible and both roles fit one workgroup, 2 ceil64(n lanes) <= 1024: n <= 32 at 16 lanes per
+// line, n <= 64 at 8 or 4.  (<4,16> and <16,8> never fit; every instance that does is scratch-free under the 128-VGPR cap
+// of 1024 threads, see profiles/sinkhorn_roles_ab.json.)
+extern "C" int kccot_sinkhorn_fused_roles_eligible(int n, int L) {
+    if (!opt(OPT_SK_FUSED_ROLES) || !kccot_sinkhorn_fused_eligible(n, L)) return 0;
+    return 2 * sink_geom(n, true).threads <= SK_MAXT;
+}
+
+template <int EPT, int LPR, bool SC, int NP>
+static int launch_fused_roles_np(const SinkFusedArgs& a, size_t lds, hipStream_t st) {
+    if constexpr ((EPT == 4 && LPR == 16) || (EPT == 16 && LPR == 8)) {
+        return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused_roles: no <%d,%d> instance", EPT, LPR);
+    } else {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_fused_roles<EPT, LPR, SC, NP>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
+            return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused_roles: cannot raise the dynamic LDS limit");
+        hipLaunchKernelGGL((sinkhorn_fused_roles<EPT, LPR, SC, NP>), dim3(NP), dim3(2 * ((a.n * LPR + 63) / 64 * 64)), lds, st, a);
+        return launch_status("sinkhorn_fused_roles");
+    }
+}
+
 template <int EPT, int LPR, bool SC, int NP>
 static int launch_fused_np(const SinkFusedArgs& a, size_t lds, hipStream_t st) {
+    if (kccot_sinkhorn_fused_roles_eligible(a.n, a.L)) return launch_fused_roles_np<EPT, LPR, SC, NP>(a, lds, st);
     // on every launch: the attribute belongs to the current device's copy of the function (a per-process "done" flag
     // would be wrong on a second device and racy between threads); it is a host-side table write
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_fused_reg<EPT, LPR, SC, NP>),
@@ -1133,8 +1455,11 @@ int kccot::sinkhorn_fused_weighted(const float* C, int nprob, const float* w, in
         return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused: n=%d L=%d does not fit (see kccot_sinkhorn_fused_eligible)", n, L);
     const SinkGeom g = sink_geom(n, true);
     SinkFusedArgs a{C, n, L, Lmin, eps, (float)(1.0 / (double)eps), thresh, cost_out, nits_out, loss_out,
-                    reinterpret_cast<int*>(ticket), dC_unit, {0.f, 0.f, 0.f, 0.f}};
+                    reinterpret_cast<int*>(ticket), dC_unit, {0.f, 0.f, 0.f, 0.f}, nullptr};
     for (int p = 0; p < nprob; ++p) a.w[p] = w[p];
+#ifdef KCCOT_DIAG
+    a.diag = g_fused_stamps;
+#endif
     const size_t lds = fused_hist_bytes(n, L);
     return sink_shortcut_enabled() ? dispatch_fused<true>(g, a, nprob, lds, st) : dispatch_fused<false>(g, a, nprob, lds, st);
 }

@@ -1,17 +1,68 @@
 #!/usr/bin/env python3
 """Where does a Sinkhorn half-step spend its cycles?  Loads the DIAGNOSTIC twin library
 (libkccot_diag.so, built with -DKCCOT_DIAG: s_memtime stamps around the phases of iteration 50)
-and prints per-wave cycle counts between stamps.  Never used by the product path."""
+and prints per-wave cycle counts between stamps.  Never used by the product path.
+usage: diag_sinkhorn.py [n [golden file]]      the forward kernel (sinkhorn_fwd_reg)
+       diag_sinkhorn.py fused [n [golden file]] the fused solve + sweep, one-role and role-split: one sweep iteration
+                                               (pass A, pass B) and one forward iteration, mean over waves and launches"""
 import ctypes, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = ctypes.CDLL(os.path.join(ROOT, "kccotgan_amd", "csrc", "libkccot_diag.so"))
 vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 lib.kccot_sinkhorn_fwd_f32.argtypes = [vp, ci, ci, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, sz, vp]
+FUSED = len(sys.argv) > 1 and sys.argv[1] == "fused"
+if FUSED:
+    del sys.argv[1]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 g = np.load(os.path.join(ROOT, "tests", "golden", sys.argv[2] if len(sys.argv) > 2 else "cfg2_s0_near.npz"))
 C = torch.from_numpy(np.stack([g["C_xy"], g["C_xx"], g["C_yy"]])).cuda()[:, :n, :n].contiguous()
 L = 100
+
+
+def fused_stamps(roles, launches=20):
+    """Stamps of sweep iteration 50 and forward iteration 50 of the fused kernel, [launch, wave, slot] of problem 0.
+    Slots: 0 pass A starts / 1 plan_b evaluated (one role: after the gv read, the wave that is on the chain; roles: the
+    column waves; on the row waves slot 1 = the gradients have arrived) / 2 DPP sum done / 3 gu written / 4 after the
+    barrier / 5 plan_a evaluated (roles: row waves; column waves: gradients arrived) / 6 DPP sum / 7 gv written / 8 after
+    the closing barrier; 9 / 10: a forward iteration's start and end; 11 / 12 and 13 / 14: around the whole forward loop and
+    the whole sweep loop (one stamp pair per 100 iterations: the stamps of iteration 50 are the only disturbance inside).
+    Every stamp costs about 40 cycles itself."""
+    lib.kccot_sinkhorn_divergence_fused_f32.argtypes = [vp, ci, cf, ci, ci, cf, vp, vp, vp, vp, vp, vp]
+    lib.kccot_set_option.argtypes = [ctypes.c_char_p, ci]
+    lib.kccot_diag_fused_stamps.argtypes = [vp]
+    assert lib.kccot_set_option(b"sinkhorn_shortcut", 0) == 0 and lib.kccot_set_option(b"sinkhorn_fused_roles", roles) == 0
+    cost = torch.empty(3, device="cuda"); nits = torch.empty(6, dtype=torch.int32, device="cuda")
+    loss = torch.empty(1, device="cuda"); ticket = torch.zeros(1, dtype=torch.int32, device="cuda"); dC = torch.empty_like(C)
+    diag = torch.zeros(3 * 16 * 16, dtype=torch.int64, device="cuda")
+    lib.kccot_diag_fused_stamps(diag.data_ptr())
+    out = []
+    for rep in range(launches + 3):
+        diag.zero_()
+        assert lib.kccot_sinkhorn_divergence_fused_f32(C.data_ptr(), n, 1.0, L, 100, 1e-2, cost.data_ptr(), nits.data_ptr(),
+                                                       loss.data_ptr(), ticket.data_ptr(), dC.data_ptr(), None) == 0
+        torch.cuda.synchronize()
+        if rep >= 3:
+            out.append(diag.cpu().numpy().reshape(3, 16, 16)[0].copy())
+    lib.kccot_diag_fused_stamps(None)
+    return np.stack(out), nits.tolist()
+
+
+if FUSED:
+    for roles in (0, 1):
+        d, its = fused_stamps(roles)
+        nw = int((d[0, :, 0] != 0).sum())
+        groups = [("all waves", range(nw))] if not roles else [("row waves", range(nw // 2)), ("column waves", range(nw // 2, nw))]
+        print("sinkhorn_fused_roles=%d  n=%d  waves=%d  nits %s" % (roles, n, nw, its))
+        for name, ws in groups:
+            ws = list(ws)
+            seg = lambda a, b: float(np.mean(d[:, ws, b] - d[:, ws, a])) if (d[:, ws, a] != 0).all() and (d[:, ws, b] != 0).all() else float("nan")
+            print("  %-12s pass A: to plan/gradients %.0f  to DPP sum %.0f  to write %.0f  to barrier exit %.0f | pass B: %.0f  %.0f  %.0f  %.0f"
+                  " | sweep iteration %.0f cycles | forward iteration %.0f cycles | whole forward loop %.0f, whole sweep loop %.0f cycles" % (
+                      name, seg(0, 1), seg(1, 2), seg(2, 3), seg(0, 4), seg(4, 5), seg(5, 6), seg(6, 7), seg(4, 8), seg(0, 8), seg(9, 10),
+                      seg(11, 12), seg(13, 14)))
+    sys.exit(0)
+
 uh = torch.empty(3, L, n, device="cuda"); vh = torch.empty(3, L, n, device="cuda")
 cost = torch.empty(3, device="cuda"); nits = torch.empty(6, dtype=torch.int32, device="cuda")
 diag = torch.zeros(3 * 16 * 16, dtype=torch.int64, device="cuda")
