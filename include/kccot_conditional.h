@@ -11,7 +11,7 @@
  *     loss_q = 2 W(C_xy; w_q, w_q) - W(C_xx; w_q, w_q) - W(C_yy; w_q, w_q)         W: the weighted loop of kccot_weighted.h
  *     loss   = sum_q omega_q loss_q                                                 (double accumulation, ascending q)
  * Real sample i and fake sample i share context i, so both marginals of all three problems are w_q.  The weights are
- * never differentiated: dC3[k] = gloss sum_q omega_q {2,-1,-1}[k] dW_{q,k}/dC through the executed iterations (double
+ * not differentiated here (kccot_weight_grad.h: dw, domega and the estimator's adjoint): dC3[k] = gloss sum_q omega_q {2,-1,-1}[k] dW_{q,k}/dC through the executed iterations (double
  * accumulation, ascending q: no result depends on the order in which workgroups finish).
  *
  * Problem p = 3 q + k reads cost matrix k of the shared C3 and weight row q; everything per problem (histories, costs,

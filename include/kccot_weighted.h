@@ -11,7 +11,7 @@
  *         v_j += eps (log b_j - LSE_i((-C_ij + u_i + v_j)/eps))
  *     W(C; a, b) = sum_ij exp((-C_ij + u_i + v_j)/eps) C_ij
  * With a = b = 1/n this is kccot_sinkhorn_fwd_f32 (to rounding: log(1/n) is then formed from the stored weights).
- * The weights are not differentiated.  A weight that is <= 0 or not finite poisons ITS problem, not the launch:
+ * The weights are not differentiated by these entry points (kccot_weight_grad.h has the ones that do).  A weight that is <= 0 or not finite poisons ITS problem, not the launch:
  * cost = NaN, nits_out[p] = -1 (kccot_sinkhorn_status reports it), NaN gradients from the reverse sweep.
  * Dispatch: n <= 128 the register-resident kernels, 128 < n <= 1024 the streaming single-workgroup solver.  The
  * multi-CU solver (option sinkhorn_coop) and the one-launch fused loss (option sinkhorn_fused) are not weighted and are

@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
-``include/kccot_weighted.h``, ``include/kccot_conditional.h`` and ``include/kccot_smooth_causal3.h``).
+``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h`` and
+``include/kccot_smooth_causal3.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -145,6 +146,27 @@ CONDITIONAL_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_weight_grad.h one to one (the gradients of the weighted solver, the weighted
+# loss and the kernel-conditional loss w.r.t. their WEIGHTS, and the adjoint of the weight estimator: an extension outside the
+# versioned surface of kccot.h)
+WEIGHT_GRAD_SIGNATURES = {
+    "kccot_sinkhorn_weighted_bwd_dw_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_weighted_sinkhorn_loss_dw_workspace_bytes": (_sz, [_i, _i64]),
+    "kccot_weighted_sinkhorn_loss_bwd_dw_f32": (_i, [_fp, _fp, _fp, _i, _i64, _f, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp, _fp,
+                                                     _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_sinkhorn_conditional_dw_workspace_bytes": (_sz, [_i, _i]),
+    "kccot_sinkhorn_conditional_bwd_dw_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp, _fp, _fp, _fp, _fp,
+                                                   _sz, _fp]),
+    "kccot_conditional_sinkhorn_loss_dw_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "kccot_conditional_sinkhorn_loss_bwd_dw_f32": (_i, [_fp, _fp, _fp, _i, _i64, _f, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp,
+                                                        _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                        _fp, _sz, _fp]),
+    "kccot_conditional_weights_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _f, _fp, _fp, _fp]),
+    "kccot_conditional_weights_dev_f32": (_i, [_fp, _i, _i, _fp, _fp, _fp]),
+    "kccot_conditional_weights_bwd_dev_f32": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
+}
+
+
 # name -> (restype, argtypes); mirrors include/kccot_smooth_causal3.h one to one (the causal 3-D smoothing -- past-only in
 # time, symmetric in space: an extension outside the versioned surface of kccot.h).  flags: the protocol bits only.
 SMOOTH3C_SIGNATURES = {
@@ -165,7 +187,8 @@ def _load():
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) +
-                              list(CONDITIONAL_SIGNATURES.items()) + list(SMOOTH3C_SIGNATURES.items())):
+                              list(CONDITIONAL_SIGNATURES.items()) + list(WEIGHT_GRAD_SIGNATURES.items()) +
+                              list(SMOOTH3C_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -7,6 +7,7 @@
 #include "../../include/kccot.h"
 #include "../../include/kccot_weighted.h"
 #include "../../include/kccot_conditional.h"
+#include "../../include/kccot_weight_grad.h"
 
 #define KCCOT_WAVE 64
 
@@ -152,7 +153,8 @@ int sinkhorn_divergence_weighted_fwd(const float* C3, const float* w_real, const
                                      hipStream_t st);
 int sinkhorn_divergence_weighted_bwd(const float* C3, const float* w_real, const float* w_fake, const float* u_hist,
                                      const float* v_hist, const int32_t* nits, int n, float eps, int L, const float* gloss,
-                                     float* gc3, float* dC3, void* ws, size_t ws_bytes, hipStream_t st);
+                                     float* gc3, float* dC3, void* ws, size_t ws_bytes, hipStream_t st,
+                                     float* da3 = nullptr, float* db3 = nullptr);
 
 // sinkhorn.hip: the 3 Q solves / reverse sweeps of the conditional loss (kccot_conditional.h) on ONE shared C3 [3,n,n]:
 // problem p = 3 q + k reads cost matrix k and weight row q of w [Q,n]; histories, costs, counts, gcost [3 Q] and dC
@@ -163,7 +165,7 @@ int sinkhorn_conditional_solve_fwd(const float* C3, const float* w, int Q, int n
                                    size_t ws_bytes, hipStream_t st);
 int sinkhorn_conditional_solve_bwd(const float* C3, const float* w, const float* u_hist, const float* v_hist,
                                    const int32_t* nits, int Q, int n, float eps, int L, const float* gcost, float* dC,
-                                   void* ws, size_t ws_bytes, hipStream_t st);
+                                   void* ws, size_t ws_bytes, hipStream_t st, float* da = nullptr, float* db = nullptr);
 
 // cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) over the whole batch.  bicausal selects the
 // feature-gradient jobs of the bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake,

@@ -9,6 +9,8 @@
 //   conditional_combine_fwd  loss = sum_q omega_q (2 c_q0 - c_q1 - c_q2), double, ascending q
 //   conditional_combine_bwd  gcost[3 q + k] = gloss omega_q {2,-1,-1}[k], on the device (no host round trip)
 //   conditional_dC_reduce    dC3[k] = sum_q dC_{q,k}, double, ascending q, one thread per entry
+//   conditional_dw_reduce    (kccot_weight_grad.h) dw[q] = sum_k (da_{3q+k} + db_{3q+k}), domega_q = gloss (2 c_q0 - c_q1 - c_q2)
+//   conditional_weights_bwd  (kccot_weight_grad.h) the adjoint of conditional_weights from the stored weights
 // and the host entry points, which only sequence stages (as loss.hip does).  Nothing here depends on the order in which
 // workgroups finish: there is no atomic and no ticket.
 #include "common.h"
@@ -27,8 +29,8 @@ constexpr int CW_WAVES = 4;              // rows per workgroup of conditional_we
 // The shift is taken on the distances ((D_qi - min_i D_q.) scale2 is the shifted logit in log2 units, with ONE rounding of
 // a difference instead of the difference of two rounded logits), the lanes stride over the row, exp2 is v_exp_f32.
 // NaN propagates: a NaN distance gives a NaN sum and a row of NaN weights (the comparison with the floor keeps a NaN).
-__global__ __launch_bounds__(CW_WAVES * 64) void conditional_weights(const float* __restrict__ D, int Q, int n, float scale2,
-                                                                      float* __restrict__ w) {
+__device__ __forceinline__ void conditional_weights_rows(const float* __restrict__ D, int Q, int n, float scale2,
+                                                         float* __restrict__ w) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * CW_WAVES + (threadIdx.x >> 6);
     if (row >= Q) return;                                   // wave-uniform
     const float* d = D + (int64_t)row * n;
@@ -43,6 +45,54 @@ __global__ __launch_bounds__(CW_WAVES * 64) void conditional_weights(const float
         const float r = __builtin_amdgcn_exp2f((d[j] - mn) * scale2) / s;
         o[j] = r < CW_FLOOR ? CW_FLOOR : r;
     }
+}
+__global__ __launch_bounds__(CW_WAVES * 64) void conditional_weights(const float* __restrict__ D, int Q, int n, float scale2,
+                                                                      float* __restrict__ w) {
+    conditional_weights_rows(D, Q, n, scale2, w);
+}
+
+// scale2 of a bandwidth, in double (bandwidth^2 may leave the fp32 range: a huge bandwidth gives -0 and uniform weights); the
+// host forms it with the same expression for the calls that take the bandwidth by value.  Not > 0: NaN.
+__host__ __device__ inline float cw_scale2(float bandwidth) {
+    if (!(bandwidth > 0.f)) return NAN;
+    return (float)(-1.4426950408889634 / (2.0 * (double)bandwidth * (double)bandwidth));
+}
+// the same rows with the bandwidth read from device memory (kccot_conditional_weights_dev_f32)
+__global__ __launch_bounds__(CW_WAVES * 64) void conditional_weights_dev(const float* __restrict__ D, int Q, int n,
+                                                                          const float* __restrict__ bw,
+                                                                          float* __restrict__ w) {
+    conditional_weights_rows(D, Q, n, cw_scale2(bw[0]), w);
+}
+
+// Adjoint of conditional_weights, one wave per row, from the STORED weights: with l_qi = -D_qi / (2 bw^2) and s = softmax(l),
+// w = max(s, floor); the floor has zero slope, so dl_qi = live ? w_qi (dw_qi - m_q) : 0 with m_q = sum_live w_qi dw_qi (the
+// floored entries hold < 2^-100 of the softmax's mass), dD = -dl / (2 bw^2) and dbw_q = sum_i dl_qi D_qi / bw^3.  Sums and
+// products in double.  `live` is !(w <= floor): a NaN weight is live and makes its row NaN.  bwp: the bandwidth in device
+// memory, or null for the by-value `bw`.
+__global__ __launch_bounds__(CW_WAVES * 64) void conditional_weights_bwd(const float* __restrict__ D, const float* __restrict__ w,
+                                                                          const float* __restrict__ dw, int Q, int n, float bw,
+                                                                          const float* __restrict__ bwp, float* __restrict__ dD,
+                                                                          float* __restrict__ dbw) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * CW_WAVES + (threadIdx.x >> 6);
+    if (row >= Q) return;                                   // wave-uniform
+    if (bwp) bw = bwp[0];
+    const double b = bw > 0.f ? (double)bw : (double)NAN;
+    const float* d = D + (int64_t)row * n;
+    const float* wr = w + (int64_t)row * n;
+    const float* gr = dw + (int64_t)row * n;
+    double m = 0.0;
+    for (int j = lane; j < n; j += 64)
+        if (!(wr[j] <= CW_FLOOR)) m += (double)wr[j] * (double)gr[j];
+    m = wave_sum_d(m);
+    const double inv2 = 1.0 / (2.0 * b * b);
+    double sb = 0.0;
+    for (int j = lane; j < n; j += 64) {
+        const double dl = !(wr[j] <= CW_FLOOR) ? (double)wr[j] * ((double)gr[j] - m) : 0.0;
+        dD[(int64_t)row * n + j] = (float)(-dl * inv2);
+        sb += dl * (double)d[j];
+    }
+    sb = wave_sum_d(sb);
+    if (lane == 0) dbw[row] = (float)(sb / (b * b * b));
 }
 
 __device__ __forceinline__ double query_weight(const float* omega, int q, int Q) {
@@ -83,8 +133,26 @@ __global__ __launch_bounds__(256) void conditional_dC_reduce(const float* __rest
     dC3[e] = (float)acc;
 }
 
-// workspace of the solver-level pair: gcost [3 Q] | dCp [3 Q,n,n] | the streaming solver's stage (n > 128)
+// dw[q,i] = sum_k (da[3 q + k, i] + db[3 q + k, i]) (double, k = 0, 1, 2) from the per-problem weight gradients [3 Q,n], which
+// carry gloss omega_q {2,-1,-1}[k] already; thread (q, 0) also writes domega[q] = gloss (2 c_q0 - c_q1 - c_q2) if wanted
+__global__ __launch_bounds__(256) void conditional_dw_reduce(const float* __restrict__ da, const float* __restrict__ db,
+                                                             const float* __restrict__ gloss, const float* __restrict__ cost,
+                                                             int Q, int n, float* __restrict__ dw, float* __restrict__ domega) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)Q * n) return;
+    const int q = (int)(e / n), i = (int)(e % n);
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc += (double)da[(int64_t)(3 * q + k) * n + i] + (double)db[(int64_t)(3 * q + k) * n + i];
+    dw[e] = (float)acc;
+    if (domega && i == 0)
+        domega[q] = (float)((double)gloss[0] * ((2.0 * (double)cost[3 * q] - (double)cost[3 * q + 1]) - (double)cost[3 * q + 2]));
+}
+
+// workspace of the solver-level pair: gcost [3 Q] | dCp [3 Q,n,n] | the streaming solver's stage (n > 128); the _dw backward
+// (kccot_weight_grad.h) keeps the per-problem da | db [3 Q,n] each behind it, from `total` on
 struct CondLayout { size_t off_dcp, off_gen, gen_bytes, total; };
+static size_t cond_dadb_bytes(int Q, int n) { return up256((size_t)6 * Q * n * sizeof(float)); }
 static CondLayout cond_layout(int Q, int n) {
     CondLayout l;
     l.off_dcp = up256((size_t)3 * Q * sizeof(float));
@@ -115,23 +183,30 @@ static int cond_fwd(const float* C3, const float* w, const float* omega, int Q, 
     return launch_status("conditional_combine_fwd");
 }
 
+// cost / dw_out / domega_out: the _dw backward (dw_out given: the workspace then extends by cond_dadb_bytes)
 static int cond_bwd(const float* gloss, const float* C3, const float* w, const float* omega, const float* u_hist,
                     const float* v_hist, const int32_t* nits, int Q, int n, float eps, int L, float* dC3_out, void* ws,
-                    hipStream_t st) {
+                    hipStream_t st, const float* cost = nullptr, float* dw_out = nullptr, float* domega_out = nullptr) {
     const CondLayout l = cond_layout(Q, n);
     char* base = static_cast<char*>(ws);
     float* gcost = reinterpret_cast<float*>(base);
     float* dCp = reinterpret_cast<float*>(base + l.off_dcp);
+    float* da = dw_out ? reinterpret_cast<float*>(base + l.total) : nullptr;
+    float* db = dw_out ? da + (size_t)3 * Q * n : nullptr;
     hipLaunchKernelGGL(conditional_combine_bwd, dim3((3 * Q + 255) / 256), dim3(256), 0, st, gloss, omega, Q, gcost);
     int rc = launch_status("conditional_combine_bwd");
     if (rc) return rc;
     rc = sinkhorn_conditional_solve_bwd(C3, w, u_hist, v_hist, nits, Q, n, eps, L, gcost, dCp,
-                                        l.gen_bytes ? base + l.off_gen : nullptr, l.gen_bytes, st);
+                                        l.gen_bytes ? base + l.off_gen : nullptr, l.gen_bytes, st, da, db);
     if (rc) return rc;
     const int64_t n3 = (int64_t)3 * n * n;
     hipLaunchKernelGGL(conditional_dC_reduce, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, (const float*)dCp, Q, n3,
                        dC3_out);
-    return launch_status("conditional_dC_reduce");
+    if ((rc = launch_status("conditional_dC_reduce")) || !dw_out) return rc;
+    const int64_t qn = (int64_t)Q * n;
+    hipLaunchKernelGGL(conditional_dw_reduce, dim3((unsigned)((qn + 255) / 256)), dim3(256), 0, st, (const float*)da,
+                       (const float*)db, gloss, cost, Q, n, dw_out, domega_out);
+    return launch_status("conditional_dw_reduce");
 }
 
 static size_t max3z(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
@@ -145,8 +220,7 @@ extern "C" int kccot_conditional_weights_f32(const float* D, int Q, int n, float
     if (Q < 1 || n < 1) return fail(KCCOT_EINVAL, "conditional_weights: bad shape Q=%d n=%d", Q, n);
     if (!(bandwidth > 0.f)) return fail(KCCOT_EINVAL, "conditional_weights: bandwidth=%g is not > 0", (double)bandwidth);
     if (n > CD_MAXN) return fail(KCCOT_EUNSUPPORTED, "conditional_weights: n=%d > %d", n, CD_MAXN);
-    // in double: bandwidth^2 may leave the fp32 range (a huge bandwidth gives scale2 = -0 and uniform weights)
-    const float scale2 = (float)(-1.4426950408889634 / (2.0 * (double)bandwidth * (double)bandwidth));
+    const float scale2 = cw_scale2(bandwidth);
     hipLaunchKernelGGL(conditional_weights, dim3((Q + CW_WAVES - 1) / CW_WAVES), dim3(CW_WAVES * 64), 0, (hipStream_t)stream, D,
                        Q, n, scale2, w_out);
     return launch_status("conditional_weights");
@@ -249,4 +323,103 @@ extern "C" int kccot_conditional_sinkhorn_loss_bwd_f32(const float* gloss, const
     if (rc) return rc;
     return cost3_bwd_loss(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake, dh_real,
                           dm_real, dm_fake, stage, ws_bytes - off, st, false);
+}
+
+// ---- the gradients w.r.t. the weights (include/kccot_weight_grad.h) --------------------------------------------------------
+extern "C" size_t kccot_sinkhorn_conditional_dw_workspace_bytes(int Q, int n) {
+    if (Q < 1 || n < 1 || n > CD_MAXN || Q > CD_MAXQ) return 0;
+    return cond_layout(Q, n).total + cond_dadb_bytes(Q, n);
+}
+
+extern "C" int kccot_sinkhorn_conditional_bwd_dw_f32(const float* gloss, const float* C3, const float* w, const float* omega,
+                                                     const float* u_hist, const float* v_hist, const int32_t* nits, int Q,
+                                                     int n, float eps, int L, float* dC3_out, const float* cost,
+                                                     float* dw_out, float* domega_out, void* ws, size_t ws_bytes,
+                                                     kccot_stream_t stream) {
+    const char* who = "sinkhorn_conditional_bwd_dw";
+    if (!gloss || !C3 || !w || !u_hist || !v_hist || !nits || !dC3_out || !cost || !dw_out)
+        return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    int rc = cond_check(who, Q, n, eps, L);
+    if (rc) return rc;
+    const size_t need = kccot_sinkhorn_conditional_dw_workspace_bytes(Q, n);
+    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return cond_bwd(gloss, C3, w, omega, u_hist, v_hist, nits, Q, n, eps, L, dC3_out, ws, (hipStream_t)stream, cost, dw_out,
+                    domega_out);
+}
+
+// workspace: dC3 [3,B,B], then ONE stage at a time (conditional solver with its da | db | cost backward)
+extern "C" size_t kccot_conditional_sinkhorn_loss_dw_workspace_bytes(int B, int64_t K, int Q) {
+    if (B < 1 || K < 1 || Q < 1 || B > CD_MAXN || Q > CD_MAXQ) return 0;
+    const size_t stage = max3z(kccot_pairwise_cost3_workspace_bytes(B, K), cond_layout(Q, B).total + cond_dadb_bytes(Q, B),
+                               kccot_pairwise_cost3_bwd_workspace_bytes(B, K));
+    return up256((size_t)3 * B * B * sizeof(float)) + up256(stage);
+}
+
+extern "C" int kccot_conditional_sinkhorn_loss_bwd_dw_f32(const float* gloss, const float* real, const float* fake, int B,
+                                                          int64_t K, float sc, const float* h_fake, const float* h_real,
+                                                          const float* m_real, const float* m_fake, int T, int J, float eps,
+                                                          int L, const float* w, const float* omega, int Q, const float* C3,
+                                                          const float* u_hist, const float* v_hist, const int32_t* nits,
+                                                          float* dfake, float* dh_fake, float* dh_real, float* dm_real,
+                                                          float* dm_fake, const float* cost, float* dw_out,
+                                                          float* domega_out, void* ws, size_t ws_bytes,
+                                                          kccot_stream_t stream) {
+    const char* who = "conditional_sinkhorn_loss_bwd_dw";
+    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w)
+        return fail(KCCOT_EINVAL, "%s: null input pointer", who);
+    if (!C3 || !u_hist || !v_hist || !nits || !cost || !dw_out) return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    int rc = cond_loss_check(who, B, K, T, J, Q, eps, L);
+    if (rc) return rc;
+    const size_t need = kccot_conditional_sinkhorn_loss_dw_workspace_bytes(B, K, Q);
+    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    char* base = static_cast<char*>(ws);
+    float* dC3 = reinterpret_cast<float*>(base);
+    const size_t off = up256((size_t)3 * B * B * sizeof(float));
+    void* stage = base + off;
+    const hipStream_t st = (hipStream_t)stream;
+    rc = cond_bwd(gloss, C3, w, omega, u_hist, v_hist, nits, Q, B, eps, L, dC3, stage, st, cost, dw_out, domega_out);
+    if (rc) return rc;
+    return cost3_bwd_loss(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake, dh_real,
+                          dm_real, dm_fake, stage, ws_bytes - off, st, false);
+}
+
+static int cw_bwd_check(const char* who, const void* D, const void* w, const void* dw, int Q, int n, const void* dD,
+                        const void* dbw) {
+    if (!D || !w || !dw || !dD || !dbw) return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    if (Q < 1 || n < 1) return fail(KCCOT_EINVAL, "%s: bad shape Q=%d n=%d", who, Q, n);
+    if (n > CD_MAXN) return fail(KCCOT_EUNSUPPORTED, "%s: n=%d > %d", who, n, CD_MAXN);
+    return 0;
+}
+
+extern "C" int kccot_conditional_weights_bwd_f32(const float* D, const float* w, const float* dw, int Q, int n,
+                                                 float bandwidth, float* dD_out, float* dbw_out, kccot_stream_t stream) {
+    const char* who = "conditional_weights_bwd";
+    int rc = cw_bwd_check(who, D, w, dw, Q, n, dD_out, dbw_out);
+    if (rc) return rc;
+    if (!(bandwidth > 0.f)) return fail(KCCOT_EINVAL, "%s: bandwidth=%g is not > 0", who, (double)bandwidth);
+    hipLaunchKernelGGL(conditional_weights_bwd, dim3((Q + CW_WAVES - 1) / CW_WAVES), dim3(CW_WAVES * 64), 0,
+                       (hipStream_t)stream, D, w, dw, Q, n, bandwidth, (const float*)nullptr, dD_out, dbw_out);
+    return launch_status(who);
+}
+
+extern "C" int kccot_conditional_weights_bwd_dev_f32(const float* D, const float* w, const float* dw, int Q, int n,
+                                                     const float* bandwidth, float* dD_out, float* dbw_out,
+                                                     kccot_stream_t stream) {
+    const char* who = "conditional_weights_bwd_dev";
+    int rc = cw_bwd_check(who, D, w, dw, Q, n, dD_out, dbw_out);
+    if (rc) return rc;
+    if (!bandwidth) return fail(KCCOT_EINVAL, "%s: null bandwidth pointer", who);
+    hipLaunchKernelGGL(conditional_weights_bwd, dim3((Q + CW_WAVES - 1) / CW_WAVES), dim3(CW_WAVES * 64), 0,
+                       (hipStream_t)stream, D, w, dw, Q, n, 0.f, bandwidth, dD_out, dbw_out);
+    return launch_status(who);
+}
+
+extern "C" int kccot_conditional_weights_dev_f32(const float* D, int Q, int n, const float* bandwidth, float* w_out,
+                                                 kccot_stream_t stream) {
+    if (!D || !w_out || !bandwidth) return fail(KCCOT_EINVAL, "conditional_weights_dev: null pointer");
+    if (Q < 1 || n < 1) return fail(KCCOT_EINVAL, "conditional_weights_dev: bad shape Q=%d n=%d", Q, n);
+    if (n > CD_MAXN) return fail(KCCOT_EUNSUPPORTED, "conditional_weights_dev: n=%d > %d", n, CD_MAXN);
+    hipLaunchKernelGGL(conditional_weights_dev, dim3((Q + CW_WAVES - 1) / CW_WAVES), dim3(CW_WAVES * 64), 0,
+                       (hipStream_t)stream, D, Q, n, bandwidth, w_out);
+    return launch_status("conditional_weights_dev");
 }

@@ -1,7 +1,8 @@
 // compute_sinkhorn_loss (gan_utils.py:204-227) as ONE host call each way: the launch sequence
 // cost assembly -> three Sinkhorn solves + combination (forward) and reverse sweep -> cost backward
 // (backward) is issued from C, so a caller pays one FFI crossing and one workspace per direction
-// instead of one per stage.  No new kernels: these entry points only sequence the stage functions.
+// instead of one per stage.  No new kernels (but the B-thread combination of the weight gradients at the end of the file):
+// these entry points only sequence the stage functions.
 // The bi-causal loss (bicausal.hip) runs the same sequence with one launch more in the forward (its second causal terms)
 // and its own feature-gradient jobs in the cost backward.
 #include "common.h"
@@ -42,7 +43,7 @@ static int loss3_bwd(bool bicausal, const float* gloss, const float* real, const
                      float eps, int L, const float* C3, const float* u_hist, const float* v_hist, const int32_t* nits,
                      const float* dC3_unit, float* dfake, float* dh_fake, float* dh_real, float* dm_real, float* dm_fake,
                      void* ws, size_t ws_bytes, kccot_stream_t stream, const float* w_real = nullptr,
-                     const float* w_fake = nullptr) {
+                     const float* w_fake = nullptr, float* da3 = nullptr, float* db3 = nullptr) {
     const hipStream_t st = (hipStream_t)stream;
     if (dC3_unit)
         return cost3_bwd_loss(dC3_unit, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake,
@@ -56,7 +57,7 @@ static int loss3_bwd(bool bicausal, const float* gloss, const float* real, const
     int rc;
     if (w_real) {
         rc = sinkhorn_divergence_weighted_bwd(C3, w_real, w_fake, u_hist, v_hist, nits, B, eps, L, gloss, gc, dC3, stage,
-                                              stage_bytes, st);
+                                              stage_bytes, st, da3, db3);
     } else if (kccot_sinkhorn_workspace_bytes(3, B) > 0) {
         // streaming solver (n > 128): weights {2,-1,-1} * gloss first, then the generic reverse sweep
         rc = kccot_mixed_divergence_bwd_f32(gloss, gc, stream);
@@ -68,6 +69,16 @@ static int loss3_bwd(bool bicausal, const float* gloss, const float* real, const
     if (rc) return rc;
     return cost3_bwd_loss(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake, dh_real,
                           dm_real, dm_fake, stage, stage_bytes, st, bicausal);
+}
+
+// dw_real = da_xy + (da_xx + db_xx), dw_fake = db_xy + (da_yy + db_yy) from the per-problem weight gradients da3, db3 [3,B]
+// of the weighted divergence (each already scaled by gloss {2,-1,-1}[k]); double, in that order
+__global__ __launch_bounds__(256) void weighted_dw_combine(const float* __restrict__ da3, const float* __restrict__ db3, int B,
+                                                           float* __restrict__ dw_real, float* __restrict__ dw_fake) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    dw_real[i] = (float)((double)da3[i] + ((double)da3[B + i] + (double)db3[B + i]));
+    dw_fake[i] = (float)((double)db3[i] + ((double)da3[2 * B + i] + (double)db3[2 * B + i]));
 }
 }  // namespace kccot
 using namespace kccot;
@@ -235,4 +246,41 @@ extern "C" int kccot_weighted_sinkhorn_loss_bwd_f32(const float* gloss, const fl
                     kccot_weighted_sinkhorn_loss_workspace_bytes(B, K));
     return loss3_bwd(false, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, C3, u_hist, v_hist,
                      nits, nullptr, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, ws_bytes, stream, w_real, w_fake);
+}
+
+// ---- the same backward with the gradient w.r.t. the two weight vectors (include/kccot_weight_grad.h) --------------------
+// workspace: the layout of kccot_weighted_sinkhorn_loss_bwd_f32, then da3 | db3 [3,B] each
+extern "C" size_t kccot_weighted_sinkhorn_loss_dw_workspace_bytes(int B, int64_t K) {
+    const size_t base = kccot_weighted_sinkhorn_loss_workspace_bytes(B, K);
+    return base ? base + up256((size_t)6 * B * sizeof(float)) : 0;
+}
+
+extern "C" int kccot_weighted_sinkhorn_loss_bwd_dw_f32(const float* gloss, const float* real, const float* fake, int B,
+                                                       int64_t K, float sc, const float* h_fake, const float* h_real,
+                                                       const float* m_real, const float* m_fake, int T, int J, float eps,
+                                                       int L, const float* w_real, const float* w_fake, const float* C3,
+                                                       const float* u_hist, const float* v_hist, const int32_t* nits,
+                                                       float* dfake, float* dh_fake, float* dh_real, float* dm_real,
+                                                       float* dm_fake, float* dw_real, float* dw_fake, void* ws,
+                                                       size_t ws_bytes, kccot_stream_t stream) {
+    const char* who = "weighted_sinkhorn_loss_bwd_dw";
+    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w_real || !w_fake)
+        return fail(KCCOT_EINVAL, "%s: null input pointer", who);
+    if (!C3 || !u_hist || !v_hist || !nits) return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    if (!dw_real || !dw_fake) return fail(KCCOT_EINVAL, "%s: null dw_real / dw_fake", who);
+    if (B <= 0 || K <= 0 || T < 1 || J < 1 || L < 0 || !(eps > 0.f))
+        return fail(KCCOT_EINVAL, "%s: bad arguments B=%d K=%lld T=%d J=%d L=%d eps=%g", who, B, (long long)K, T, J, L,
+                    (double)eps);
+    if (B > 1024) return fail(KCCOT_EUNSUPPORTED, "%s: B=%d > 1024", who, B);
+    const size_t need = kccot_weighted_sinkhorn_loss_dw_workspace_bytes(B, K);
+    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    const size_t base = kccot_weighted_sinkhorn_loss_workspace_bytes(B, K);
+    float* da3 = reinterpret_cast<float*>(static_cast<char*>(ws) + base);
+    float* db3 = da3 + (size_t)3 * B;
+    int rc = loss3_bwd(false, gloss, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, eps, L, C3, u_hist, v_hist,
+                       nits, nullptr, dfake, dh_fake, dh_real, dm_real, dm_fake, ws, base, stream, w_real, w_fake, da3, db3);
+    if (rc) return rc;
+    hipLaunchKernelGGL(weighted_dw_combine, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)da3,
+                       (const float*)db3, B, dw_real, dw_fake);
+    return launch_status("weighted_dw_combine");
 }

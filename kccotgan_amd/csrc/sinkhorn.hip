@@ -421,6 +421,8 @@ struct SinkBwdArgs {
     const float* wa;      // weighted marginals as in SinkArgs (sinkhorn_bwd_reg_w only); w_div = 2: C is the shared C3
     const float* wb;
     int w_div;
+    float* da;            // [nprob,n] dcost/da, dcost/db scaled by gcost (the _dw kernels only; see sinkhorn_bwd_body)
+    float* db;
 };
 
 // WEIGHTED (mu = a, nu = b): the column sums of the second argument are b_j and the row sums of the first a_i, so
@@ -430,8 +432,24 @@ struct SinkBwdArgs {
 // ones, so a pass costs the same instructions as with the constant; everything else is unchanged (log a and log b enter
 // the updates additively; the weights themselves are not differentiated).  A problem the forward poisoned (nits < 0: a
 // weight <= 0 or not finite) gets NaN gradients.
-template <int EPT, int LPR, bool WEIGHTED>
+// DW (with WEIGHTED; include/kccot_weight_grad.h): the weights ARE differentiated.  u_t = eps log a + (terms without a direct
+// a), v_t = eps log b + (...), so with gu_t the adjoint of u_t that gu[] holds after pass A of iteration t and gv_t the
+// adjoint of v_t that gv[] holds when pass A of iteration t starts (gv_nits: the final-cost term)
+//   dcost/da_i = (eps / a_i) sum_{t=1..nits} gu_t[i],      dcost/db_j = (eps / b_j) sum_{t=1..nits} gv_t[j]
+// (what pass B writes at it == 1 is the adjoint of the constant v_0 = 0 and is not added).  The two running sums live in
+// LDS beside gu / gv, in double, entry `line` touched only by the thread that writes gu[line] / gv[line]: one private
+// read-add-write per line and half-step, no atomic, no barrier of its own, nothing on the dependent chain.  The factor
+// eps / a_i is applied once, at the end.  dC is computed by the same instructions as without DW.
+// The conserved mode.  Q_t has column sums 1 and P_t row sums 1, so sum_i gu_t[i] = -sum_j gv_t[j] and sum_j gv_{t-1}[j] =
+// -sum_i gu_t[i]: the total of the adjoints is handed on unchanged from half-step to half-step, and it starts at
+// sum_i gu_nits[i] = g cost/eps - g cost/eps = 0.  Exactly, every total is therefore zero (but that of gv_nits); in fp32 the
+// first one is a rounding residue, it never decays (eigenvalue 1), and nits copies of it end up in the sums -- the one error
+// of da / db that grows with the iteration count.  Its shape is known (a_i in gu, b_j in gv, the marginals of the plans), and
+// so is its true amplitude (zero), so it is removed at the end: sa_i -= a_i sum(sa) / sum(a), likewise sb without the
+// final-cost term, which is kept apart in gvf[].  One wave, once per launch, after the loop.
+template <int EPT, int LPR, bool WEIGHTED, bool DW = false>
 __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
+    static_assert(WEIGHTED || !DW, "the weight gradient belongs to the weighted sweep");
     constexpr int PADN = SK_MAXN + 16 * 16;
     __shared__ __attribute__((aligned(16))) float Ua[WEIGHTED ? 2 : 1][WEIGHTED ? PADN : 4];
     __shared__ __attribute__((aligned(16))) float Va[WEIGHTED ? 2 : 1][WEIGHTED ? PADN : 4];
@@ -440,6 +458,9 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
     __shared__ __attribute__((aligned(16))) float V[2][PADN];
     __shared__ __attribute__((aligned(16))) float gu[PADN];
     __shared__ __attribute__((aligned(16))) float gv[PADN];
+    __shared__ double sab[DW ? 2 : 1][DW ? SK_MAXN : 1];                // sum_t gu_t, sum_{t<nits} gv_t: entry `line` is its owner's alone
+    __shared__ float gvf[DW ? SK_MAXN : 1];                             // gv_nits, the final-cost term
+    __shared__ double mode[DW ? 2 : 1];                                 // amplitude of the conserved mode in sab[0], sab[1]
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, line = t / LPR, q = t % LPR;
     const bool active = line < n;
@@ -459,6 +480,9 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
                     const int idx = q * EPT + m;
                     if (idx < n) a.dC[(int64_t)p * n * n + (int64_t)line * n + idx] = NAN;
                 }
+                if constexpr (DW) {
+                    if (q == 0) { a.da[(int64_t)p * n + line] = NAN; a.db[(int64_t)p * n + line] = NAN; }
+                }
             }
             return;
         }
@@ -477,6 +501,7 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
         gu[i] = gv[i] = 0.f;
         if constexpr (WEIGHTED) Ua[0][i] = Ua[1][i] = Va[0][i] = Va[1][i] = 0.f;
     }
+    if constexpr (DW) { if (t < SK_MAXN) sab[0][t] = sab[1][t] = 0.0; }
     __syncthreads();
     // history index k holds (U_{k+1}, V_{k+1}); iteration `it` (1-based) lives in slot it & 1;
     // V_0 = 0
@@ -520,7 +545,11 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
         }
         su = seg_sum<LPR>(su);
         sv = seg_sum<LPR>(sv);
-        if (active && q == 0) { gu[line] = g * su * LN2; gv[line] = g * sv * LN2; }
+        if (active && q == 0) {
+            const float gvn = g * sv * LN2;
+            gu[line] = g * su * LN2; gv[line] = gvn;
+            if constexpr (DW) gvf[line] = nits > 0 ? gvn : 0.f;                  // with no iteration v = v_0, a constant
+        }
     }
     const float lw2 = __builtin_amdgcn_logf(1.0f / (float)n);
     __syncthreads();
@@ -545,7 +574,11 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
             }
             s = seg_sum<LPR>(s);
             // grad wrt u_t: the final-cost term on the last iteration, nothing on older ones
-            if (active && q == 0) gu[line] = (it == nits ? gu[line] : 0.f) - s;
+            if (active && q == 0) {
+                const float gun = (it == nits ? gu[line] : 0.f) - s;
+                gu[line] = gun;
+                if constexpr (DW) sab[0][line] += (double)gun;
+            }
         }
         lds_barrier();      // LDS-only: the history prefetch (nu, nv) stays in flight across it
         // refill the slots the older iteration needs: U[(it-1)&1] <- U_{it-1}, V[it&1] <- V_{it-2}
@@ -571,11 +604,33 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
                 r += w;
             }
             r = seg_sum<LPR>(r);
-            if (active && q == 0) gv[line] = -r;
+            if (active && q == 0) {
+                gv[line] = -r;
+                if constexpr (DW) { if (it > 1) sab[1][line] += (double)(-r); }   // it == 1: the adjoint of v_0 = 0, not added
+            }
         }
         lds_barrier();
     }
 
+    if constexpr (DW) {
+        const float* pa = weights_of(a.wa, a.wb, a.w_div, p, n, true);
+        const float* pb = weights_of(a.wa, a.wb, a.w_div, p, n, false);
+        if (t < 64) {     // (the loop's closing barrier, or the one before it, made every entry of sab visible)
+            double ea = 0.0, eb = 0.0, ta = 0.0, tb = 0.0;
+            for (int i = t; i < n; i += 64) { ea += sab[0][i]; eb += sab[1][i]; ta += (double)pa[i]; tb += (double)pb[i]; }
+            ea = wave_sum_d(ea); eb = wave_sum_d(eb); ta = wave_sum_d(ta); tb = wave_sum_d(tb);
+            if (t == 0) { mode[0] = ea / ta; mode[1] = eb / tb; }
+        }
+        __syncthreads();
+        if (active && q == 0) {
+            // da, db are read from the kernel arguments HERE, not with the others at the top: two pointers fewer in SGPRs
+            // through the loop (the EPT = 16 forms are short of them too)
+            const SinkBwdArgs* ka = (const SinkBwdArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+            const double wa = (double)pa[line], wb = (double)pb[line];
+            ka->da[(int64_t)p * n + line] = (float)((double)a.eps * (sab[0][line] - mode[0] * wa) / wa);
+            ka->db[(int64_t)p * n + line] = (float)((double)a.eps * (((double)gvf[line] + sab[1][line]) - mode[1] * wb) / wb);
+        }
+    }
     // dC = row-layout part + (column-layout part)^T
     float* dC = a.dC + (int64_t)p * n * n;
     if (active) {
@@ -600,6 +655,9 @@ template <int EPT, int LPR>
 __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg(SinkBwdArgs a) { sinkhorn_bwd_body<EPT, LPR, false>(a); }
 template <int EPT, int LPR>
 __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg_w(SinkBwdArgs a) { sinkhorn_bwd_body<EPT, LPR, true>(a); }
+// the weighted sweep that also writes da, db (include/kccot_weight_grad.h)
+template <int EPT, int LPR>
+__global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg_dw(SinkBwdArgs a) { sinkhorn_bwd_body<EPT, LPR, true, true>(a); }
 
 // ------------------------------------------------------------------------------------------
 // Fused solve + reverse sweep of the mixed divergence (compute_sinkhorn_loss when a gradient is wanted):
@@ -1225,7 +1283,7 @@ int launch_sinkhorn_fwd_gen(const float* C, int nprob, int n, float eps, int L, 
                             size_t ws_bytes, hipStream_t st, const float* wa, const float* wb, int w_div);
 int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
                             float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st,
-                            const float* wa, const float* wb, int w_div);
+                            const float* wa, const float* wb, int w_div, float* da, float* db);
 }  // namespace kccot
 
 using namespace kccot;
@@ -1328,9 +1386,11 @@ extern "C" int kccot_sinkhorn_status(const int32_t* nits, int nprob, kccot_strea
 static int sinkhorn_bwd(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
                         float eps, int L, const float* gcost, float* dC_out, void* ws, size_t ws_bytes,
                         kccot_stream_t stream, int div_weights, const float* wa = nullptr, const float* wb = nullptr,
-                        int w_div = 0) {
+                        int w_div = 0, float* da = nullptr, float* db = nullptr) {
     if (!C || !u_hist || !v_hist || !nits || !gcost || !dC_out)
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: null pointer");
+    if ((da == nullptr) != (db == nullptr) || (da && !wa))
+        return fail(KCCOT_EINVAL, "sinkhorn_bwd: da and db are given together, with the weights");
     if ((wa == nullptr) != (wb == nullptr)) return fail(KCCOT_EINVAL, "sinkhorn_bwd: give both weight vectors or neither");
     if (w_div == 1 && nprob != 3) return fail(KCCOT_EINVAL, "sinkhorn_bwd: the divergence's weights need nprob = 3");
     if (w_div == 2 && nprob % 3) return fail(KCCOT_EINVAL, "sinkhorn_bwd: the conditional mode needs nprob = 3 Q");
@@ -1338,10 +1398,15 @@ static int sinkhorn_bwd(const float* C, const float* u_hist, const float* v_hist
         return fail(KCCOT_EINVAL, "sinkhorn_bwd: bad arguments nprob=%d n=%d L=%d eps=%g", nprob, n, L, (double)eps);
     if (n > SK_MAXN)
         return launch_sinkhorn_bwd_gen(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes,
-                                       (hipStream_t)stream, wa, wb, w_div);
+                                       (hipStream_t)stream, wa, wb, w_div, da, db);
     SinkGeom g = sink_geom(n, false);
-    SinkBwdArgs a{C, u_hist, v_hist, nits, gcost, dC_out, n, L, eps, (float)(1.0 / (double)eps), div_weights, wa, wb, w_div};
+    SinkBwdArgs a{C, u_hist, v_hist, nits, gcost, dC_out, n, L, eps, (float)(1.0 / (double)eps), div_weights, wa, wb, w_div,
+                  da, db};
     hipStream_t st = (hipStream_t)stream;
+    if (da) {
+        KCCOT_SK_DISPATCH(sinkhorn_bwd_reg_dw, a, g, nprob, st)
+        return launch_status("sinkhorn_bwd_reg_dw");
+    }
     if (wa) {
         KCCOT_SK_DISPATCH(sinkhorn_bwd_reg_w, a, g, nprob, st)
         return launch_status("sinkhorn_bwd_reg_w");
@@ -1524,6 +1589,17 @@ extern "C" int kccot_sinkhorn_weighted_bwd_f32(const float* C, const float* a, c
     return sinkhorn_bwd(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes, stream, 0, a, b, 0);
 }
 
+// the same sweep, which also writes dcost/da and dcost/db [nprob,n] scaled by gcost (include/kccot_weight_grad.h)
+extern "C" int kccot_sinkhorn_weighted_bwd_dw_f32(const float* C, const float* a, const float* b, const float* u_hist,
+                                                  const float* v_hist, const int32_t* nits, int nprob, int n, float eps,
+                                                  int L, const float* gcost, float* dC_out, float* da_out, float* db_out,
+                                                  void* ws, size_t ws_bytes, kccot_stream_t stream) {
+    if (!a || !b) return fail(KCCOT_EINVAL, "sinkhorn_weighted_bwd_dw: null weight pointer");
+    if (!da_out || !db_out) return fail(KCCOT_EINVAL, "sinkhorn_weighted_bwd_dw: null da_out / db_out");
+    return sinkhorn_bwd(C, u_hist, v_hist, nits, nprob, n, eps, L, gcost, dC_out, ws, ws_bytes, stream, 0, a, b, 0, da_out,
+                        db_out);
+}
+
 // the three solves of the weighted divergence on C3 = [xy, xx, yy] with marginals (a,b), (a,a), (b,b), a = w_real,
 // b = w_fake, and loss = 2 xy - xx - yy (loss.hip)
 int kccot::sinkhorn_divergence_weighted_fwd(const float* C3, const float* w_real, const float* w_fake, int n, float eps,
@@ -1541,18 +1617,20 @@ int kccot::sinkhorn_divergence_weighted_fwd(const float* C3, const float* w_real
                         ws_bytes, st, loss_out, reinterpret_cast<int*>(ticket), w_real, w_fake, 1);
 }
 
-// dC3 = d loss / d C3 scaled by gloss[0]; gc3: three floats of scratch (the per-problem weights, n > 128 only)
+// dC3 = d loss / d C3 scaled by gloss[0]; gc3: three floats of scratch (the per-problem weights, n > 128 only); da3, db3
+// [3,n] (both or neither): the weight gradients of the three problems, scaled by gloss {2,-1,-1}
 int kccot::sinkhorn_divergence_weighted_bwd(const float* C3, const float* w_real, const float* w_fake, const float* u_hist,
                                             const float* v_hist, const int32_t* nits, int n, float eps, int L,
                                             const float* gloss, float* gc3, float* dC3, void* ws, size_t ws_bytes,
-                                            hipStream_t st) {
+                                            hipStream_t st, float* da3, float* db3) {
     if (!w_real || !w_fake || !gloss || !gc3) return fail(KCCOT_EINVAL, "weighted divergence backward: null pointer");
     if (n > SK_MAXN) {
         int rc = kccot_mixed_divergence_bwd_f32(gloss, gc3, st);
         if (rc) return rc;
-        return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gc3, dC3, ws, ws_bytes, st, 0, w_real, w_fake, 1);
+        return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gc3, dC3, ws, ws_bytes, st, 0, w_real, w_fake, 1, da3,
+                            db3);
     }
-    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3, ws, ws_bytes, st, 1, w_real, w_fake, 1);
+    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3, n, eps, L, gloss, dC3, ws, ws_bytes, st, 1, w_real, w_fake, 1, da3, db3);
 }
 
 // ---- conditional mode (include/kccot_conditional.h, conditional.hip) ------------------------------------------------------
@@ -1565,9 +1643,10 @@ int kccot::sinkhorn_conditional_solve_fwd(const float* C3, const float* w, int Q
                         ws_bytes, st, nullptr, nullptr, w, w, 2);
 }
 
-// gcost [3 Q]: the upstream gradient of every problem's cost; dC [3 Q,n,n]: the per-problem gradients
+// gcost [3 Q]: the upstream gradient of every problem's cost; dC [3 Q,n,n]: the per-problem gradients; da, db [3 Q,n] (both
+// or neither): the per-problem weight gradients
 int kccot::sinkhorn_conditional_solve_bwd(const float* C3, const float* w, const float* u_hist, const float* v_hist,
                                           const int32_t* nits, int Q, int n, float eps, int L, const float* gcost, float* dC,
-                                          void* ws, size_t ws_bytes, hipStream_t st) {
-    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3 * Q, n, eps, L, gcost, dC, ws, ws_bytes, st, 0, w, w, 2);
+                                          void* ws, size_t ws_bytes, hipStream_t st, float* da, float* db) {
+    return sinkhorn_bwd(C3, u_hist, v_hist, nits, 3 * Q, n, eps, L, gcost, dC, ws, ws_bytes, st, 0, w, w, 2, da, db);
 }

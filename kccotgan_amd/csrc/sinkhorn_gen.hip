@@ -446,6 +446,8 @@ struct SinkGenBwdArgs {
     const float* wa;     // weighted marginals as in SinkGenArgs (sinkhorn_bwd_gen<true> only)
     const float* wb;
     int w_div;
+    float* da;           // [nprob,n] dcost/da, dcost/db scaled by gcost (sinkhorn_bwd_gen<true, true> only)
+    float* db;
 };
 
 // See sinkhorn.hip for the derivation.  Accumulators live in global memory (L2): the row pass
@@ -454,10 +456,18 @@ struct SinkGenBwdArgs {
 // W (mu = a, nu = b): the column sums that normalise Q_t are b_j and the row sums that normalise P_t are a_i, so the
 // constant eps*log(1/n) becomes eps*log b_j in pass A and eps*log a_i in pass B (staged in LDS once).  A problem the
 // forward poisoned (nits < 0) gets NaN gradients.
-template <bool W>
+// DW (with W; include/kccot_weight_grad.h): also da = (eps / a) sum_t gu_t and db = (eps / b) sum_t gv_t, as in
+// sinkhorn_bwd_body: the two sums are kept in LDS in double, entry i touched only by lane 0 of the wave that owns line i (the
+// same wave in the row pass and in the column pass), and scaled once at the end, after the conserved mode of the adjoints
+// (true amplitude zero, shape a_i / b_j: see sinkhorn_bwd_body) has been removed; gv_nits is kept apart in gvf_s.
+template <bool W, bool DW = false>
 __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a) {
+    static_assert(W || !DW, "the weight gradient belongs to the weighted sweep");
     __shared__ float ut[SG_MAXN], vt[SG_MAXN], vp[SG_MAXN], gu[SG_MAXN], gv[SG_MAXN];
     __shared__ float ea_s[W ? SG_MAXN : 1], eb_s[W ? SG_MAXN : 1];
+    __shared__ double sa_s[DW ? SG_MAXN : 1], sb_s[DW ? SG_MAXN : 1];
+    __shared__ float gvf_s[DW ? SG_MAXN : 1];
+    __shared__ double mode[DW ? 2 : 1];
     const int p = blockIdx.x, n = a.n;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6, nw = SG_THREADS / 64;
     int pc = p;          // the cost matrix this problem reads: its own, or (conditional mode) matrix p % 3 of the shared C3
@@ -473,6 +483,9 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
     if constexpr (W) {
         if (nits < 0) {          // block-uniform
             for (int64_t e = t; e < (int64_t)n * n; e += SG_THREADS) { dC[e] = NAN; dCT[e] = 0.f; }
+            if constexpr (DW) {
+                for (int i = t; i < n; i += SG_THREADS) { a.da[(int64_t)p * n + i] = NAN; a.db[(int64_t)p * n + i] = NAN; }
+            }
             return;
         }
         gen_stage_weights(a.wa, a.wb, a.w_div, p, n, eps, ea_s, eb_s);
@@ -480,6 +493,7 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
     for (int i = t; i < n; i += SG_THREADS) {
         ut[i] = nits > 0 ? uh[(int64_t)(nits - 1) * n + i] : 0.f;
         vt[i] = nits > 0 ? vh[(int64_t)(nits - 1) * n + i] : 0.f;
+        if constexpr (DW) { sa_s[i] = 0.0; sb_s[i] = 0.0; }
     }
     __syncthreads();
     // final cost term: dC = g*pi*(1 - C/eps); gu = g*sum_j pi C/eps; gv likewise; dCT = 0
@@ -505,7 +519,11 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
             sv += pc * c;
         }
         sv = wave_sum(sv);
-        if (lane == 0) gv[j] = g * sv * inv_eps;
+        if (lane == 0) {
+            const float gvf = g * sv * inv_eps;
+            gv[j] = gvf;
+            if constexpr (DW) gvf_s[j] = nits > 0 ? gvf : 0.f;                  // with no iteration v = v_0, a constant
+        }
     }
     const float aconst = eps * logf(1.0f / (float)n);
     for (int it = nits; it >= 1; --it) {
@@ -528,7 +546,11 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
                 s += w;
             }
             s = wave_sum(s);
-            if (lane == 0) gu[i] = (it == nits ? gu[i] : 0.f) - s;
+            if (lane == 0) {
+                const float gun = (it == nits ? gu[i] : 0.f) - s;
+                gu[i] = gun;
+                if constexpr (DW) sa_s[i] += (double)gun;
+            }
         }
         __syncthreads();
         // (B) column pass with P_t: gv_j = -sum_i P_ij gu_i ; dC_ij += P_ij gu_i (kept transposed)
@@ -543,7 +565,27 @@ __global__ __launch_bounds__(SG_THREADS) void sinkhorn_bwd_gen(SinkGenBwdArgs a)
                 r += w;
             }
             r = wave_sum(r);
-            if (lane == 0) gv[j] = -r;
+            if (lane == 0) {
+                gv[j] = -r;
+                if constexpr (DW) { if (it > 1) sb_s[j] += (double)(-r); }        // it == 1: the adjoint of v_0 = 0, not added
+            }
+        }
+    }
+    if constexpr (DW) {
+        const float* pa = gen_weights_of(a.wa, a.wb, a.w_div, p, n, true);
+        const float* pb = gen_weights_of(a.wa, a.wb, a.w_div, p, n, false);
+        __syncthreads();
+        if (wid == 0) {
+            double ea = 0.0, eb = 0.0, ta = 0.0, tb = 0.0;
+            for (int i = lane; i < n; i += 64) { ea += sa_s[i]; eb += sb_s[i]; ta += (double)pa[i]; tb += (double)pb[i]; }
+            ea = wave_sum_d(ea); eb = wave_sum_d(eb); ta = wave_sum_d(ta); tb = wave_sum_d(tb);
+            if (lane == 0) { mode[0] = ea / ta; mode[1] = eb / tb; }
+        }
+        __syncthreads();
+        for (int i = t; i < n; i += SG_THREADS) {
+            const double wa = (double)pa[i], wb = (double)pb[i];
+            a.da[(int64_t)p * n + i] = (float)((double)eps * (sa_s[i] - mode[0] * wa) / wa);
+            a.db[(int64_t)p * n + i] = (float)((double)eps * (((double)gvf_s[i] + sb_s[i]) - mode[1] * wb) / wb);
         }
     }
 }
@@ -599,7 +641,7 @@ int launch_sinkhorn_fwd_gen(const float* C, int nprob, int n, float eps, int L, 
 
 int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_hist, const int32_t* nits, int nprob, int n,
                             float eps, int L, const float* gcost, float* dC, void* ws, size_t ws_bytes, hipStream_t st,
-                            const float* wa, const float* wb, int w_div) {
+                            const float* wa, const float* wb, int w_div, float* da, float* db) {
     if (n > SG_MAXN) return fail(KCCOT_EUNSUPPORTED, "sinkhorn_bwd: n=%d > %d", n, SG_MAXN);
     const size_t need = w_div == 2 ? sinkhorn_gen_conditional_workspace_bytes(nprob / 3, n) : sinkhorn_gen_workspace_bytes(nprob, n);
     if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "sinkhorn_bwd: workspace %zu < required %zu", ws_bytes, need);
@@ -612,8 +654,9 @@ int launch_sinkhorn_bwd_gen(const float* C, const float* u_hist, const float* v_
     hipLaunchKernelGGL(transpose_batched, tc, dim3(256), 0, st, C, CT, n);
     int rc = launch_status("transpose_batched");
     if (rc) return rc;
-    SinkGenBwdArgs a{C, CT, u_hist, v_hist, nits, gcost, dC, dCT, n, L, eps, (float)(1.0 / (double)eps), wa, wb, w_div};
-    if (wa) hipLaunchKernelGGL(sinkhorn_bwd_gen<true>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    SinkGenBwdArgs a{C, CT, u_hist, v_hist, nits, gcost, dC, dCT, n, L, eps, (float)(1.0 / (double)eps), wa, wb, w_div, da, db};
+    if (da) hipLaunchKernelGGL((sinkhorn_bwd_gen<true, true>), dim3(nprob), dim3(SG_THREADS), 0, st, a);
+    else if (wa) hipLaunchKernelGGL(sinkhorn_bwd_gen<true>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
     else hipLaunchKernelGGL(sinkhorn_bwd_gen<false>, dim3(nprob), dim3(SG_THREADS), 0, st, a);
     if ((rc = launch_status("sinkhorn_bwd_gen"))) return rc;
     hipLaunchKernelGGL(add_transposed_batched, tg, dim3(256), 0, st, (const float*)dCT, dC, n);

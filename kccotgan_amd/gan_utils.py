@@ -19,7 +19,8 @@ __all__ = ["cost_xy", "modified_cost", "bi_causal_modified_cost", "benchmark_sin
            "compute_sinkhorn", "compute_N", "scale_invariante_martingale_regularization",
            "compute_sinkhorn_loss", "compute_mixed_sinkhorn_loss", "compute_bicausal_sinkhorn_loss",
            "compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss", "kernel_conditional_weights",
-           "compute_conditional_sinkhorn_loss", "last_info", "raise_if_solver_aborted"]
+           "compute_conditional_sinkhorn_loss", "compute_kernel_conditional_sinkhorn_loss", "last_info",
+           "raise_if_solver_aborted"]
 
 # executed Sinkhorn iteration counts (device int32 tensors, no host sync) of the latest calls;
 # the reference keeps them in a local (gan_utils.py:148,158) although its docstring promises them
@@ -393,12 +394,11 @@ def _weighted_path(n):
 
 
 def _weights(w, n, name, normalize):
-    """A weight vector as contiguous fp32 [n] on the device; ``normalize`` divides by its sum there (no host sync)."""
+    """A weight vector as contiguous fp32 [n] on the device; ``normalize`` divides by its sum there (no host sync).  Plain
+    torch operations: a gradient w.r.t. the returned vector reaches ``w`` through them."""
     if not torch.is_tensor(w):
         raise TypeError("%s must be a tensor of %d weights" % (name, n))
     _lib.require_gpu(w)
-    if w.requires_grad:
-        raise NotImplementedError("%s: the weighted Sinkhorn solver does not differentiate w.r.t. the weights" % name)
     if w.dim() != 1 or w.shape[0] != n:
         raise ValueError("%s must be [%d], got %s" % (name, n, tuple(w.shape)))
     w = w if w.dtype == torch.float32 else w.float()
@@ -408,14 +408,15 @@ def _weights(w, n, name, normalize):
 
 
 class _WeightedSinkhorn(torch.autograd.Function):
-    """_Sinkhorn with marginals a, b [nprob,n] (kccot_sinkhorn_weighted_fwd_f32 / _bwd_f32); no gradient to a, b."""
+    """_Sinkhorn with marginals a, b [nprob,n] (kccot_sinkhorn_weighted_fwd_f32 / _bwd_f32); when a or b wants a gradient the
+    backward is kccot_sinkhorn_weighted_bwd_dw_f32 (include/kccot_weight_grad.h: the same dC bits, plus da, db)."""
 
     @staticmethod
     def forward(ctx, C, a, b, eps, L, Lmin, stop_mode, tag):
         nprob, n, _ = C.shape
         C = C.contiguous()
         dev = C.device
-        keep = ctx.needs_input_grad[0]
+        keep = any(ctx.needs_input_grad[:3])
         Lh = max(int(L), 1)
         u_hist = _lib.empty((nprob, Lh, n), torch.float32, dev) if keep else None
         v_hist = _lib.empty((nprob, Lh, n), torch.float32, dev) if keep else None
@@ -439,6 +440,14 @@ class _WeightedSinkhorn(torch.autograd.Function):
         gcost = gcost.contiguous().float()
         dC = _lib.empty_like(C)
         ws, wsb = workspace(lib.kccot_sinkhorn_workspace_bytes(nprob, n), C)
+        need = ctx.needs_input_grad
+        if need[1] or need[2]:
+            dab = _lib.empty((2, nprob, n), torch.float32, C.device)
+            check(lib.kccot_sinkhorn_weighted_bwd_dw_f32(ptr(C), ptr(a), ptr(b), ptr(u_hist), ptr(v_hist), ptr(nits), nprob, n,
+                                                         ctx.eps, ctx.Lh, ptr(gcost), ptr(dC), ptr(dab[0]), ptr(dab[1]), ws,
+                                                         wsb, stream_of(C)), "sinkhorn_weighted_bwd_dw")
+            return (dC if need[0] else None, dab[0] if need[1] else None, dab[1] if need[2] else None, None, None, None,
+                    None, None)
         check(lib.kccot_sinkhorn_weighted_bwd_f32(ptr(C), ptr(a), ptr(b), ptr(u_hist), ptr(v_hist), ptr(nits), nprob, n,
                                                   ctx.eps, ctx.Lh, ptr(gcost), ptr(dC), ws, wsb, stream_of(C)),
               "sinkhorn_weighted_bwd")
@@ -447,7 +456,8 @@ class _WeightedSinkhorn(torch.autograd.Function):
 
 class _WeightedSinkhornLoss(torch.autograd.Function):
     """The one-batch loss with weighted marginals as ONE library call each way (kccot_weighted_sinkhorn_loss_fwd_f32 /
-    _bwd_f32), modelled on _SinkhornLoss: always the dual-history path (the fused launch is not weighted)."""
+    _bwd_f32), modelled on _SinkhornLoss: always the dual-history path (the fused launch is not weighted).  When w_real or
+    w_fake wants a gradient the backward is kccot_weighted_sinkhorn_loss_bwd_dw_f32 (include/kccot_weight_grad.h)."""
 
     @staticmethod
     def forward(ctx, tag, sc, eps, L, Lmin, w_real, w_fake, real, fake, *feats):
@@ -463,7 +473,7 @@ class _WeightedSinkhornLoss(torch.autograd.Function):
             raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
                                       "use compute_weighted_sinkhorn for a gradient w.r.t. both operands")
         dev = real.device
-        keep = any(need[1:])
+        keep = any(need[1:]) or any(ctx.needs_input_grad[5:7])
         Lh = max(int(L), 1)
         nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
         small = _lib.empty((4,), torch.float32, dev)                                 # costs | loss
@@ -500,6 +510,15 @@ class _WeightedSinkhornLoss(torch.autograd.Function):
         df = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[1:]) else None
         dfeats = [(df[i] if need[1 + i] else None) for i in range(4)]
         st = stream_of(real)
+        want_w = ctx.needs_input_grad[5:7]
+        if any(want_w):
+            dw = _lib.empty((2, B), torch.float32, real.device)
+            ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_dw_workspace_bytes(B, K), real, st)
+            check(lib.kccot_weighted_sinkhorn_loss_bwd_dw_f32(
+                ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w_real), ptr(w_fake), ptr(state),
+                ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ptr(dw[0]), ptr(dw[1]),
+                ws, wsb, st), "weighted_sinkhorn_loss_bwd_dw")
+            return (None,) * 5 + (dw[0] if want_w[0] else None, dw[1] if want_w[1] else None, None, dfake, *dfeats)
         ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_workspace_bytes(B, K), real, st)
         check(lib.kccot_weighted_sinkhorn_loss_bwd_f32(
             ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w_real), ptr(w_fake), ptr(state),
@@ -510,7 +529,9 @@ class _WeightedSinkhornLoss(torch.autograd.Function):
 
 class _ConditionalSinkhornLoss(torch.autograd.Function):
     """The kernel-conditional loss as ONE library call each way (kccot_conditional_sinkhorn_loss_fwd_f32 / _bwd_f32),
-    modelled on _WeightedSinkhornLoss: w [Q,B] weight rows, omega [Q] query weights or None (1/Q)."""
+    modelled on _WeightedSinkhornLoss: w [Q,B] weight rows, omega [Q] query weights or None (1/Q).  When w or omega wants a
+    gradient (compute_kernel_conditional_sinkhorn_loss only: compute_conditional_sinkhorn_loss refuses first) the backward is
+    kccot_conditional_sinkhorn_loss_bwd_dw_f32 (include/kccot_weight_grad.h)."""
 
     @staticmethod
     def forward(ctx, tag, sc, eps, L, Lmin, w, omega, real, fake, *feats):
@@ -526,7 +547,7 @@ class _ConditionalSinkhornLoss(torch.autograd.Function):
         if need[0]:
             raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
         dev = real.device
-        keep = any(need[1:])
+        keep = any(need[1:]) or any(ctx.needs_input_grad[5:7])
         Lh = max(int(L), 1)
         nc, nh = _pad64(3 * B * B), _pad64(3 * Q * Lh * B)
         small = _lib.empty((3 * Q + 1,), torch.float32, dev)                         # costs [Q,3] | loss
@@ -546,13 +567,13 @@ class _ConditionalSinkhornLoss(torch.autograd.Function):
         last_info[tag + "_fused_sweep"] = False
         last_info[tag + "_path"] = _weighted_path(B)
         if keep:
-            ctx.save_for_backward(real, fake, *feats, w, omega, state, nits)
+            ctx.save_for_backward(real, fake, *feats, w, omega, state, nits, small)
         ctx.cfg = (float(sc), float(eps), Lh)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        real, fake, *feats, w, omega, state, nits = ctx.saved_tensors
+        real, fake, *feats, w, omega, state, nits, small = ctx.saved_tensors
         sc, eps, Lh = ctx.cfg
         B, K = real.shape
         Q = w.shape[0]
@@ -564,12 +585,56 @@ class _ConditionalSinkhornLoss(torch.autograd.Function):
         df = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[1:]) else None
         dfeats = [(df[i] if need[1 + i] else None) for i in range(4)]
         st = stream_of(real)
+        want_w, want_om = ctx.needs_input_grad[5], ctx.needs_input_grad[6] and omega is not None
+        if want_w or want_om:
+            dw = _lib.empty((Q, B), torch.float32, real.device)
+            dom = _lib.empty((Q,), torch.float32, real.device) if want_om else None
+            ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_dw_workspace_bytes(B, K, Q), real, st)
+            check(lib.kccot_conditional_sinkhorn_loss_bwd_dw_f32(
+                ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w), ptr(omega), Q, ptr(state),
+                ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ptr(small[:3 * Q]),
+                ptr(dw), ptr(dom), ws, wsb, st), "conditional_sinkhorn_loss_bwd_dw")
+            return (None,) * 5 + (dw if want_w else None, dom, None, dfake, *dfeats)
         ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q), real, st)
         check(lib.kccot_conditional_sinkhorn_loss_bwd_f32(
             ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w), ptr(omega), Q, ptr(state),
             ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ws, wsb, st),
             "conditional_sinkhorn_loss_bwd")
         return (None,) * 8 + (dfake, *dfeats)
+
+
+class _KernelWeights(torch.autograd.Function):
+    """w = max(softmax(-D / (2 bw^2)), 2^-100) by rows (kccot_conditional_weights_f32) with its adjoint
+    (kccot_conditional_weights_bwd_f32, include/kccot_weight_grad.h).  ``bw``: a Python float (a constant), or a 0-dim fp32
+    device tensor, which is read on the device (the _dev entry points: no host read, the same bits) and differentiated."""
+
+    @staticmethod
+    def forward(ctx, D, bw):
+        Q, B = D.shape
+        w = _lib.empty((Q, B), torch.float32, D.device)
+        if torch.is_tensor(bw):
+            check(lib.kccot_conditional_weights_dev_f32(ptr(D), Q, B, ptr(bw), ptr(w), stream_of(D)), "conditional_weights")
+        else:
+            check(lib.kccot_conditional_weights_f32(ptr(D), Q, B, bw, ptr(w), stream_of(D)), "conditional_weights")
+        ctx.save_for_backward(D, w, *([bw] if torch.is_tensor(bw) else []))
+        ctx.bw = None if torch.is_tensor(bw) else bw
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        D, w, *bwt = ctx.saved_tensors
+        Q, B = D.shape
+        dw = dw.contiguous().float()
+        dD = _lib.empty((Q, B), torch.float32, D.device)
+        dbw = _lib.empty((Q,), torch.float32, D.device)
+        if bwt:
+            check(lib.kccot_conditional_weights_bwd_dev_f32(ptr(D), ptr(w), ptr(dw), Q, B, ptr(bwt[0]), ptr(dD), ptr(dbw),
+                                                            stream_of(D)), "conditional_weights_bwd")
+        else:
+            check(lib.kccot_conditional_weights_bwd_f32(ptr(D), ptr(w), ptr(dw), Q, B, ctx.bw, ptr(dD), ptr(dbw),
+                                                        stream_of(D)), "conditional_weights_bwd")
+        gbw = dbw.double().sum().float().reshape(()) if (bwt and ctx.needs_input_grad[1]) else None   # the Q row terms
+        return (dD if ctx.needs_input_grad[0] else None), gbw
 
 
 class _MixedDivergence(torch.autograd.Function):
@@ -746,8 +811,9 @@ def compute_weighted_sinkhorn(x, y, hy, Mx, scaling_coef, mu, nu, epsilon=1.0, L
     """compute_sinkhorn (gan_utils.py:124-165, bi_causal=False) with marginals ``mu`` over the rows (the samples of x) and
     ``nu`` over the columns (the samples of y) instead of 1/n: the updates subtract from log mu_i / log nu_j.
     EXTENSION: the reference hard-codes the uniform marginals (gan_utils.py:138-139).  ``mu`` / ``nu``: [n] device tensors,
-    strictly positive, finite and normalised by the caller; they are not differentiated (one that requires a gradient
-    raises NotImplementedError).  With mu = nu = 1/n this is compute_sinkhorn to rounding.  A weight that is <= 0 or not
+    strictly positive, finite and normalised by the caller.  Differentiable w.r.t. x, y, hy, Mx AND mu, nu (the reverse sweep
+    sums the adjoints of the duals it holds anyway: include/kccot_weight_grad.h; the gradient is that of the cost as a
+    function of unconstrained weights, not projected onto sum = 1).  With mu = nu = 1/n this is compute_sinkhorn to rounding.  A weight that is <= 0 or not
     finite gives a NaN cost and a negative count in last_info["compute_weighted_sinkhorn"] (raise_if_solver_aborted
     reports it).  n <= 128 runs the register-resident kernels, larger n the streaming single-workgroup solver; the multi-CU
     solver is not weighted and never used here (last_info["compute_weighted_sinkhorn_path"])."""
@@ -773,8 +839,10 @@ def compute_weighted_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
 
     ``sinkhorn_eps`` and ``sinkhorn_l`` ARE applied (this function has no reference quirk to mirror).  ``w_real`` /
     ``w_fake``: [B] device tensors of strictly positive finite weights; ``normalize=True`` divides each by its sum on the
-    device (no host synchronisation), ``normalize=False`` takes them as given.  Differentiable w.r.t. the fake videos and
-    the four features; a real video or a weight tensor that requires a gradient raises NotImplementedError.  Always the
+    device (no host synchronisation), ``normalize=False`` takes them as given.  Differentiable w.r.t. the fake videos, the
+    four features and the two weight vectors (through the normalisation, which is a torch division; the weight gradients
+    come from kccot_weighted_sinkhorn_loss_bwd_dw_f32 and are computed only when asked for: the other gradients are the same
+    bits either way); a real video that requires a gradient raises NotImplementedError.  Always the
     dual-history path: the one-launch fused loss and the multi-CU solver are not weighted.  Records
     last_info["compute_weighted_sinkhorn_loss"] (three counts; negative = a bad weight poisoned that problem, its cost
     and the gradients are NaN), ``..._executed``, ``..._costs`` [3], ``..._C3`` [3,B,B], ``..._fused_sweep`` (False) and
@@ -795,11 +863,13 @@ def kernel_conditional_weights(context, bandwidth, queries=None):
         w[q,i] = max(softmax_i(-D[q,i] / (2 bandwidth^2)), 2^-100)      (kccot_conditional_weights_f32)
 
     -- the floor keeps a peaked kernel from handing the solver a zero weight; rows are not renormalised after it.  Returns
-    [Q, B] fp32.  The weights are not differentiated: a context that requires a gradient raises NotImplementedError."""
+    [Q, B] fp32.  The weights are not differentiated here: a context that requires a gradient raises NotImplementedError --
+    compute_kernel_conditional_sinkhorn_loss is the differentiable form (context, bandwidth and query weights)."""
     if not torch.is_tensor(context) or context.dim() < 2:
         raise ValueError("context must be a tensor [batch, ...]")
     if context.requires_grad:
-        raise NotImplementedError("kernel_conditional_weights does not differentiate w.r.t. the context; detach it")
+        raise NotImplementedError("kernel_conditional_weights does not differentiate w.r.t. the context; detach it, or use "
+                                  "compute_kernel_conditional_sinkhorn_loss, which does")
     if not float(bandwidth) > 0.0:
         raise ValueError("bandwidth must be > 0 (got %r)" % (bandwidth,))
     c = _flat2(context)
@@ -835,7 +905,8 @@ def compute_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps
 
     ``sinkhorn_eps`` and ``sinkhorn_l`` ARE applied, as in compute_weighted_sinkhorn_loss.  ``weights``: [Q, B] device
     tensor, strictly positive and finite, rows normalised by the caller.  Differentiable w.r.t. the fake videos and the
-    four features; a real video or a weight tensor that requires a gradient raises NotImplementedError.  Records
+    four features; a real video or a weight tensor that requires a gradient raises NotImplementedError
+    (compute_kernel_conditional_sinkhorn_loss differentiates w.r.t. the context, the bandwidth and the query weights).  Records
     last_info["compute_conditional_sinkhorn_loss"] (counts [Q,3]; a negative row = a bad weight poisoned that query: its
     costs, the loss and the gradients are NaN), ``..._executed`` [Q,3], ``..._costs`` [Q,3], ``..._C3`` [3,B,B],
     ``..._path`` ("register" for B <= 128, "streaming" above) and ``..._fused_sweep`` (False)."""
@@ -843,7 +914,8 @@ def compute_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps
         if t is not None and not torch.is_tensor(t):
             raise TypeError("%s must be a tensor" % name)
         if t is not None and t.requires_grad:
-            raise NotImplementedError("%s: the conditional Sinkhorn loss does not differentiate w.r.t. the weights" % name)
+            raise NotImplementedError("%s: the conditional Sinkhorn loss does not differentiate w.r.t. the weights; "
+                                      "compute_kernel_conditional_sinkhorn_loss does" % name)
     if torch.is_tensor(f_real) and f_real.requires_grad:
         raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
     if weights.dim() != 2 or weights.shape[0] < 1:
@@ -865,6 +937,67 @@ def compute_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps
                                           *vids, *feats)
 
 
+def compute_kernel_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
+                                             m_fake, context, bandwidth, queries=None, query_weights=None, video=True):
+    """kernel_conditional_weights and compute_conditional_sinkhorn_loss in ONE differentiable call:
+
+        loss = sum_q omega_q (2 W(C_xy; w_q, w_q) - W(C_xx; w_q, w_q) - W(C_yy; w_q, w_q)),
+        w_q  = max(softmax_i(-|c_q - c_i|^2 / (2 bandwidth^2)), 2^-100),      c = ``context`` [B, ...], q over ``queries``
+
+    EXTENSION, not reference behaviour.  Differentiable w.r.t. the fake videos and the four features (as
+    compute_conditional_sinkhorn_loss), and w.r.t. what that pair of functions refuses:
+      * ``query_weights`` [Q]:  dloss/domega_q is the loss of query q;
+      * ``bandwidth`` when it is a 0-dim fp32 device tensor (it is then read on the device, never on the host, so a step can
+        be captured; it must be > 0, else the weights are NaN and the solver reports them).  A Python float is a constant;
+      * ``context``: dloss/dw [Q,B] (the reverse sweeps' sums of dual adjoints, include/kccot_weight_grad.h) -> the adjoint
+        of the kernel estimator (floored entries have zero slope) -> the squared distances' backward, on the query side and
+        on the sample side.
+    The weight gradient is computed only when one of the three asks for it.  With nothing new requiring a gradient the result
+    and the other gradients are, bit for bit, those of compute_conditional_sinkhorn_loss(..., kernel_conditional_weights(
+    context, bandwidth, queries), query_weights).  A real video that requires a gradient raises NotImplementedError.  Records
+    the keys of compute_conditional_sinkhorn_loss under last_info["compute_kernel_conditional_sinkhorn_loss"...]."""
+    tag = "compute_kernel_conditional_sinkhorn_loss"
+    if not torch.is_tensor(context) or context.dim() < 2:
+        raise ValueError("context must be a tensor [batch, ...]")
+    if query_weights is not None and not torch.is_tensor(query_weights):
+        raise TypeError("query_weights must be a tensor")
+    if torch.is_tensor(f_real) and f_real.requires_grad:
+        raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
+    if torch.is_tensor(bandwidth):
+        if bandwidth.dim() != 0:
+            raise ValueError("a tensor bandwidth must be 0-dim, got shape %s" % (tuple(bandwidth.shape),))
+    elif not float(bandwidth) > 0.0:
+        raise ValueError("bandwidth must be > 0 (got %r)" % (bandwidth,))
+    vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l, True)
+    B = vids[0].shape[0]
+    c = _flat2(context)
+    if c.shape[0] != B:
+        raise ValueError("context must have the videos' batch size %d, got %d" % (B, c.shape[0]))
+    if B > 1024:
+        raise NotImplementedError("%s: B=%d > 1024" % (tag, B))
+    cq = c
+    if queries is not None:
+        queries = torch.as_tensor(queries, device=c.device)
+        if queries.dim() != 1 or queries.numel() < 1 or queries.dtype not in (torch.int32, torch.int64):
+            raise ValueError("queries must be a non-empty 1-D integer index tensor")
+        cq = c.index_select(0, queries.long()).contiguous()
+    Q = cq.shape[0]
+    omega = None
+    if query_weights is not None:
+        if tuple(query_weights.shape) != (Q,):
+            raise ValueError("query_weights must be [%d], got %s" % (Q, tuple(query_weights.shape)))
+        _lib.require_gpu(query_weights)
+        omega = (query_weights if query_weights.dtype == torch.float32 else query_weights.float()).contiguous()
+    if torch.is_tensor(bandwidth):
+        _lib.require_gpu(bandwidth)
+        bw = bandwidth if bandwidth.dtype == torch.float32 else bandwidth.float()
+    else:
+        bw = float(bandwidth)
+    D = cost_xy(cq, c, 1.0).contiguous()
+    w = _KernelWeights.apply(D, bw)
+    return _ConditionalSinkhornLoss.apply(tag, float(scaling_coef), eps, L, _LMIN, w, omega, *vids, *feats)
+
+
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
     """Synchronising status check of the solves recorded under ``tags`` in ``last_info`` (``kccot_sinkhorn_status``): raises
     ``KccotError`` if a multi-CU Sinkhorn solve gave up (negative iteration count; its cost and gradients are NaN).  The
@@ -873,7 +1006,7 @@ def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
     single-GPU and the batch-sharded path both record their counts under "compute_sinkhorn_loss"); pass
     ``("compute_sinkhorn",)`` / ``("benchmark_sinkhorn",)`` after a direct call of those.  Under the tags of the weighted
     solver ("compute_weighted_sinkhorn", "compute_weighted_sinkhorn_loss") and of the conditional loss
-    ("compute_conditional_sinkhorn_loss", counts [Q,3]) a negative count means a weight that was <= 0 or not finite, and
+    ("compute_conditional_sinkhorn_loss", "compute_kernel_conditional_sinkhorn_loss", counts [Q,3]) a negative count means a weight that was <= 0 or not finite, and
     the error says so.  A checked entry is dropped, so a stale record of an earlier call can never be
     blamed for a later NaN."""
     for tag in tags:
@@ -886,7 +1019,7 @@ def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
             part = nits[lo:lo + 4096]
             rc = rc or lib.kccot_sinkhorn_status(ptr(part), int(part.numel()), stream_of(nits))
         if rc == _lib.EABORTED:
-            if tag.startswith(("compute_weighted_", "compute_conditional_")):     # never multi-CU: the only cause
+            if tag.startswith(("compute_weighted_", "compute_conditional_", "compute_kernel_conditional_")):     # never multi-CU: the only cause
                 raise _lib.KccotError("%s: a marginal weight of a problem was <= 0 or not finite; its cost and gradients "
                                       "are NaN (counts %s)" % (tag, nits.tolist()))
             raise _lib.KccotError("%s: %s" % (tag, lib.kccot_last_error().decode("utf-8", "replace")))
