@@ -59,18 +59,20 @@ def solver_yardstick(n, eps, Lit):
     return tuple(rel_err(torch.stack([x[k] for x in s]), torch.stack([x[k] for x in r])) for k in (3, 4))
 
 
-def solve_dw(L, C, a, b, eps, Lit, gcost=GCOST):
-    """dC of kccot_sinkhorn_weighted_bwd_f32, then (dC, da, db) of kccot_sinkhorn_weighted_bwd_dw_f32 on the same forward."""
+def solve_dw(L, C, a, b, eps, Lit, gcost=GCOST, c_off=0, Lmin=W.LMIN, stop_mode=0):
+    """dC of kccot_sinkhorn_weighted_bwd_f32, then (dC, da, db) of kccot_sinkhorn_weighted_bwd_dw_f32 on the same forward; the
+    forward's cost, both rows of nits and the whole (NaN-prefilled) histories come back too.  c_off: as GW.solve."""
     nprob, n, _ = C.shape
     Lh = max(Lit, 1)
-    bufs = {"C": Buf(C.shape, C), "a": Buf(a.shape, a), "b": Buf(b.shape, b), "u": Buf((nprob, Lh, n)), "v": Buf((nprob, Lh, n)),
+    bufs = {"C": GW.OffsetBuf(C.shape, C, c_off), "a": Buf(a.shape, a), "b": Buf(b.shape, b), "u": Buf((nprob, Lh, n)),
+            "v": Buf((nprob, Lh, n)),
             "cost": Buf((nprob,)), "nits": Buf((2 * nprob,), dtype=I32), "dC0": Buf(C.shape), "dC": Buf(C.shape),
             "da": Buf((nprob, n)), "db": Buf((nprob, n)), "g": Buf((nprob,), torch.tensor(gcost[:nprob]))}
     ws, wsb = workspace(L.lib.kccot_sinkhorn_workspace_bytes(nprob, n))
     bufs["ws"] = ws
     wp = ws.ptr() if wsb else None
-    call(L, "kccot_sinkhorn_weighted_fwd_f32", bufs["C"].ptr(), bufs["a"].ptr(), bufs["b"].ptr(), nprob, n, eps, Lit, W.LMIN,
-         W.THRESH, 0, bufs["u"].ptr(), bufs["v"].ptr(), bufs["cost"].ptr(), bufs["nits"].ptr(), None, wp, wsb, None)
+    call(L, "kccot_sinkhorn_weighted_fwd_f32", bufs["C"].ptr(), bufs["a"].ptr(), bufs["b"].ptr(), nprob, n, eps, Lit, Lmin,
+         W.THRESH, stop_mode, bufs["u"].ptr(), bufs["v"].ptr(), bufs["cost"].ptr(), bufs["nits"].ptr(), None, wp, wsb, None)
     call(L, "kccot_sinkhorn_weighted_bwd_f32", bufs["C"].ptr(), bufs["a"].ptr(), bufs["b"].ptr(), bufs["u"].ptr(),
          bufs["v"].ptr(), bufs["nits"].ptr(), nprob, n, eps, Lh, bufs["g"].ptr(), bufs["dC0"].ptr(), wp, wsb, None)
     call(L, "kccot_sinkhorn_weighted_bwd_dw_f32", bufs["C"].ptr(), bufs["a"].ptr(), bufs["b"].ptr(), bufs["u"].ptr(),
@@ -78,7 +80,7 @@ def solve_dw(L, C, a, b, eps, Lit, gcost=GCOST):
          bufs["db"].ptr(), wp, wsb, None)
     for k, bf in bufs.items():
         assert bf.guards_intact(), "guard zone of %s overwritten (n=%d)" % (k, n)
-    return {k: bufs[k].t.clone() for k in ("nits", "dC0", "dC", "da", "db")}
+    return {k: bufs[k].t.clone() for k in ("nits", "dC0", "dC", "da", "db", "cost", "u", "v")}
 
 
 @pytest.mark.parametrize("eps,Lit", [(0.8, 7), (1.0, 100)])
@@ -109,7 +111,7 @@ def test_one_iteration_and_weight_gradient_bits_do_not_depend_on_nprob(L):
 
 
 # ================================================================ 7. the weighted loss through autograd
-def _loss_weight_grads(shape, dtype, normalize, scale):
+def _loss_weight_grads(shape, dtype, normalize, scale, Lit=GW.LOSS_L):
     """(dw_real, dw_fake) of the weighted loss by the torch sweep in `dtype`: cost matrices, three sweeps with g = {2,-1,-1},
     dw_real = da_xy + (da_xx + db_xx), dw_fake = db_xy + (da_yy + db_yy), then the normalisation's own adjoint."""
     t = GW.loss_inputs(shape)
@@ -120,9 +122,9 @@ def _loss_weight_grads(shape, dtype, normalize, scale):
           W.ot.modified_cost(y, y, d["h_fake"], d["m_fake"], W.cases.SC)]
     wr, wf = (t["w_real"] * scale).to(dtype), (t["w_fake"] * scale).to(dtype)
     a, b = (wr / wr.sum(), wf / wf.sum()) if normalize else (wr, wf)
-    xy = WG.sweep(C3[0], a, b, GW.LOSS_EPS, GW.LOSS_L, g=2.0, dtype=dtype)
-    xx = WG.sweep(C3[1], a, a, GW.LOSS_EPS, GW.LOSS_L, g=-1.0, dtype=dtype)
-    yy = WG.sweep(C3[2], b, b, GW.LOSS_EPS, GW.LOSS_L, g=-1.0, dtype=dtype)
+    xy = WG.sweep(C3[0], a, b, GW.LOSS_EPS, Lit, g=2.0, dtype=dtype)
+    xx = WG.sweep(C3[1], a, a, GW.LOSS_EPS, Lit, g=-1.0, dtype=dtype)
+    yy = WG.sweep(C3[2], b, b, GW.LOSS_EPS, Lit, g=-1.0, dtype=dtype)
     da, db = xy[3] + (xx[3] + xx[4]), xy[4] + (yy[3] + yy[4])
     if normalize:        # a = w / s: dw = (da - <da, a>) / s
         da, db = (da - (da * a).sum()) / wr.sum(), (db - (db * b).sum()) / wf.sum()
@@ -130,17 +132,17 @@ def _loss_weight_grads(shape, dtype, normalize, scale):
 
 
 @functools.lru_cache(maxsize=None)
-def loss_weight_reference(shape, normalize, scale):
+def loss_weight_reference(shape, normalize, scale, Lit=GW.LOSS_L):
     """float64 autograd of W.weighted_loss (with the normalisation) w.r.t. w_real, w_fake, and the yardsticks."""
     t = GW.loss_inputs(shape)
     d = {k: t[k].double() for k in ("real", "fake") + FEATS}
     wr, wf = (t["w_real"] * scale).double().requires_grad_(True), (t["w_fake"] * scale).double().requires_grad_(True)
     a, b = (wr / wr.sum(), wf / wf.sum()) if normalize else (wr, wf)
-    loss, _, nits = W.weighted_loss(d["real"], d["fake"], W.cases.SC, GW.LOSS_EPS, GW.LOSS_L, d["h_fake"], d["m_real"], d["h_real"],
+    loss, _, nits = W.weighted_loss(d["real"], d["fake"], W.cases.SC, GW.LOSS_EPS, Lit, d["h_fake"], d["m_real"], d["h_real"],
                                     d["m_fake"], a, b)
-    assert nits == (GW.LOSS_L,) * 3
+    assert nits == (Lit,) * 3
     ref = torch.autograd.grad(loss, (wr, wf))
-    r64, r32 = _loss_weight_grads(shape, F64, normalize, scale), _loss_weight_grads(shape, F32, normalize, scale)
+    r64, r32 = _loss_weight_grads(shape, F64, normalize, scale, Lit), _loss_weight_grads(shape, F32, normalize, scale, Lit)
     for x, y in zip(r64, ref):                       # the sweep composition IS the gradient (float64 against float64)
         assert rel_err(x, y) <= 1e-9
     return ref, tuple(rel_err(x, y) for x, y in zip(r32, r64))
@@ -227,7 +229,7 @@ def cond_autograd(n, Q, given):
     return torch.autograd.grad(loss, (wl, om))
 
 
-def cond_solve_dw(L, C3, w, omega, eps, Lit, gloss, want_domega=True):
+def cond_solve_dw(L, C3, w, omega, eps, Lit, gloss, want_domega=True, Lmin=W.LMIN):
     Q, n = w.shape
     Lh = max(Lit, 1)
     bufs = {"C3": Buf(C3.shape, C3), "w": Buf(w.shape, w), "u": Buf((Q, 3, Lh, n)), "v": Buf((Q, 3, Lh, n)), "cost": Buf((Q, 3)),
@@ -240,7 +242,7 @@ def cond_solve_dw(L, C3, w, omega, eps, Lit, gloss, want_domega=True):
     ws, wsb = workspace(L.lib.kccot_sinkhorn_conditional_dw_workspace_bytes(Q, n))
     assert wsb > wsb0 > 0
     bufs["ws0"], bufs["ws"] = ws0, ws
-    call(L, "kccot_sinkhorn_conditional_fwd_f32", bufs["C3"].ptr(), bufs["w"].ptr(), op, Q, n, eps, Lit, W.LMIN, W.THRESH,
+    call(L, "kccot_sinkhorn_conditional_fwd_f32", bufs["C3"].ptr(), bufs["w"].ptr(), op, Q, n, eps, Lit, Lmin, W.THRESH,
          bufs["u"].ptr(), bufs["v"].ptr(), bufs["cost"].ptr(), bufs["nits"].ptr(), bufs["loss"].ptr(), ws0.ptr(), wsb0, None)
     call(L, "kccot_sinkhorn_conditional_bwd_f32", bufs["g"].ptr(), bufs["C3"].ptr(), bufs["w"].ptr(), op, bufs["u"].ptr(),
          bufs["v"].ptr(), bufs["nits"].ptr(), Q, n, eps, Lh, bufs["dC0"].ptr(), ws0.ptr(), wsb0, None)
@@ -251,7 +253,7 @@ def cond_solve_dw(L, C3, w, omega, eps, Lit, gloss, want_domega=True):
         assert bf.guards_intact(), "guard zone of %s overwritten (n=%d Q=%d)" % (k, n, Q)
     if not want_domega:
         assert bufs["dom"].untouched()
-    return {k: bufs[k].t.clone() for k in ("nits", "cost", "dC0", "dC3", "dw", "dom")}
+    return {k: bufs[k].t.clone() for k in ("nits", "cost", "dC0", "dC3", "dw", "dom", "loss", "u", "v")}
 
 
 @pytest.mark.parametrize("Q", [1, 7])
