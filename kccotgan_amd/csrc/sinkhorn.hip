@@ -106,6 +106,29 @@ __device__ __forceinline__ void load_other(float (&o)[EPT], const float* arr, in
     }
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Pins r[] in VGPRs at this point of the instruction stream.  lds_barrier() is an asm volatile with a memory clobber: that
+// holds LDS and global accesses on their side of the barrier, but NOT register arithmetic, which the compiler is free to sink
+// behind it (it did: the column role's whole plan of sinkhorn_fused_roles, 8 v_exp_f32 and their adds, went to the head of the
+// chain pass that the role split exists to keep clear).  An empty asm volatile that takes the values as in/out operands emits
+// no instruction; the values have to exist when it is reached, and asm volatile statements keep their order, so
+// keep_in_regs(r); lds_barrier(); puts everything r[] depends on in front of the barrier.  The values are pinned as two-wide
+// vectors (one aligned VGPR pair per operand), so that the v_pk_*_f32 that consume them keep their register pairs.
+template <int N>
+__device__ __forceinline__ void keep_in_regs(float (&r)[N]) {
+    if constexpr (N >= 2) {
+#pragma unroll
+        for (int m = 0; m < N; m += 2) {
+            f32x2 t = {r[m], r[m + 1]};
+            asm volatile("" : "+v"(t));
+            r[m] = t.x; r[m + 1] = t.y;
+        }
+    } else {
+        asm volatile("" : "+v"(r[0]));
+    }
+}
+
 // ---- log2-domain half-step ---------------------------------------------------------------------
 // With k2 = log2(e)/eps the kernels carry  c2 = C*k2,  U = u*k2,  V = v*k2  and evaluate
 //     y = (U_i - c2_ij) + V_j            [= ((-C+u)+v)/eps * log2(e), same association as gan_utils.py:153]
@@ -114,8 +137,6 @@ __device__ __forceinline__ void load_other(float (&o)[EPT], const float* arr, in
 // adds per entry instead of add/add/mul/mul, exp2/log2 are single hardware instructions, and the
 // two-wide vector type lets hipcc issue packed v_pk_add_f32.  The iterates are the same numbers in
 // other units; only fp32 rounding differs (the duals are O(1e3) with an ulp of 1e-4 either way).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 template <int EPT, int LPR, bool ROW>
 __device__ __forceinline__ float half_step(const float (&c2)[EPT], float self, const float* other, int q, float lw2) {
     float o[EPT];
@@ -1188,13 +1209,17 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
         KCCOT_STAMP(COL ? 7 : 3);
     };
     KCCOT_STAMP_IF(true, 13);
-    if constexpr (!COL) { if (nits >= 1) plan(nits); }
+    // Every plan is pinned (keep_in_regs) in front of the barrier that ends the pass it is evaluated in: the chain pass behind
+    // that barrier then holds the gradient read and the chain, and no plan arithmetic (tests/test_fused_roles_schedule.py
+    // checks the emitted code of every instance).  The stamps of the diagnostic twin are taken behind the pinned registers, so
+    // that they time the plan and not only its loads.
+    if constexpr (!COL) { if (nits >= 1) { plan(nits); keep_in_regs(pl); } }
     for (int it = nits; it >= 1; --it) {
         KCCOT_STAMP(0);
-        if constexpr (COL) { plan(it); KCCOT_STAMP(1); } else chain(it);              // (A) through v_t
+        if constexpr (COL) { plan(it); keep_in_regs(pl); KCCOT_STAMP(1); } else chain(it);              // (A) through v_t
         lds_barrier();
         KCCOT_STAMP(4);
-        if constexpr (COL) chain(it); else { if (it > 1) plan(it - 1); KCCOT_STAMP(5); }   // (B) through u_t
+        if constexpr (COL) chain(it); else { if (it > 1) { plan(it - 1); keep_in_regs(pl); } KCCOT_STAMP(5); }   // (B) through u_t
         lds_barrier();
         KCCOT_STAMP(8);
     }
