@@ -36,6 +36,7 @@ inline int launch_status(const char* what) {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 
 // ---- wave-level reductions (64-wide wavefront; xor butterflies leave the result in every lane)
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory
@@ -166,6 +167,17 @@ int sinkhorn_conditional_solve_fwd(const float* C3, const float* w, int Q, int n
 int sinkhorn_conditional_solve_bwd(const float* C3, const float* w, const float* u_hist, const float* v_hist,
                                    const int32_t* nits, int Q, int n, float eps, int L, const float* gcost, float* dC,
                                    void* ws, size_t ws_bytes, hipStream_t st, float* da = nullptr, float* db = nullptr);
+
+// conditional.hip: the solver stage of the conditional loss on a finished C3 [3,n,n], after cond_check (its limits on Q and n:
+// KCCOT_EINVAL / KCCOT_EUNSUPPORTED).  cond_fwd: the 3 Q solves -> loss = sum_q omega_q (2 c_q0 - c_q1 - c_q2); cond_bwd: gcost ->
+// the 3 Q reverse sweeps -> dC3_out = sum_q dC_q [-> dw_out [Q,n], domega_out [Q] (may be null) from the forward's cost [Q,3]].
+// ws: kccot_sinkhorn_conditional_workspace_bytes(Q, n) bytes, with dw_out kccot_sinkhorn_conditional_dw_workspace_bytes(Q, n).
+int cond_check(const char* who, int Q, int n, float eps, int L);
+int cond_fwd(const float* C3, const float* w, const float* omega, int Q, int n, float eps, int L, int Lmin, float thresh,
+             float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* loss_out, void* ws, hipStream_t st);
+int cond_bwd(const float* gloss, const float* C3, const float* w, const float* omega, const float* u_hist, const float* v_hist,
+             const int32_t* nits, int Q, int n, float eps, int L, float* dC3_out, void* ws, hipStream_t st,
+             const float* cost = nullptr, float* dw_out = nullptr, float* domega_out = nullptr);
 
 // cost_bwd.hip: kccot_pairwise_cost3_bwd_scaled_f32 (gscale = NULL: unscaled) over the whole batch.  bicausal selects the
 // feature-gradient jobs of the bi-causal loss (bicausal.hip): dh_fake = gxy.dm_real + 2 gyy.dm_fake,

@@ -11,8 +11,9 @@
 //   conditional_dC_reduce    dC3[k] = sum_q dC_{q,k}, double, ascending q, one thread per entry
 //   conditional_dw_reduce    (kccot_weight_grad.h) dw[q] = sum_k (da_{3q+k} + db_{3q+k}), domega_q = gloss (2 c_q0 - c_q1 - c_q2)
 //   conditional_weights_bwd  (kccot_weight_grad.h) the adjoint of conditional_weights from the stored weights
-// and the host entry points, which only sequence stages (as loss.hip does).  Nothing here depends on the order in which
-// workgroups finish: there is no atomic and no ticket.
+// and their host side: the solver stage cond_fwd / cond_bwd, which loss.hip sequences like its other stages, and the entry
+// points of the solver-level pair and of the weight estimator.  Nothing here depends on the order in which workgroups finish:
+// there is no atomic and no ticket.
 #include "common.h"
 #include <math.h>
 
@@ -162,7 +163,7 @@ static CondLayout cond_layout(int Q, int n) {
     return l;
 }
 
-static int cond_check(const char* who, int Q, int n, float eps, int L) {
+int cond_check(const char* who, int Q, int n, float eps, int L) {
     if (Q < 1 || n < 1 || L < 0 || !(eps > 0.f))
         return fail(KCCOT_EINVAL, "%s: bad arguments Q=%d n=%d L=%d eps=%g", who, Q, n, L, (double)eps);
     if (n > CD_MAXN) return fail(KCCOT_EUNSUPPORTED, "%s: n=%d > %d", who, n, CD_MAXN);
@@ -172,7 +173,7 @@ static int cond_check(const char* who, int Q, int n, float eps, int L) {
     return 0;
 }
 
-static int cond_fwd(const float* C3, const float* w, const float* omega, int Q, int n, float eps, int L, int Lmin,
+int cond_fwd(const float* C3, const float* w, const float* omega, int Q, int n, float eps, int L, int Lmin,
                     float thresh, float* u_hist, float* v_hist, float* cost_out, int32_t* nits_out, float* loss_out, void* ws,
                     hipStream_t st) {
     const CondLayout l = cond_layout(Q, n);
@@ -184,9 +185,9 @@ static int cond_fwd(const float* C3, const float* w, const float* omega, int Q, 
 }
 
 // cost / dw_out / domega_out: the _dw backward (dw_out given: the workspace then extends by cond_dadb_bytes)
-static int cond_bwd(const float* gloss, const float* C3, const float* w, const float* omega, const float* u_hist,
+int cond_bwd(const float* gloss, const float* C3, const float* w, const float* omega, const float* u_hist,
                     const float* v_hist, const int32_t* nits, int Q, int n, float eps, int L, float* dC3_out, void* ws,
-                    hipStream_t st, const float* cost = nullptr, float* dw_out = nullptr, float* domega_out = nullptr) {
+                    hipStream_t st, const float* cost, float* dw_out, float* domega_out) {
     const CondLayout l = cond_layout(Q, n);
     char* base = static_cast<char*>(ws);
     float* gcost = reinterpret_cast<float*>(base);
@@ -208,8 +209,6 @@ static int cond_bwd(const float* gloss, const float* C3, const float* w, const f
                        (const float*)db, gloss, cost, Q, n, dw_out, domega_out);
     return launch_status("conditional_dw_reduce");
 }
-
-static size_t max3z(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 
 }  // namespace kccot
 using namespace kccot;
@@ -261,70 +260,6 @@ extern "C" int kccot_sinkhorn_conditional_bwd_f32(const float* gloss, const floa
     return cond_bwd(gloss, C3, w, omega, u_hist, v_hist, nits, Q, n, eps, L, dC3_out, ws, (hipStream_t)stream);
 }
 
-// ---- the loss from videos and features: stages only ----------------------------------------------------------------------
-// workspace: dC3 [3,B,B] of the backward, then ONE stage at a time (cost assembly | conditional solver | cost backward)
-extern "C" size_t kccot_conditional_sinkhorn_loss_workspace_bytes(int B, int64_t K, int Q) {
-    if (B < 1 || K < 1 || Q < 1 || B > CD_MAXN || Q > CD_MAXQ) return 0;
-    const size_t stage = max3z(kccot_pairwise_cost3_workspace_bytes(B, K), cond_layout(Q, B).total,
-                               kccot_pairwise_cost3_bwd_workspace_bytes(B, K));
-    return up256((size_t)3 * B * B * sizeof(float)) + up256(stage);
-}
-
-static int cond_loss_check(const char* who, int B, int64_t K, int T, int J, int Q, float eps, int L) {
-    if (B < 1 || K < 1 || T < 1 || J < 1)
-        return fail(KCCOT_EINVAL, "%s: bad arguments B=%d K=%lld T=%d J=%d", who, B, (long long)K, T, J);
-    return cond_check(who, Q, B, eps, L);
-}
-
-extern "C" int kccot_conditional_sinkhorn_loss_fwd_f32(const float* real, const float* fake, int B, int64_t K, float sc,
-                                                       const float* h_fake, const float* h_real, const float* m_real,
-                                                       const float* m_fake, int T, int J, float eps, int L, int Lmin,
-                                                       float thresh, unsigned flags, const float* w, const float* omega, int Q,
-                                                       float* C3, float* u_hist, float* v_hist, float* cost_out,
-                                                       int32_t* nits_out, float* loss_out, void* ws, size_t ws_bytes,
-                                                       kccot_stream_t stream) {
-    const char* who = "conditional_sinkhorn_loss_fwd";
-    if (!real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w) return fail(KCCOT_EINVAL, "%s: null input pointer", who);
-    if (!C3 || !cost_out || !nits_out || !loss_out) return fail(KCCOT_EINVAL, "%s: null output pointer", who);
-    if ((u_hist == nullptr) != (v_hist == nullptr)) return fail(KCCOT_EINVAL, "%s: u_hist and v_hist must be given together", who);
-    if (flags & (KCCOT_COST_BICAUSAL_TERM_ONLY | KCCOT_COST_RBF_SUM | KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS))
-        return fail(KCCOT_EINVAL, "%s: flags 0x%x do not apply to a loss call", who, flags);
-    int rc = cond_loss_check(who, B, K, T, J, Q, eps, L);
-    if (rc) return rc;
-    const size_t need = kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-    rc = kccot_pairwise_cost3_f32(real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, flags, C3, ws, ws_bytes, stream);
-    if (rc) return rc;
-    return cond_fwd(C3, w, omega, Q, B, eps, L, Lmin, thresh, u_hist, v_hist, cost_out, nits_out, loss_out, ws,
-                    (hipStream_t)stream);
-}
-
-extern "C" int kccot_conditional_sinkhorn_loss_bwd_f32(const float* gloss, const float* real, const float* fake, int B,
-                                                       int64_t K, float sc, const float* h_fake, const float* h_real,
-                                                       const float* m_real, const float* m_fake, int T, int J, float eps,
-                                                       int L, const float* w, const float* omega, int Q, const float* C3,
-                                                       const float* u_hist, const float* v_hist, const int32_t* nits,
-                                                       float* dfake, float* dh_fake, float* dh_real, float* dm_real,
-                                                       float* dm_fake, void* ws, size_t ws_bytes, kccot_stream_t stream) {
-    const char* who = "conditional_sinkhorn_loss_bwd";
-    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w)
-        return fail(KCCOT_EINVAL, "%s: null input pointer", who);
-    if (!C3 || !u_hist || !v_hist || !nits) return fail(KCCOT_EINVAL, "%s: null pointer", who);
-    int rc = cond_loss_check(who, B, K, T, J, Q, eps, L);
-    if (rc) return rc;
-    const size_t need = kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-    char* base = static_cast<char*>(ws);
-    float* dC3 = reinterpret_cast<float*>(base);
-    const size_t off = up256((size_t)3 * B * B * sizeof(float));
-    void* stage = base + off;
-    const hipStream_t st = (hipStream_t)stream;
-    rc = cond_bwd(gloss, C3, w, omega, u_hist, v_hist, nits, Q, B, eps, L, dC3, stage, st);
-    if (rc) return rc;
-    return cost3_bwd_loss(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake, dh_real,
-                          dm_real, dm_fake, stage, ws_bytes - off, st, false);
-}
-
 // ---- the gradients w.r.t. the weights (include/kccot_weight_grad.h) --------------------------------------------------------
 extern "C" size_t kccot_sinkhorn_conditional_dw_workspace_bytes(int Q, int n) {
     if (Q < 1 || n < 1 || n > CD_MAXN || Q > CD_MAXQ) return 0;
@@ -345,42 +280,6 @@ extern "C" int kccot_sinkhorn_conditional_bwd_dw_f32(const float* gloss, const f
     if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
     return cond_bwd(gloss, C3, w, omega, u_hist, v_hist, nits, Q, n, eps, L, dC3_out, ws, (hipStream_t)stream, cost, dw_out,
                     domega_out);
-}
-
-// workspace: dC3 [3,B,B], then ONE stage at a time (conditional solver with its da | db | cost backward)
-extern "C" size_t kccot_conditional_sinkhorn_loss_dw_workspace_bytes(int B, int64_t K, int Q) {
-    if (B < 1 || K < 1 || Q < 1 || B > CD_MAXN || Q > CD_MAXQ) return 0;
-    const size_t stage = max3z(kccot_pairwise_cost3_workspace_bytes(B, K), cond_layout(Q, B).total + cond_dadb_bytes(Q, B),
-                               kccot_pairwise_cost3_bwd_workspace_bytes(B, K));
-    return up256((size_t)3 * B * B * sizeof(float)) + up256(stage);
-}
-
-extern "C" int kccot_conditional_sinkhorn_loss_bwd_dw_f32(const float* gloss, const float* real, const float* fake, int B,
-                                                          int64_t K, float sc, const float* h_fake, const float* h_real,
-                                                          const float* m_real, const float* m_fake, int T, int J, float eps,
-                                                          int L, const float* w, const float* omega, int Q, const float* C3,
-                                                          const float* u_hist, const float* v_hist, const int32_t* nits,
-                                                          float* dfake, float* dh_fake, float* dh_real, float* dm_real,
-                                                          float* dm_fake, const float* cost, float* dw_out,
-                                                          float* domega_out, void* ws, size_t ws_bytes,
-                                                          kccot_stream_t stream) {
-    const char* who = "conditional_sinkhorn_loss_bwd_dw";
-    if (!gloss || !real || !fake || !h_fake || !h_real || !m_real || !m_fake || !w)
-        return fail(KCCOT_EINVAL, "%s: null input pointer", who);
-    if (!C3 || !u_hist || !v_hist || !nits || !cost || !dw_out) return fail(KCCOT_EINVAL, "%s: null pointer", who);
-    int rc = cond_loss_check(who, B, K, T, J, Q, eps, L);
-    if (rc) return rc;
-    const size_t need = kccot_conditional_sinkhorn_loss_dw_workspace_bytes(B, K, Q);
-    if (!ws || ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
-    char* base = static_cast<char*>(ws);
-    float* dC3 = reinterpret_cast<float*>(base);
-    const size_t off = up256((size_t)3 * B * B * sizeof(float));
-    void* stage = base + off;
-    const hipStream_t st = (hipStream_t)stream;
-    rc = cond_bwd(gloss, C3, w, omega, u_hist, v_hist, nits, Q, B, eps, L, dC3, stage, st, cost, dw_out, domega_out);
-    if (rc) return rc;
-    return cost3_bwd_loss(dC3, nullptr, real, fake, B, K, sc, h_fake, h_real, m_real, m_fake, T, J, dfake, dh_fake, dh_real,
-                          dm_real, dm_fake, stage, ws_bytes - off, st, false);
 }
 
 static int cw_bwd_check(const char* who, const void* D, const void* w, const void* dw, int Q, int n, const void* dD,

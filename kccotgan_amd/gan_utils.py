@@ -46,12 +46,18 @@ def _flat2(x):
     return x.contiguous()
 
 
+def _gpu_f32(t):
+    """A device tensor as contiguous fp32 (None stays None)."""
+    if t is None:
+        return None
+    _lib.require_gpu(t)
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
+
+
 def _feat(t):
     if t.dim() != 3:
         raise ValueError("h / M must be [batch, time steps, J], got %s" % (tuple(t.shape),))
-    _lib.require_gpu(t)
-    t = t if t.dtype == torch.float32 else t.float()
-    return t.contiguous()
+    return _gpu_f32(t)
 
 
 def _same(x, y):
@@ -266,127 +272,6 @@ def _pad64(n):
     return (n + 63) & ~63
 
 
-# The loss entry points of one loss, called with the pointer arguments _SinkhornLoss assembles:
-#   fwd(head, u_hist, v_hist, dC_unit, tail)
-#       head = (real, fake, B, K, sc, *features, T, J, eps, L, Lmin, thresh, flags, C)
-#       tail = (costs, nits, loss, ticket, ws, ws_bytes, stream)
-#   bwd(gloss, inputs, hist, dC_unit, outs)
-#       inputs = (real, fake, B, K, sc, *features, T, J), hist = (eps, L, C, u_hist, v_hist, nits),
-#       outs = (dfake, *dfeatures, ws, ws_bytes, stream)
-# The fused path (solves + reverse sweep in one launch) passes dC_unit and null history; the history path the reverse.
-# P problems, stack videos per operand ([x; x'] for the mixed loss), key: the last_info name of the matrices.
-_LossSpec = collections.namedtuple("_LossSpec", "P stack ws_bytes fwd bwd key shape_error")
-
-
-def _one_fwd(head, uh, vh, dCu, tail):
-    if dCu is not None:
-        check(lib.kccot_sinkhorn_loss_fused_fwd_f32(*head, dCu, *tail), "sinkhorn_loss_fused_fwd")
-    else:
-        check(lib.kccot_sinkhorn_loss_fwd_f32(*head, uh, vh, *tail), "sinkhorn_loss_fwd")
-
-
-def _one_bwd(g, inputs, hist, dCu, outs):
-    if dCu is not None:
-        check(lib.kccot_sinkhorn_loss_fused_bwd_f32(g, dCu, *inputs, *outs), "sinkhorn_loss_fused_bwd")
-    else:
-        check(lib.kccot_sinkhorn_loss_bwd_f32(g, *inputs, *hist, *outs), "sinkhorn_loss_bwd")
-
-
-_ONE_BATCH = _LossSpec(3, 1, lib.kccot_sinkhorn_loss_workspace_bytes, _one_fwd, _one_bwd, "_C3",
-                       "real and fake must have the same shape: {} vs {}")
-_BICAUSAL = _LossSpec(
-    3, 1, lib.kccot_bicausal_sinkhorn_loss_workspace_bytes,
-    lambda head, uh, vh, dCu, tail: check(lib.kccot_bicausal_sinkhorn_loss_fwd_f32(*head, uh, vh, dCu, *tail),
-                                          "bicausal_sinkhorn_loss_fwd"),
-    lambda g, inputs, hist, dCu, outs: check(lib.kccot_bicausal_sinkhorn_loss_bwd_f32(g, *inputs, *hist, dCu, *outs),
-                                             "bicausal_sinkhorn_loss_bwd"),
-    "_C3", "real and fake must have the same shape: {} vs {}")
-_MIXED = _LossSpec(
-    4, 2, lib.kccot_mixed_sinkhorn_loss_workspace_bytes,
-    lambda head, uh, vh, dCu, tail: check(lib.kccot_mixed_sinkhorn_loss_fwd_f32(*head, uh, vh, dCu, *tail),
-                                          "mixed_sinkhorn_loss_fwd"),
-    lambda g, inputs, hist, dCu, outs: check(lib.kccot_mixed_sinkhorn_loss_bwd_f32(g, *inputs, *hist, dCu, *outs),
-                                             "mixed_sinkhorn_loss_bwd"),
-    "_Cmix", "the four videos must have the same shape")
-
-
-class _SinkhornLoss(torch.autograd.Function):
-    """A Sinkhorn loss of ``spec`` (_ONE_BATCH, _BICAUSAL or _MIXED) as ONE library call each way: the cost matrices, the
-    P solves + their combination, and back.  When a gradient is wanted and the dual history fits the CU's LDS
-    (kccot_sinkhorn_fused_eligible: configs[0], configs[1]) the solves and the reverse sweep are ONE launch: no history
-    leaves the CU, the state kept for backward is d loss / d C at dLoss = 1 and backward is coefficient build + video
-    gradient only.  Otherwise the dual history path.  Same kernels as _Cost3 followed by _SinkhornDivergence for the
-    one-batch loss, a third of the host work."""
-
-    @staticmethod
-    def forward(ctx, spec, tag, sc, eps, L, Lmin, real, fake, *feats):
-        rows, K = real.shape
-        B = rows // spec.stack
-        if fake.shape != real.shape or rows % spec.stack:
-            raise ValueError(spec.shape_error.format(tuple(real.shape), tuple(fake.shape)))
-        T, J = feats[0].shape[1], feats[0].shape[2]
-        for t in feats:
-            if t.shape != (B, T, J):
-                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        need = ctx.needs_input_grad[6:]                                             # real, fake, *feats
-        if need[0]:
-            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
-                                      "use compute_sinkhorn for a gradient w.r.t. both operands")
-        P, dev = spec.P, real.device
-        keep = any(need[1:])
-        Lh = max(int(L), 1)
-        nc, nh = _pad64(P * B * B), _pad64(P * Lh * B)
-        small = _lib.empty((P + 1,), torch.float32, dev)                             # costs | loss
-        nits = _lib.empty((2 * P,), torch.int32, dev)       # [reference-equivalent counts | iterations executed]
-        st = stream_of(real)
-        ws, wsb = workspace(spec.ws_bytes(B, K), real, st)
-        fused = bool(keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
-        if fused:
-            state = _lib.empty((2 * nc,), torch.float32, dev)                        # C | dC at dLoss = 1
-            uh = vh = None
-            dCu = ptr(state[nc:])
-        else:
-            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # C | u_hist | v_hist
-            uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
-            dCu = None
-        loss = small[P:]
-        spec.fwd((ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH,
-                  cost_flags, ptr(state)), uh, vh, dCu,
-                 (ptr(small), ptr(nits), ptr(loss), ptr(_ticket(dev)), ws, wsb, st))
-        last_info[tag], last_info[tag + "_executed"] = nits[:P], nits[P:]
-        last_info[tag + "_costs"] = small[:P]
-        last_info[tag + spec.key] = state[:P * B * B].view(P, B, B)
-        last_info[tag + "_fused_sweep"] = fused
-        if keep:
-            ctx.save_for_backward(real, fake, *feats, state, nits)
-        ctx.spec, ctx.cfg = spec, (float(sc), float(eps), Lh, fused)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        real, fake, *feats, state, nits = ctx.saved_tensors
-        spec, (sc, eps, Lh, fused) = ctx.spec, ctx.cfg
-        P, nf = spec.P, len(feats)
-        rows, K = real.shape
-        B = rows // spec.stack
-        T, J = feats[0].shape[1], feats[0].shape[2]
-        nc, nh = _pad64(P * B * B), _pad64(P * Lh * B)
-        need = ctx.needs_input_grad[7:]                                             # fake, *feats
-        g = g.reshape(1).contiguous().float()
-        dfake = _lib.empty_like(fake) if need[0] else None
-        df = _lib.empty((nf, B, T, J), torch.float32, real.device) if any(need[1:]) else None
-        dfeats = [(df[i] if need[1 + i] else None) for i in range(nf)]
-        st = stream_of(real)
-        ws, wsb = workspace(spec.ws_bytes(B, K), real, st)
-        if fused:
-            hist, dCu = (eps, Lh, None, None, None, None), ptr(state[nc:])
-        else:
-            hist, dCu = (eps, Lh, ptr(state), ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits)), None
-        spec.bwd(ptr(g), (ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J), hist, dCu,
-                 (ptr(dfake), *map(ptr, dfeats), ws, wsb, st))
-        return (None,) * 7 + (dfake, *dfeats)
-
-
 def _weighted_path(n):
     """The solver a weighted solve of size n runs on (include/kccot_weighted.h): never the multi-CU solver, never the
     one-launch fused loss."""
@@ -454,153 +339,177 @@ class _WeightedSinkhorn(torch.autograd.Function):
         return dC, None, None, None, None, None, None, None
 
 
-class _WeightedSinkhornLoss(torch.autograd.Function):
-    """The one-batch loss with weighted marginals as ONE library call each way (kccot_weighted_sinkhorn_loss_fwd_f32 /
-    _bwd_f32), modelled on _SinkhornLoss: always the dual-history path (the fused launch is not weighted).  When w_real or
-    w_fake wants a gradient the backward is kccot_weighted_sinkhorn_loss_bwd_dw_f32 (include/kccot_weight_grad.h)."""
+# What differs between the five losses _SinkhornLoss drives.  The entry points are called with the pointer arguments it
+# assembles (w: the weight arguments, () for uniform marginals):
+#   fwd(head, w, C, u_hist, v_hist, dC_unit, tail)
+#       head = (real, fake, B, K, sc, *features, T, J, eps, L, Lmin, thresh, flags)
+#       tail = (costs, nits, loss, [ticket,] ws, ws_bytes, stream)
+#   bwd(gloss, inputs, hist, w, saved, dC_unit, outs, dw, tail)
+#       inputs = (real, fake, B, K, sc, *features, T, J), hist = (eps, L), saved = (C, u_hist, v_hist, nits),
+#       outs = (dfake, *dfeatures), dw = the weight-gradient arguments (() unless a weight wants one),
+#       tail = (ws, ws_bytes, stream)
+# The fused path (solves + reverse sweep in one launch; ``fusable``) passes dC_unit and null history, the history path the
+# reverse.
+#   P cost matrices, ``stack`` videos per operand ([x; x'] for the mixed loss), key: the last_info name of the matrices
+#   real_hint: what the refusal of a gradient w.r.t. real points to;  ticket: the forward takes the arrival counter
+#   queries: wa is [Q,B], one set of P solves per row (costs and counts are recorded as [Q,P]), and Q follows B, K in the
+#            workspace queries ws_bytes (forward and plain backward) / dw_ws_bytes (weight-gradient backward)
+#   dw(wa, small, want) -> (the dw arguments, (d wa, d wb)), want = which of (wa, wb) asks for a gradient
+_OPERANDS_HINT = "; use %s for a gradient w.r.t. both operands"
+_LossSpec = collections.namedtuple(
+    "_LossSpec", "ws_bytes fwd bwd P stack key shape_error real_hint fusable ticket queries dw_ws_bytes dw",
+    defaults=(3, 1, "_C3", "real and fake must have the same shape: {} vs {}", _OPERANDS_HINT % "compute_sinkhorn", True,
+              True, False, None, None))
+
+
+def _one_fwd(head, w, C, uh, vh, dCu, tail):
+    if dCu is not None:
+        check(lib.kccot_sinkhorn_loss_fused_fwd_f32(*head, C, dCu, *tail), "sinkhorn_loss_fused_fwd")
+    else:
+        check(lib.kccot_sinkhorn_loss_fwd_f32(*head, C, uh, vh, *tail), "sinkhorn_loss_fwd")
+
+
+def _one_bwd(g, inputs, hist, w, saved, dCu, outs, dw, tail):
+    if dCu is not None:
+        check(lib.kccot_sinkhorn_loss_fused_bwd_f32(g, dCu, *inputs, *outs, *tail), "sinkhorn_loss_fused_bwd")
+    else:
+        check(lib.kccot_sinkhorn_loss_bwd_f32(g, *inputs, *hist, *saved, *outs, *tail), "sinkhorn_loss_bwd")
+
+
+def _entry_points(name, unit_slot):
+    """(fwd, bwd) on kccot_<name>_fwd_f32 / _bwd_f32 / _bwd_dw_f32 (when a weight wants a gradient); unit_slot: they take
+    dC_unit behind the history."""
+    f, b = getattr(lib, "kccot_%s_fwd_f32" % name), getattr(lib, "kccot_%s_bwd_f32" % name)
+    bdw = getattr(lib, "kccot_%s_bwd_dw_f32" % name, None)
+
+    def fwd(head, w, C, uh, vh, dCu, tail):
+        check(f(*head, *w, C, uh, vh, *((dCu,) if unit_slot else ()), *tail), name + "_fwd")
+
+    def bwd(g, inputs, hist, w, saved, dCu, outs, dw, tail):
+        if dw:
+            check(bdw(g, *inputs, *hist, *w, *saved, *outs, *dw, *tail), name + "_bwd_dw")
+        else:
+            check(b(g, *inputs, *hist, *w, *saved, *((dCu,) if unit_slot else ()), *outs, *tail), name + "_bwd")
+    return fwd, bwd
+
+
+def _weighted_dw(wa, small, want):
+    dw = _lib.empty((2, wa.shape[0]), torch.float32, wa.device)
+    return (ptr(dw[0]), ptr(dw[1])), (dw[0] if want[0] else None, dw[1] if want[1] else None)
+
+
+def _conditional_dw(w, small, want):     # small[:3 Q]: the costs of the forward, which d omega is made of
+    dw = _lib.empty(tuple(w.shape), torch.float32, w.device)
+    dom = _lib.empty((w.shape[0],), torch.float32, w.device) if want[1] else None
+    return (ptr(small[:3 * w.shape[0]]), ptr(dw), ptr(dom)), (dw if want[0] else None, dom)
+
+
+_ONE_BATCH = _LossSpec(lib.kccot_sinkhorn_loss_workspace_bytes, _one_fwd, _one_bwd)
+_BICAUSAL = _LossSpec(lib.kccot_bicausal_sinkhorn_loss_workspace_bytes, *_entry_points("bicausal_sinkhorn_loss", True))
+_MIXED = _LossSpec(lib.kccot_mixed_sinkhorn_loss_workspace_bytes, *_entry_points("mixed_sinkhorn_loss", True), P=4, stack=2,
+                   key="_Cmix", shape_error="the four videos must have the same shape")
+# weighted marginals: always the dual-history path (the fused launch is not weighted)
+_WEIGHTED = _LossSpec(lib.kccot_weighted_sinkhorn_loss_workspace_bytes, *_entry_points("weighted_sinkhorn_loss", False),
+                      real_hint=_OPERANDS_HINT % "compute_weighted_sinkhorn", fusable=False,
+                      dw_ws_bytes=lib.kccot_weighted_sinkhorn_loss_dw_workspace_bytes, dw=_weighted_dw)
+_CONDITIONAL = _LossSpec(lib.kccot_conditional_sinkhorn_loss_workspace_bytes,
+                         *_entry_points("conditional_sinkhorn_loss", False), real_hint="", fusable=False, ticket=False,
+                         queries=True, dw_ws_bytes=lib.kccot_conditional_sinkhorn_loss_dw_workspace_bytes, dw=_conditional_dw)
+
+# Where _SinkhornLoss.apply takes its tensors: (spec, tag, sc, eps, L, Lmin, real, fake, *features, wa, wb).  The weight pair
+# closes the list, behind the 4 or 6 features, so that backward's tuple keeps (7 x None, dfake, *dfeatures) in front: the
+# partial-gradient tests of the bi-causal and the mixed loss read the loss node by these positions.
+_REAL, _FAKE, _FEATS, _WEIGHTS = 6, 7, 8, -2
+
+
+class _SinkhornLoss(torch.autograd.Function):
+    """A Sinkhorn loss of ``spec`` (_ONE_BATCH, _BICAUSAL, _MIXED, _WEIGHTED or _CONDITIONAL) as ONE library call each way:
+    the cost matrices, the solves + their combination, and back.  (wa, wb), the last two arguments: None for uniform
+    marginals, (w_real, w_fake) [B] each for _WEIGHTED, (w [Q,B] weight rows, omega [Q] query weights or None = 1/Q) for
+    _CONDITIONAL.
+    When a gradient is wanted and the dual history fits the CU's LDS (kccot_sinkhorn_fused_eligible: configs[0],
+    configs[1]) the solves and the reverse sweep of an unweighted loss are ONE launch: no history leaves the CU, the state
+    kept for backward is d loss / d C at dLoss = 1 and backward is coefficient build + video gradient only.  Otherwise the
+    dual history path; when wa or wb wants a gradient its backward is the _bwd_dw entry point
+    (include/kccot_weight_grad.h: the other gradients are the same bits).  Same kernels as _Cost3 followed by
+    _SinkhornDivergence for the one-batch loss, a third of the host work."""
 
     @staticmethod
-    def forward(ctx, tag, sc, eps, L, Lmin, w_real, w_fake, real, fake, *feats):
-        B, K = real.shape
-        if fake.shape != real.shape:
-            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
+    def forward(ctx, spec, tag, sc, eps, L, Lmin, real, fake, *feats_and_weights):
+        *feats, wa, wb = feats_and_weights
+        rows, K = real.shape
+        B = rows // spec.stack
+        if fake.shape != real.shape or rows % spec.stack:
+            raise ValueError(spec.shape_error.format(tuple(real.shape), tuple(fake.shape)))
         T, J = feats[0].shape[1], feats[0].shape[2]
         for t in feats:
             if t.shape != (B, T, J):
                 raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        need = ctx.needs_input_grad[7:]                                             # real, fake, *feats
-        if need[0]:
-            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
-                                      "use compute_weighted_sinkhorn for a gradient w.r.t. both operands")
-        dev = real.device
-        keep = any(need[1:]) or any(ctx.needs_input_grad[5:7])
+        need = ctx.needs_input_grad
+        if need[_REAL]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)"
+                                      + spec.real_hint)
+        P, dev = spec.P, real.device
+        q = (wa.shape[0],) if spec.queries else ()
+        NP = P * (q[0] if q else 1)                                                 # solves
+        keep = any(need[_FAKE:])                                                    # fake, features or weights
         Lh = max(int(L), 1)
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
-        small = _lib.empty((4,), torch.float32, dev)                                 # costs | loss
-        nits = _lib.empty((6,), torch.int32, dev)           # [reference-equivalent counts | iterations executed]
+        nc, nh = _pad64(P * B * B), _pad64(NP * Lh * B)
+        small = _lib.empty((NP + 1,), torch.float32, dev)                            # costs | loss
+        nits = _lib.empty((2 * NP,), torch.int32, dev)      # [reference-equivalent counts | iterations executed]
         st = stream_of(real)
-        ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_workspace_bytes(B, K), real, st)
-        state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)      # C | u_hist | v_hist
-        uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
-        loss = small[3:]
-        check(lib.kccot_weighted_sinkhorn_loss_fwd_f32(
-            ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
-            ptr(w_real), ptr(w_fake), ptr(state), uh, vh, ptr(small), ptr(nits), ptr(loss), ptr(_ticket(dev)), ws, wsb, st),
-            "weighted_sinkhorn_loss_fwd")
-        last_info[tag], last_info[tag + "_executed"] = nits[:3], nits[3:]
-        last_info[tag + "_costs"] = small[:3]
-        last_info[tag + "_C3"] = state[:3 * B * B].view(3, B, B)
-        last_info[tag + "_fused_sweep"] = False
-        last_info[tag + "_path"] = _weighted_path(B)
+        ws, wsb = workspace(spec.ws_bytes(B, K, *q), real, st)
+        fused = bool(spec.fusable and keep and lib.kccot_sinkhorn_fused_eligible(B, int(L)))
+        if fused:
+            state = _lib.empty((2 * nc,), torch.float32, dev)                        # C | dC at dLoss = 1
+            uh = vh = None
+            dCu = ptr(state[nc:])
+        else:
+            state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)  # C | u_hist | v_hist
+            uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
+            dCu = None
+        loss = small[NP:]
+        spec.fwd((ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags),
+                 () if wa is None else (ptr(wa), ptr(wb), *q), ptr(state), uh, vh, dCu,
+                 (ptr(small), ptr(nits), ptr(loss), *((ptr(_ticket(dev)),) if spec.ticket else ()), ws, wsb, st))
+        per_query = (lambda t: t.view(q[0], P)) if q else (lambda t: t)
+        last_info[tag], last_info[tag + "_executed"] = per_query(nits[:NP]), per_query(nits[NP:])
+        last_info[tag + "_costs"] = per_query(small[:NP])
+        last_info[tag + spec.key] = state[:P * B * B].view(P, B, B)
+        last_info[tag + "_fused_sweep"] = fused
+        if wa is not None:
+            last_info[tag + "_path"] = _weighted_path(B)
         if keep:
-            ctx.save_for_backward(real, fake, *feats, w_real, w_fake, state, nits)
-        ctx.cfg = (float(sc), float(eps), Lh)
+            ctx.save_for_backward(real, fake, *feats, wa, wb, state, nits, small)
+        ctx.spec, ctx.cfg = spec, (float(sc), float(eps), Lh, fused)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        real, fake, *feats, w_real, w_fake, state, nits = ctx.saved_tensors
-        sc, eps, Lh = ctx.cfg
-        B, K = real.shape
+        real, fake, *feats, wa, wb, state, nits, small = ctx.saved_tensors
+        spec, (sc, eps, Lh, fused) = ctx.spec, ctx.cfg
+        P, nf = spec.P, len(feats)
+        rows, K = real.shape
+        B = rows // spec.stack
         T, J = feats[0].shape[1], feats[0].shape[2]
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Lh * B)
-        need = ctx.needs_input_grad[8:]                                             # fake, *feats
+        q = (wa.shape[0],) if spec.queries else ()
+        nc, nh = _pad64(P * B * B), _pad64(P * (q[0] if q else 1) * Lh * B)
+        need = ctx.needs_input_grad
         g = g.reshape(1).contiguous().float()
-        dfake = _lib.empty_like(fake) if need[0] else None
-        df = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[1:]) else None
-        dfeats = [(df[i] if need[1 + i] else None) for i in range(4)]
+        dfake = _lib.empty_like(fake) if need[_FAKE] else None
+        df = _lib.empty((nf, B, T, J), torch.float32, real.device) if any(need[_FEATS:_WEIGHTS]) else None
+        dfeats = [(df[i] if need[_FEATS + i] else None) for i in range(nf)]
+        want = need[_WEIGHTS:]
+        dw, dwab = spec.dw(wa, small, want) if any(want) else ((), (None, None))
         st = stream_of(real)
-        want_w = ctx.needs_input_grad[5:7]
-        if any(want_w):
-            dw = _lib.empty((2, B), torch.float32, real.device)
-            ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_dw_workspace_bytes(B, K), real, st)
-            check(lib.kccot_weighted_sinkhorn_loss_bwd_dw_f32(
-                ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w_real), ptr(w_fake), ptr(state),
-                ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ptr(dw[0]), ptr(dw[1]),
-                ws, wsb, st), "weighted_sinkhorn_loss_bwd_dw")
-            return (None,) * 5 + (dw[0] if want_w[0] else None, dw[1] if want_w[1] else None, None, dfake, *dfeats)
-        ws, wsb = workspace(lib.kccot_weighted_sinkhorn_loss_workspace_bytes(B, K), real, st)
-        check(lib.kccot_weighted_sinkhorn_loss_bwd_f32(
-            ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w_real), ptr(w_fake), ptr(state),
-            ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ws, wsb, st),
-            "weighted_sinkhorn_loss_bwd")
-        return (None,) * 8 + (dfake, *dfeats)
-
-
-class _ConditionalSinkhornLoss(torch.autograd.Function):
-    """The kernel-conditional loss as ONE library call each way (kccot_conditional_sinkhorn_loss_fwd_f32 / _bwd_f32),
-    modelled on _WeightedSinkhornLoss: w [Q,B] weight rows, omega [Q] query weights or None (1/Q).  When w or omega wants a
-    gradient (compute_kernel_conditional_sinkhorn_loss only: compute_conditional_sinkhorn_loss refuses first) the backward is
-    kccot_conditional_sinkhorn_loss_bwd_dw_f32 (include/kccot_weight_grad.h)."""
-
-    @staticmethod
-    def forward(ctx, tag, sc, eps, L, Lmin, w, omega, real, fake, *feats):
-        B, K = real.shape
-        Q = w.shape[0]
-        if fake.shape != real.shape:
-            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
-        T, J = feats[0].shape[1], feats[0].shape[2]
-        for t in feats:
-            if t.shape != (B, T, J):
-                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        need = ctx.needs_input_grad[7:]                                             # real, fake, *feats
-        if need[0]:
-            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
-        dev = real.device
-        keep = any(need[1:]) or any(ctx.needs_input_grad[5:7])
-        Lh = max(int(L), 1)
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Q * Lh * B)
-        small = _lib.empty((3 * Q + 1,), torch.float32, dev)                         # costs [Q,3] | loss
-        nits = _lib.empty((6 * Q,), torch.int32, dev)       # [reference-equivalent counts | iterations executed], [Q,3] each
-        st = stream_of(real)
-        ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q), real, st)
-        state = _lib.empty((nc + (2 * nh if keep else 0),), torch.float32, dev)      # C3 | u_hist | v_hist
-        uh, vh = (ptr(state[nc:nc + nh]), ptr(state[nc + nh:])) if keep else (None, None)
-        loss = small[3 * Q:]
-        check(lib.kccot_conditional_sinkhorn_loss_fwd_f32(
-            ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, float(eps), int(L), int(Lmin), _THRESH, cost_flags,
-            ptr(w), ptr(omega), Q, ptr(state), uh, vh, ptr(small), ptr(nits), ptr(loss), ws, wsb, st),
-            "conditional_sinkhorn_loss_fwd")
-        last_info[tag], last_info[tag + "_executed"] = nits[:3 * Q].view(Q, 3), nits[3 * Q:].view(Q, 3)
-        last_info[tag + "_costs"] = small[:3 * Q].view(Q, 3)
-        last_info[tag + "_C3"] = state[:3 * B * B].view(3, B, B)
-        last_info[tag + "_fused_sweep"] = False
-        last_info[tag + "_path"] = _weighted_path(B)
-        if keep:
-            ctx.save_for_backward(real, fake, *feats, w, omega, state, nits, small)
-        ctx.cfg = (float(sc), float(eps), Lh)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        real, fake, *feats, w, omega, state, nits, small = ctx.saved_tensors
-        sc, eps, Lh = ctx.cfg
-        B, K = real.shape
-        Q = w.shape[0]
-        T, J = feats[0].shape[1], feats[0].shape[2]
-        nc, nh = _pad64(3 * B * B), _pad64(3 * Q * Lh * B)
-        need = ctx.needs_input_grad[8:]                                             # fake, *feats
-        g = g.reshape(1).contiguous().float()
-        dfake = _lib.empty_like(fake) if need[0] else None
-        df = _lib.empty((4, B, T, J), torch.float32, real.device) if any(need[1:]) else None
-        dfeats = [(df[i] if need[1 + i] else None) for i in range(4)]
-        st = stream_of(real)
-        want_w, want_om = ctx.needs_input_grad[5], ctx.needs_input_grad[6] and omega is not None
-        if want_w or want_om:
-            dw = _lib.empty((Q, B), torch.float32, real.device)
-            dom = _lib.empty((Q,), torch.float32, real.device) if want_om else None
-            ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_dw_workspace_bytes(B, K, Q), real, st)
-            check(lib.kccot_conditional_sinkhorn_loss_bwd_dw_f32(
-                ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w), ptr(omega), Q, ptr(state),
-                ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ptr(small[:3 * Q]),
-                ptr(dw), ptr(dom), ws, wsb, st), "conditional_sinkhorn_loss_bwd_dw")
-            return (None,) * 5 + (dw if want_w else None, dom, None, dfake, *dfeats)
-        ws, wsb = workspace(lib.kccot_conditional_sinkhorn_loss_workspace_bytes(B, K, Q), real, st)
-        check(lib.kccot_conditional_sinkhorn_loss_bwd_f32(
-            ptr(g), ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J, eps, Lh, ptr(w), ptr(omega), Q, ptr(state),
-            ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits), ptr(dfake), *map(ptr, dfeats), ws, wsb, st),
-            "conditional_sinkhorn_loss_bwd")
-        return (None,) * 8 + (dfake, *dfeats)
+        ws, wsb = workspace((spec.dw_ws_bytes if dw else spec.ws_bytes)(B, K, *q), real, st)
+        if fused:
+            saved, dCu = (None, None, None, None), ptr(state[nc:])
+        else:
+            saved, dCu = (ptr(state), ptr(state[nc:nc + nh]), ptr(state[nc + nh:]), ptr(nits)), None
+        spec.bwd(ptr(g), (ptr(real), ptr(fake), B, K, sc, *map(ptr, feats), T, J), (eps, Lh),
+                 () if wa is None else (ptr(wa), ptr(wb), *q), saved, dCu, (ptr(dfake), *map(ptr, dfeats)), dw, (ws, wsb, st))
+        return (None,) * _FAKE + (dfake, *dfeats, *dwab)
 
 
 class _KernelWeights(torch.autograd.Function):
@@ -749,7 +658,8 @@ def compute_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l
     vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l,
                                        honor_eps_l)
     # one library call each way; equivalent to _Cost3 (C3 = [xy, xx, yy]) followed by _SinkhornDivergence
-    return _SinkhornLoss.apply(_ONE_BATCH, "compute_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats)
+    return _SinkhornLoss.apply(_ONE_BATCH, "compute_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats,
+                               None, None)
 
 
 def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef, sinkhorn_eps, sinkhorn_l,
@@ -780,7 +690,8 @@ def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef
     # stacked minibatches (2 B K floats copied); cat's backward hands d[y; y'] back to y and y' as two views
     R = torch.cat([vids[0], vids[2]], 0)
     F = torch.cat([vids[1], vids[3]], 0)
-    return _SinkhornLoss.apply(_MIXED, "compute_mixed_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, R, F, *feats)
+    return _SinkhornLoss.apply(_MIXED, "compute_mixed_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, R, F, *feats,
+                               None, None)
 
 
 def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
@@ -803,8 +714,8 @@ def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
     """
     vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l,
                                        honor_eps_l)
-    return _SinkhornLoss.apply(_BICAUSAL, "compute_bicausal_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids,
-                               *feats)
+    return _SinkhornLoss.apply(_BICAUSAL, "compute_bicausal_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats,
+                               None, None)
 
 
 def compute_weighted_sinkhorn(x, y, hy, Mx, scaling_coef, mu, nu, epsilon=1.0, L=100):
@@ -850,8 +761,27 @@ def compute_weighted_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
     vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l, True)
     B = vids[0].shape[0]
     a, b = _weights(w_real, B, "w_real", normalize), _weights(w_fake, B, "w_fake", normalize)
-    return _WeightedSinkhornLoss.apply("compute_weighted_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, a, b, *vids,
-                                       *feats)
+    return _SinkhornLoss.apply(_WEIGHTED, "compute_weighted_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats,
+                               a, b)
+
+
+def _query_rows(c, queries, who):
+    """The rows of the context c [B, Kc] that ``queries`` names (None: all B, in order), within the weight estimator's limit
+    on B."""
+    if c.shape[0] > 1024:
+        raise NotImplementedError("%s: B=%d > 1024" % (who, c.shape[0]))
+    if queries is None:
+        return c
+    queries = torch.as_tensor(queries, device=c.device)
+    if queries.dim() != 1 or queries.numel() < 1 or queries.dtype not in (torch.int32, torch.int64):
+        raise ValueError("queries must be a non-empty 1-D integer index tensor")
+    return c.index_select(0, queries.long()).contiguous()
+
+
+def _check_query_weights(query_weights, Q):
+    """``query_weights`` is None or [Q] (_gpu_f32 then makes it what the library reads)."""
+    if query_weights is not None and tuple(query_weights.shape) != (Q,):
+        raise ValueError("query_weights must be [%d], got %s" % (Q, tuple(query_weights.shape)))
 
 
 def kernel_conditional_weights(context, bandwidth, queries=None):
@@ -873,18 +803,9 @@ def kernel_conditional_weights(context, bandwidth, queries=None):
     if not float(bandwidth) > 0.0:
         raise ValueError("bandwidth must be > 0 (got %r)" % (bandwidth,))
     c = _flat2(context)
-    B = c.shape[0]
-    if B > 1024:
-        raise NotImplementedError("kernel_conditional_weights: B=%d > 1024" % B)
-    cq = c
-    if queries is not None:
-        queries = torch.as_tensor(queries, device=c.device)
-        if queries.dim() != 1 or queries.numel() < 1 or queries.dtype not in (torch.int32, torch.int64):
-            raise ValueError("queries must be a non-empty 1-D integer index tensor")
-        cq = c.index_select(0, queries.long()).contiguous()
     with torch.no_grad():
-        D = cost_xy(cq, c, 1.0).contiguous()
-    Q = D.shape[0]
+        D = cost_xy(_query_rows(c, queries, "kernel_conditional_weights"), c, 1.0).contiguous()
+    Q, B = D.shape
     w = _lib.empty((Q, B), torch.float32, c.device)
     check(lib.kccot_conditional_weights_f32(ptr(D), Q, B, float(bandwidth), ptr(w), stream_of(D)), "conditional_weights")
     return w
@@ -920,21 +841,13 @@ def compute_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps
         raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289)")
     if weights.dim() != 2 or weights.shape[0] < 1:
         raise ValueError("weights must be [Q, B] with Q >= 1, got %s" % (tuple(weights.shape),))
-    Q = weights.shape[0]
-    if query_weights is not None and tuple(query_weights.shape) != (Q,):
-        raise ValueError("query_weights must be [%d], got %s" % (Q, tuple(query_weights.shape)))
+    _check_query_weights(query_weights, weights.shape[0])
     vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l, True)
     B = vids[0].shape[0]
     if weights.shape[1] != B:
         raise ValueError("weights must be [Q, %d], got %s" % (B, tuple(weights.shape)))
-    _lib.require_gpu(weights)
-    w = (weights if weights.dtype == torch.float32 else weights.float()).contiguous()
-    omega = None
-    if query_weights is not None:
-        _lib.require_gpu(query_weights)
-        omega = (query_weights if query_weights.dtype == torch.float32 else query_weights.float()).contiguous()
-    return _ConditionalSinkhornLoss.apply("compute_conditional_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, w, omega,
-                                          *vids, *feats)
+    return _SinkhornLoss.apply(_CONDITIONAL, "compute_conditional_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids,
+                               *feats, _gpu_f32(weights), _gpu_f32(query_weights))
 
 
 def compute_kernel_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
@@ -973,29 +886,12 @@ def compute_kernel_conditional_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkh
     c = _flat2(context)
     if c.shape[0] != B:
         raise ValueError("context must have the videos' batch size %d, got %d" % (B, c.shape[0]))
-    if B > 1024:
-        raise NotImplementedError("%s: B=%d > 1024" % (tag, B))
-    cq = c
-    if queries is not None:
-        queries = torch.as_tensor(queries, device=c.device)
-        if queries.dim() != 1 or queries.numel() < 1 or queries.dtype not in (torch.int32, torch.int64):
-            raise ValueError("queries must be a non-empty 1-D integer index tensor")
-        cq = c.index_select(0, queries.long()).contiguous()
-    Q = cq.shape[0]
-    omega = None
-    if query_weights is not None:
-        if tuple(query_weights.shape) != (Q,):
-            raise ValueError("query_weights must be [%d], got %s" % (Q, tuple(query_weights.shape)))
-        _lib.require_gpu(query_weights)
-        omega = (query_weights if query_weights.dtype == torch.float32 else query_weights.float()).contiguous()
-    if torch.is_tensor(bandwidth):
-        _lib.require_gpu(bandwidth)
-        bw = bandwidth if bandwidth.dtype == torch.float32 else bandwidth.float()
-    else:
-        bw = float(bandwidth)
-    D = cost_xy(cq, c, 1.0).contiguous()
-    w = _KernelWeights.apply(D, bw)
-    return _ConditionalSinkhornLoss.apply(tag, float(scaling_coef), eps, L, _LMIN, w, omega, *vids, *feats)
+    cq = _query_rows(c, queries, tag)
+    _check_query_weights(query_weights, cq.shape[0])
+    omega = _gpu_f32(query_weights)
+    bw = _gpu_f32(bandwidth) if torch.is_tensor(bandwidth) else float(bandwidth)
+    w = _KernelWeights.apply(cost_xy(cq, c, 1.0).contiguous(), bw)
+    return _SinkhornLoss.apply(_CONDITIONAL, tag, float(scaling_coef), eps, L, _LMIN, *vids, *feats, w, omega)
 
 
 def raise_if_solver_aborted(tags=("compute_sinkhorn_loss",)):
