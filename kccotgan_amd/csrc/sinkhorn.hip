@@ -999,6 +999,28 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
 // every path (both roles run the same loop with the same wave-uniform trip counts; only the work between barriers differs).
 // Host: taken when 2 TR <= 1024 (kccot_sinkhorn_fused_roles_eligible); otherwise sinkhorn_fused_reg runs.
 // ------------------------------------------------------------------------------------------
+// Wave priority in the reverse sweep.  The two roles share every SIMD (two waves of each in the 1024-thread
+// instances) and the SIMD's vector port goes to the higher priority, then to the older wave: at equal priority the row
+// role's waves (the older ones) win it in both passes, and the column role's chain, which the whole workgroup waits for in
+// pass B, gets the slots the row role's plan leaves.  So the role that is on the chain runs its pass raised and drops to 0 in
+// front of the barrier that ends it; the role evaluating its plan runs at 0.  s_setprio is a scalar instruction that ignores
+// EXEC: the role is a template parameter, so each instantiation carries its own unconditional pair.
+// KCCOT_SWEEP_PRIO selects the form for experiment builds (profiles/sinkhorn_sweep_priority_ab.json): 0 none, 1 the chain
+// pass raised in both roles (the product: -4.5 us), 2 in the column role only (-3.2 us), 3 the column role raised for the
+// whole sweep (+1.9 us: the penalty only moves to pass A).  Levels 1, 2 and 3 measure the same.
+#ifndef KCCOT_SWEEP_PRIO
+#define KCCOT_SWEEP_PRIO 1
+#endif
+#ifndef KCCOT_SWEEP_PRIO_LEVEL
+#define KCCOT_SWEEP_PRIO_LEVEL 1
+#endif
+template <bool ON>
+__device__ __forceinline__ void sweep_prio(bool raised) {
+    if constexpr (ON) {
+        if (raised) __builtin_amdgcn_s_setprio(KCCOT_SWEEP_PRIO_LEVEL); else __builtin_amdgcn_s_setprio(0);
+    }
+}
+
 template <int EPT, int LPR, bool SHORTCUT, int NPROB, bool COL>
 __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* hist, float* gu, float* gv, float* red,
                                                  int* mis, const int TR) {
@@ -1214,15 +1236,19 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     // checks the emitted code of every instance).  The stamps of the diagnostic twin are taken behind the pinned registers, so
     // that they time the plan and not only its loads.
     if constexpr (!COL) { if (nits >= 1) { plan(nits); keep_in_regs(pl); } }
+    if constexpr (COL) sweep_prio<KCCOT_SWEEP_PRIO == 3>(true);
     for (int it = nits; it >= 1; --it) {
         KCCOT_STAMP(0);
-        if constexpr (COL) { plan(it); keep_in_regs(pl); KCCOT_STAMP(1); } else chain(it);              // (A) through v_t
+        if constexpr (COL) { plan(it); keep_in_regs(pl); KCCOT_STAMP(1); }                             // (A) through v_t
+        else { sweep_prio<KCCOT_SWEEP_PRIO == 1>(true); chain(it); sweep_prio<KCCOT_SWEEP_PRIO == 1>(false); }
         lds_barrier();
         KCCOT_STAMP(4);
-        if constexpr (COL) chain(it); else { if (it > 1) { plan(it - 1); keep_in_regs(pl); } KCCOT_STAMP(5); }   // (B) through u_t
+        if constexpr (COL) { sweep_prio<KCCOT_SWEEP_PRIO == 1 || KCCOT_SWEEP_PRIO == 2>(true); chain(it); sweep_prio<KCCOT_SWEEP_PRIO == 1 || KCCOT_SWEEP_PRIO == 2>(false); }
+        else { if (it > 1) { plan(it - 1); keep_in_regs(pl); } KCCOT_STAMP(5); }                           // (B) through u_t
         lds_barrier();
         KCCOT_STAMP(8);
     }
+    if constexpr (COL) sweep_prio<KCCOT_SWEEP_PRIO == 3>(false);
     KCCOT_STAMP_IF(true, 14);
     // dC = row-layout part + (column-layout part)^T
     float* dC = a.dC + (int64_t)p * n * n;

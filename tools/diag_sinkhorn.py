@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Where does a Sinkhorn half-step spend its cycles?  Loads the DIAGNOSTIC twin library
 (libkccot_diag.so, built with -DKCCOT_DIAG: s_memtime stamps around the phases of iteration 50)
-and prints per-wave cycle counts between stamps.  Never used by the product path.
+and prints per-wave cycle counts between stamps.  Never used by the product path.  KCCOT_LIB_PATH names another
+build of the twin (stamps of two trees side by side).
 usage: diag_sinkhorn.py [n [golden file]]      the forward kernel (sinkhorn_fwd_reg)
        diag_sinkhorn.py fused [n [golden file]] the fused solve + sweep, one-role and role-split: one sweep iteration
                                                (pass A, pass B) and one forward iteration, mean over waves and launches"""
 import ctypes, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-lib = ctypes.CDLL(os.path.join(ROOT, "kccotgan_amd", "csrc", "libkccot_diag.so"))
+# KCCOT_LIB_PATH: another build of the diagnostic twin (A/B stamps of two trees), as kccotgan_amd/_lib.py reads it
+lib = ctypes.CDLL(os.environ.get("KCCOT_LIB_PATH") or os.path.join(ROOT, "kccotgan_amd", "csrc", "libkccot_diag.so"))
 vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 lib.kccot_sinkhorn_fwd_f32.argtypes = [vp, ci, ci, cf, ci, ci, cf, ci, vp, vp, vp, vp, vp, vp, sz, vp]
 FUSED = len(sys.argv) > 1 and sys.argv[1] == "fused"
