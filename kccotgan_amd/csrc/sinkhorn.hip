@@ -71,7 +71,7 @@ struct SinkArgs {
     unsigned long long* diag;   // diagnostic build only; null otherwise
     float* loss_out;      // mixed divergence 2*cost[0]-cost[1]-cost[2] (nprob == 3), or null
     int* ticket;          // arrival counter for loss_out: zero on entry, reset to zero by the last workgroup
-    int shortcut;         // 1: exact periodic-state shortcut enabled (see sinkhorn_fwd_reg)
+    int shortcut;         // 1: exact periodic-state shortcut enabled (shortcut_mismatch)
     // weighted marginals (the _w kernels only; an extension, not reference behaviour): strictly positive finite weights,
     // log taken once per lane before the loop.  w_div = 0: wa, wb are [nprob,n], problem p reads row p.  w_div = 1: wa =
     // w_real [n], wb = w_fake [n] and the three problems of the divergence read (a,b), (a,a), (b,b).  NULL: mu = nu = 1/n.
@@ -194,6 +194,181 @@ __device__ __forceinline__ void load_costs(const float* __restrict__ C, int n, i
     }
 }
 
+// ---- stages shared by the register forms ---------------------------------------------------------
+// sinkhorn_fwd_body, sinkhorn_bwd_body, sinkhorn_fused_reg and fused_roles_body are tested for BIT-identical results against
+// each other; the stages that more than one of them runs are defined once, here.  Barriers, pins and stamps stay at the call
+// sites, so that every wave of every form meets the same ones.  A stage is shared only where every kernel that calls it
+// keeps its registers, scratch, LDS and the opcode sequence of every loop that holds a barrier; the fused LDS prologue, the
+// forward's cost loop and ring fill and the sweep kernel's final-cost adjoint and dC write-back did not, and stay in their
+// bodies.
+
+// EXACT periodic-state shortcut.  One iteration is a deterministic function of the state (u,v).  As soon as the state after
+// iteration k equals, bit for bit, the state after iteration k-p (p <= 4) the sequence is periodic from there on, and the
+// state after any later iteration K is a stored state congruent to K modulo p: nothing is approximated, the loop is merely
+// not re-executed.  (Sharp problems -- costs of O(1e3) against eps = 1, the GAN regime -- reach an fp32 fixed point within a
+// handful of iterations.)  The kernel jumps to one iteration before the first point at which the reference's stop rule
+// could fire (or before L), fills the history the backward needs, and resumes the ordinary loop, so the stop logic and the
+// final iterate are computed by the same code as without the shortcut.  nits_out[p] is the reference-equivalent iteration
+// count; nits_out[nprob + p] the number of iterations actually executed.
+//
+// Detection costs no LDS round trip on the critical path: every lane keeps its line's last four duals in registers and
+// compares in place (shortcut_mismatch); one ballot per candidate period folds the wave's lines, lane 0 ORs the wave's mismatch
+// mask into an LDS word (shortcut_vote), and the word is read back after the closing barrier but only CONSUMED one
+// iteration later (shortcut_period: its latency hides under the next half-step).
+//
+// step (a): ORs into `bits` bit pp <=> the new dual sn differs from the one pp iterations earlier (cur: one iteration
+// earlier, p2 .. p4: the line's ring).  The ring stays three plain floats of the caller, which moves it on by one
+// (p4 = p3; p3 = p2; p2 = cur) right after the call: taken by reference the ring is promoted to registers only after
+// inlining, and the forward loops of the one-role kernels came out scheduled differently.
+__device__ __forceinline__ void shortcut_mismatch(int& bits, float sn, float cur, float p2, float p3, float p4) {
+    const unsigned b = __float_as_uint(sn);
+    bits |= (b != __float_as_uint(cur) ? 2 : 0) | (b != __float_as_uint(p2) ? 4 : 0) |
+           (b != __float_as_uint(p3) ? 8 : 0) | (b != __float_as_uint(p4) ? 16 : 0);
+}
+// step (b): the wave's vote into mis[it & 3]
+__device__ __forceinline__ void shortcut_vote(int bits, bool active, int t, int* mis, int it) {
+    if (!active) bits = 0;
+    int wb = 0;
+#pragma unroll
+    for (int pp = 1; pp <= 4; ++pp)
+        if (__builtin_amdgcn_ballot_w64((bits >> pp) & 1)) wb |= 1 << pp;
+    if ((t & 63) == 0 && wb) atomicOr(&mis[it & 3], wb);
+}
+// step (c), at the end of iteration `it`: the smallest period the PREVIOUS iteration's votes allow (0: none).  mprev
+// describes iteration it-1: bit pp clear <=> S_it == S_{it-pp} (valid for it-1 >= pp).
+__device__ __forceinline__ int shortcut_period(int* mis, int it, int t, int& mprev) {
+    const int mcur = mis[it & 3];                 // consumed at the end of the NEXT iteration
+    if (t == 0) mis[(it + 2) & 3] = 0;
+    int per = 0;
+#pragma unroll
+    for (int pp = 4; pp >= 1; --pp)
+        if (it - 1 >= pp && !((mprev >> pp) & 1)) per = pp;
+    mprev = mcur;
+    return per;
+}
+// ... and the iteration count K1 to resume at, so that iteration K1+1, the first at which the reference could leave its
+// loop early (or the last one), is real
+__device__ __forceinline__ int shortcut_resume(int L, int Lmin, int stop_mode) {
+    int first_stop = (stop_mode == KCCOT_STOP_INDEX) ? Lmin + 1 : Lmin;
+    if (first_stop < 1) first_stop = 1;
+    return (L < first_stop ? L : first_stop) - 1;
+}
+// The history fill of the jump in the fused kernels, whose history is in LDS: the states from S_{nits-per+1} on repeat with
+// period per, so row k <- row lo + (k - lo) mod per for k in (nits, K1].  (sinkhorn_fwd_body fills from its LDS ring instead.)
+__device__ __forceinline__ void fill_history_rows(float* hu, float* hv, int NS, int n, int t, int nits, int K1, int per) {
+    const int lo = nits - per + 1;
+    for (int e = t; e < (K1 - nits) * n; e += blockDim.x) {
+        const int k = nits + 1 + e / n, i = e % n;
+        const int src = lo + (k - lo) % per;
+        hu[k * NS + i] = hu[src * NS + i];
+        hv[k * NS + i] = hv[src * NS + i];
+    }
+}
+
+// gan_utils.py:162-164 in the fused kernels: pi = exp((-C + u + v^T)/eps); cost = sum(pi * C) over a row-layout lane's
+// entries (C re-read: L2-resident).  sinkhorn_fwd_body keeps its own loop, which also writes and poisons the plan.
+template <int EPT>
+__device__ __forceinline__ float cost_partial(const float (&crow)[EPT], float ui, const float* v, const float* C, int n,
+                                              int line, int q, bool active) {
+    float part = 0.f;
+    if (active) {
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) {
+            const int idx = q * EPT + m;
+            if (idx < n) {
+                const float pi = __builtin_amdgcn_exp2f((ui - crow[m]) + v[idx]);
+                part += pi * C[(int64_t)line * n + idx];
+            }
+        }
+    }
+    return part;
+}
+
+// Thread 0 of problem p publishes its cost and iteration counts; with `combine`, the last of the NPROB workgroups to arrive
+// writes loss = sum_p w[p] cost[p], added left to right: (2 c0 - c1) - c2 on three problems (gan_utils.py:225),
+// ((c0 + c1) - c2) - c3 on four (w[p] = +-1 or 2, so w[p] c[p] is exact and x + (-c) == x - c).
+// Placement-independent hand-off without fences -- the FIRST ROW of MI355X_MICROARCH.md's table of measured hand-offs ("one
+// lane of each storing workgroup ... an agent-scope atomic add; the workgroup whose add came last, told by the value its add
+// returned, loads only after its add has returned; stores all sc1, loads all sc1, 4-byte"): the handed-off word is stored
+// with agent scope (written through), the store drained (vmcnt(0)), then the relaxed ticket; the last arriver reads the
+// costs with agent-scope loads.  This is gfx950 behaviour, not a guarantee of the HIP memory model (under which it is a
+// race): the emitted cache-policy bits and the drain are pinned by
+// tests/test_abi.py::test_isa_of_the_three_cost_hand_off_to_the_combining_workgroup, and this library builds for gfx950
+// only.  (Until round 3: plain store + agent release fence + acquire fence in the last arriver -- an L2 write-back and an L1
+// invalidate, ~1.7 us each, on the one thread the workgroup then waits for.)
+// Three words are read back either way: on four problems the combining workgroup's own cost is the one in its register.
+// The pointers are taken as references to the members of the kernel-argument struct ON PURPOSE: by value all four are loaded
+// at the call, ahead of the branches that use them, and the one-role fused kernels came out with two more SGPRs.
+template <int NPROB>
+__device__ __forceinline__ void publish_cost(float* const& cost_out, int32_t* const& nits_out, float* const& loss_out,
+                                             int* const& ticket, int p, float cost, int nits, int computed, const float* w,
+                                             bool combine) {
+    __hip_atomic_store(cost_out + p, cost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    nits_out[p] = nits;
+    nits_out[gridDim.x + p] = computed;
+    if (!combine) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const int tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk == (int)gridDim.x - 1) {
+        float c[NPROB];
+        if constexpr (NPROB == 3) {
+#pragma unroll
+            for (int pp = 0; pp < 3; ++pp) c[pp] = __hip_atomic_load(cost_out + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            float o[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                o[k] = __hip_atomic_load(cost_out + ((p + 1 + k) & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int pp = 0; pp < 4; ++pp) {
+                const int k = (pp - p - 1) & 3;                    // pp = (p + 1 + k) & 3; k = 3 is p itself
+                c[pp] = k == 0 ? o[0] : k == 1 ? o[1] : k == 2 ? o[2] : cost;
+            }
+        }
+        float l = w[0] * c[0];
+#pragma unroll
+        for (int pp = 1; pp < NPROB; ++pp) l += w[pp] * c[pp];
+        loss_out[0] = l;
+        __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// Adjoint of the final cost, one entry of one orientation.  cost = sum_ij pi_ij C_ij, pi = exp2((U - c2) + V);  C/eps = c2*ln2:
+//   dcost/dC_ij (direct) = pi_ij (1 - C_ij/eps); dcost/du_i = sum_j pi_ij C_ij/eps; same for v
+// ROW: d = g * (direct term) and ss += pi_ij c2_ij, the line's part of dcost/du_i; column: d = 0 and the part of dcost/dv_j.
+// The loop over a lane's entries and the seg_sum stay with the caller: sinkhorn_fused_reg takes both orientations of an
+// entry in one loop trip, a role takes its own (sinkhorn_bwd_body keeps its own block).  gu[line] / gv[line] = g * seg_sum(ss) * LN2.
+template <bool ROW>
+__device__ __forceinline__ void final_cost_adjoint(float c2, float self, float other, bool ok, float g, float& d, float& ss) {
+    const float cc = ok ? c2 : 0.f;
+    const float pv = ok ? __builtin_amdgcn_exp2f(ROW ? ((self - cc) + other) : ((other - cc) + self)) : 0.f;
+    d = ROW ? g * pv * (1.f - cc * LN2) : 0.f;
+    ss += pv * cc;
+}
+
+// dC = row-layout part + (column-layout part)^T: the row lanes store, the column lanes add behind the caller's
+// __threadfence_block(); __syncthreads();
+template <int EPT>
+__device__ __forceinline__ void store_dc_rows(float* dC, const float (&drow)[EPT], int n, int line, int q, bool active) {
+    if (active) {
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) {
+            const int idx = q * EPT + m;
+            if (idx < n) dC[(int64_t)line * n + idx] = drow[m];
+        }
+    }
+}
+template <int EPT>
+__device__ __forceinline__ void add_dc_cols(float* dC, const float (&dcol)[EPT], int n, int line, int q, bool active) {
+    if (active) {
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) {
+            const int idx = q * EPT + m;
+            if (idx < n) dC[(int64_t)idx * n + line] += dcol[m];
+        }
+    }
+}
+
 template <int EPT, int LPR, bool SHORTCUT, bool WEIGHTED>
 __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     // padded so that the float4 reads of lines past n stay inside the arrays
@@ -230,23 +405,8 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     // stop rule in log2 units: sum|u-u_prev| = sum|U-U_prev| * eps*ln2
     const float err_scale = a.eps * LN2;
 
-    // EXACT shortcut.  One iteration is a deterministic function of the state (u,v).  As soon as the
-    // state after iteration k equals, bit for bit, the state after iteration k-p (p <= 4) the
-    // sequence is periodic from there on, and the state after any later iteration K is a stored
-    // state congruent to K modulo p: nothing is approximated, the loop is merely not re-executed.
-    // (Sharp problems -- costs of O(1e3) against eps = 1, the GAN regime -- reach an fp32 fixed point
-    // within a handful of iterations.)  The kernel jumps to one iteration before the first point at
-    // which the reference's stop rule could fire (or before L), fills the history the backward
-    // needs, and resumes the ordinary loop, so the stop logic and the final iterate are computed
-    // by the same code as without the shortcut.  nits_out[p] is the reference-equivalent iteration
-    // count; nits_out[nprob + p] the number of iterations actually executed.
-    //
-    // Detection costs no LDS round trip on the critical path: every lane keeps its line's last four
-    // duals in registers and compares in place; one ballot per candidate period folds the wave's
-    // lines, lane 0 ORs the wave's mismatch mask into an LDS word, and the word is read back after
-    // the closing barrier but only CONSUMED one iteration later (its latency hides under the next
-    // half-step).  The ring of the last four states in LDS is written every iteration and read
-    // only at the jump.
+    // The exact periodic-state shortcut (shortcut_mismatch).  The ring of the last four states in LDS is written every iteration and
+    // read only at the jump.
     __shared__ float ring_u[4][SK_MAXN], ring_v[4][SK_MAXN];
     __shared__ int mis[4];
     if (SHORTCUT) {
@@ -268,9 +428,7 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
         const float du = (active && q == 0) ? fabsf(un - ui) : 0.f;
         int bits = 0;
         if (SHORTCUT && detect) {
-            const unsigned b = __float_as_uint(un);
-            bits = (b != __float_as_uint(ui) ? 2 : 0) | (b != __float_as_uint(pu2) ? 4 : 0) |
-                   (b != __float_as_uint(pu3) ? 8 : 0) | (b != __float_as_uint(pu4) ? 16 : 0);
+            shortcut_mismatch(bits, un, ui, pu2, pu3, pu4);
             pu4 = pu3; pu3 = pu2; pu2 = ui;
         }
         ui = un;
@@ -285,16 +443,9 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
         const float vn = half_step<EPT, LPR, false>(ccol, vj, u_s, q, lwv);
         KCCOT_STAMP(4);
         if (SHORTCUT && detect) {
-            const unsigned b = __float_as_uint(vn);
-            bits |= (b != __float_as_uint(vj) ? 2 : 0) | (b != __float_as_uint(pv2) ? 4 : 0) |
-                    (b != __float_as_uint(pv3) ? 8 : 0) | (b != __float_as_uint(pv4) ? 16 : 0);
+            shortcut_mismatch(bits, vn, vj, pv2, pv3, pv4);
             pv4 = pv3; pv3 = pv2; pv2 = vj;
-            if (!active) bits = 0;
-            int wb = 0;
-#pragma unroll
-            for (int pp = 1; pp <= 4; ++pp)
-                if (__builtin_amdgcn_ballot_w64((bits >> pp) & 1)) wb |= 1 << pp;
-            if ((t & 63) == 0 && wb) atomicOr(&mis[it & 3], wb);
+            shortcut_vote(bits, active, t, mis, it);
         }
         vj = vn;
         if (active && q == 0) {
@@ -315,21 +466,11 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
             if (a.thresh > err) break;
         }
         if (SHORTCUT && detect) {
-            const int mcur = mis[it & 3];                 // consumed at the end of the NEXT iteration
-            if (t == 0) mis[(it + 2) & 3] = 0;
-            // mprev describes iteration it-1: bit pp clear <=> S_it == S_{it-pp} (valid for it-1 >= pp)
-            int per = 0;
-#pragma unroll
-            for (int pp = 4; pp >= 1; --pp)
-                if (it - 1 >= pp && !((mprev >> pp) & 1)) per = pp;          // smallest matching period
-            mprev = mcur;
+            const int per = shortcut_period(mis, it, t, mprev);
             KCCOT_STAMP(7);
             if (per) {
                 detect = false;
-                // first iteration count at which the reference could leave its loop early
-                int first_stop = (a.stop_mode == KCCOT_STOP_INDEX) ? a.Lmin + 1 : a.Lmin;
-                if (first_stop < 1) first_stop = 1;
-                const int K1 = (a.L < first_stop ? a.L : first_stop) - 1;   // resume so that iteration K1+1 is real
+                const int K1 = shortcut_resume(a.L, a.Lmin, a.stop_mode);
                 if (K1 > nits) {
                     // the states from S_{it-per} on have period per, and the ring holds S_{nits-3..nits}
                     // (S_k in slot (k-1) & 3): S_k = S_src(k), src(k) = lo + (k - lo) mod per, lo = nits-per+1
@@ -371,30 +512,9 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     float cost = block_sum(part, red);
     if (WEIGHTED && bad) { cost = NAN; nits = -1; }
     if (t == 0) {
-        // the last of the three workgroups to arrive combines the costs (gan_utils.py:225).  Placement-independent
-        // hand-off without fences -- the FIRST ROW of MI355X_MICROARCH.md's table of measured hand-offs ("one lane of each
-        // storing workgroup ... an agent-scope atomic add; the workgroup whose add came last, told by the value its add
-        // returned, loads only after its add has returned; stores all sc1, loads all sc1, 4-byte"): the handed-off word is
-        // stored with agent scope (written through), the store drained (vmcnt(0)), then the relaxed ticket; the last arriver
-        // reads the costs with agent-scope loads.  This is gfx950 behaviour, not a guarantee of the HIP memory model (under
-        // which it is a race): the emitted cache-policy bits and the drain are pinned by
-        // tests/test_abi.py::test_isa_of_the_three_cost_hand_off_to_the_combining_workgroup, and this library builds for
-        // gfx950 only.  (Until round 3: plain store + agent release fence + acquire fence in the last arriver -- an L2
-        // write-back and an L1 invalidate, ~1.7 us each, on the one thread the workgroup then waits for.)
-        __hip_atomic_store(a.cost_out + p, cost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.nits_out[p] = nits;
-        a.nits_out[gridDim.x + p] = computed;
-        if (a.loss_out) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int tk = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk == (int)gridDim.x - 1) {
-                const float c0 = __hip_atomic_load(a.cost_out + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const float c1 = __hip_atomic_load(a.cost_out + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const float c2 = __hip_atomic_load(a.cost_out + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                a.loss_out[0] = (2.0f * c0 - c1) - c2;
-                __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        // with loss_out, the last of the three workgroups to arrive combines the costs (gan_utils.py:225)
+        const float w[3] = {2.0f, -1.0f, -1.0f};
+        publish_cost<3>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost, nits, computed, w, a.loss_out != nullptr);
     }
 }
 
@@ -693,8 +813,9 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_bwd_reg_dw(SinkBwdArgs a) { 
 //   * d loss / d C is produced for dLoss = 1 with the per-problem weights of the launch: {2,-1,-1} of gan_utils.py:225
 //     on three problems (compute_sinkhorn_loss), {+1,+1,-1,-1} on four (compute_mixed_sinkhorn_loss); the cost backward
 //     multiplies by the upstream scalar when it builds its coefficients (the gradient is linear in it).
-// Arithmetic is that of sinkhorn_fwd_body / sinkhorn_bwd_reg, instruction for instruction: costs, iteration counts and
-// duals are bit-identical to the two-kernel path, dC to the two-kernel path at the same lanes-per-line.
+// Arithmetic is that of sinkhorn_fwd_body / sinkhorn_bwd_body, instruction for instruction (half_step and the shared stages
+// above): costs, iteration counts and duals are bit-identical to the two-kernel path, dC to the two-kernel path at the same
+// lanes-per-line.
 // Eligibility (host): n <= 128 and 2 (L+1) NS floats of history within the CU's LDS; otherwise the two kernels run.
 // ------------------------------------------------------------------------------------------
 struct SinkFusedArgs {
@@ -750,7 +871,7 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     float pu2 = 0.f, pu3 = 0.f, pu4 = 0.f, pv2 = 0.f, pv3 = 0.f, pv4 = 0.f;
     int nits = 0;
     float ui = 0.f, vj = 0.f;
-    // ---------------------------------------------------------------- forward (see sinkhorn_fwd_body)
+    // ---------------------------------------------------------------- forward (the loop of sinkhorn_fwd_body on LDS history)
     KCCOT_STAMP_IF(true, 11);                                  // 11 .. 12: the whole forward loop
     for (int it = 0; it < L; ++it) {
         KCCOT_STAMP(9);
@@ -758,9 +879,7 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         const float du = (active && q == 0) ? fabsf(un - ui) : 0.f;
         int bits = 0;
         if (SHORTCUT && detect) {
-            const unsigned b = __float_as_uint(un);
-            bits = (b != __float_as_uint(ui) ? 2 : 0) | (b != __float_as_uint(pu2) ? 4 : 0) |
-                   (b != __float_as_uint(pu3) ? 8 : 0) | (b != __float_as_uint(pu4) ? 16 : 0);
+            shortcut_mismatch(bits, un, ui, pu2, pu3, pu4);
             pu4 = pu3; pu3 = pu2; pu2 = ui;
         }
         ui = un;
@@ -768,16 +887,9 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         lds_barrier();
         const float vn = half_step<EPT, LPR, false>(ccol, vj, hu + (it + 1) * NS, q, lw2);
         if (SHORTCUT && detect) {
-            const unsigned b = __float_as_uint(vn);
-            bits |= (b != __float_as_uint(vj) ? 2 : 0) | (b != __float_as_uint(pv2) ? 4 : 0) |
-                    (b != __float_as_uint(pv3) ? 8 : 0) | (b != __float_as_uint(pv4) ? 16 : 0);
+            shortcut_mismatch(bits, vn, vj, pv2, pv3, pv4);
             pv4 = pv3; pv3 = pv2; pv2 = vj;
-            if (!active) bits = 0;
-            int wb = 0;
-#pragma unroll
-            for (int pp = 1; pp <= 4; ++pp)
-                if (__builtin_amdgcn_ballot_w64((bits >> pp) & 1)) wb |= 1 << pp;
-            if ((t & 63) == 0 && wb) atomicOr(&mis[it & 3], wb);
+            shortcut_vote(bits, active, t, mis, it);
         }
         vj = vn;
         if (active && q == 0) hv[(it + 1) * NS + line] = vn;
@@ -790,26 +902,12 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
             if (a.thresh > err) break;
         }
         if (SHORTCUT && detect) {
-            const int mcur = mis[it & 3];
-            if (t == 0) mis[(it + 2) & 3] = 0;
-            int per = 0;
-#pragma unroll
-            for (int pp = 4; pp >= 1; --pp)
-                if (it - 1 >= pp && !((mprev >> pp) & 1)) per = pp;
-            mprev = mcur;
+            const int per = shortcut_period(mis, it, t, mprev);
             if (per) {
                 detect = false;
-                int first_stop = a.Lmin < 1 ? 1 : a.Lmin;
-                const int K1 = (L < first_stop ? L : first_stop) - 1;
+                const int K1 = shortcut_resume(L, a.Lmin, KCCOT_STOP_COUNT);
                 if (K1 > nits) {
-                    // states from S_{nits-per+1} on repeat with period per: row k <- row lo + (k - lo) mod per
-                    const int lo = nits - per + 1;
-                    for (int e = t; e < (K1 - nits) * n; e += blockDim.x) {
-                        const int k = nits + 1 + e / n, i = e % n;
-                        const int src = lo + (k - lo) % per;
-                        hu[k * NS + i] = hu[src * NS + i];
-                        hv[k * NS + i] = hv[src * NS + i];
-                    }
+                    fill_history_rows(hu, hv, NS, n, t, nits, K1, per);
                     __syncthreads();
                     ui = hu[K1 * NS + (active ? line : 0)];
                     vj = hv[K1 * NS + (active ? line : 0)];
@@ -821,56 +919,13 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     }
 
     KCCOT_STAMP_IF(true, 12);
-    // gan_utils.py:162-164: pi = exp((-C + u + v^T)/eps); cost = sum(pi * C)
     const float* Vn = hv + nits * NS;
     const float* Un = hu + nits * NS;
-    float part = 0.f;
-    if (active) {
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = q * EPT + m;
-            if (idx < n) {
-                const float pi = __builtin_amdgcn_exp2f((ui - crow[m]) + Vn[idx]);
-                part += pi * C[(int64_t)line * n + idx];
-            }
-        }
-    }
+    const float part = cost_partial<EPT>(crow, ui, Vn, C, n, line, q, active);
     const float cost = block_sum(part, red);
-    if (t == 0) {
-        // (fence-free hand-off as in sinkhorn_fwd_body: agent-scope store, drained, then the ticket)
-        __hip_atomic_store(a.cost_out + p, cost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a.nits_out[p] = nits;
-        a.nits_out[gridDim.x + p] = computed;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int tk = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tk == (int)gridDim.x - 1) {
-            // sum_p w[p] c[p] left to right: (2 c0 - c1) - c2 on three problems, ((c0 + c1) - c2) - c3 on four (w[p] c[p]
-            // is exact and x + (-c) == x - c).  Three words are read back either way: on four problems the combining
-            // workgroup's own cost is the one in its register.
-            float c[NPROB];
-            if constexpr (NPROB == 3) {
-#pragma unroll
-                for (int pp = 0; pp < 3; ++pp) c[pp] = __hip_atomic_load(a.cost_out + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                float o[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    o[k] = __hip_atomic_load(a.cost_out + ((p + 1 + k) & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (int pp = 0; pp < 4; ++pp) {
-                    const int k = (pp - p - 1) & 3;                    // pp = (p + 1 + k) & 3; k = 3 is p itself
-                    c[pp] = k == 0 ? o[0] : k == 1 ? o[1] : k == 2 ? o[2] : cost;
-                }
-            }
-            float l = a.w[0] * c[0];
-#pragma unroll
-            for (int pp = 1; pp < NPROB; ++pp) l += a.w[pp] * c[pp];
-            a.loss_out[0] = l;
-            __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost, nits, computed, a.w, true);
 
-    // ---------------------------------------------------------------- reverse sweep (see sinkhorn_bwd_reg)
+    // ---------------------------------------------------------------- reverse sweep (sinkhorn_bwd_body on LDS history)
     const float g = a.w[p];                                   // d(sum_p w[p] cost[p]) / d cost[p] at dLoss = 1
     const int lsafe = active ? line : 0;
     float drow[EPT], dcol[EPT];
@@ -883,13 +938,8 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
 #pragma unroll
         for (int m = 0; m < EPT; ++m) {
             const bool ok = active && (q * EPT + m) < n;
-            const float cr = ok ? crow[m] : 0.f, cc = ok ? ccol[m] : 0.f;
-            const float pr = ok ? __builtin_amdgcn_exp2f((uf - cr) + ov[m]) : 0.f;
-            drow[m] = g * pr * (1.f - cr * LN2);
-            dcol[m] = 0.f;
-            su += pr * cr;
-            const float pc = ok ? __builtin_amdgcn_exp2f((ou[m] - cc) + vf) : 0.f;
-            sv += pc * cc;
+            final_cost_adjoint<true>(crow[m], uf, ov[m], ok, g, drow[m], su);
+            final_cost_adjoint<false>(ccol[m], vf, ou[m], ok, g, dcol[m], sv);
         }
         su = seg_sum<LPR>(su);
         sv = seg_sum<LPR>(sv);
@@ -961,24 +1011,11 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         KCCOT_STAMP(8);
     }
     KCCOT_STAMP_IF(true, 14);
-    // dC = row-layout part + (column-layout part)^T
     float* dC = a.dC + (int64_t)p * n * n;
-    if (active) {
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = q * EPT + m;
-            if (idx < n) dC[(int64_t)line * n + idx] = drow[m];
-        }
-    }
+    store_dc_rows<EPT>(dC, drow, n, line, q, active);
     __threadfence_block();
     __syncthreads();
-    if (active) {
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = q * EPT + m;
-            if (idx < n) dC[(int64_t)idx * n + line] += dcol[m];
-        }
-    }
+    add_dc_cols<EPT>(dC, dcol, n, line, q, active);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1043,6 +1080,7 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
         const bool ok = line < n && idx < n;
         c2[m] = ok ? C[COL ? (int64_t)idx * n + line : (int64_t)line * n + idx] * k2 : INFINITY;
     }
+    // row 0, the pad columns, gu / gv and mis zeroed, by every thread of both roles (the prologue of sinkhorn_fused_reg)
     for (int i = t; i < NS; i += blockDim.x) { hu[i] = 0.f; hv[i] = 0.f; }
     if (NS > n) {
         const int padw = NS - n;
@@ -1064,22 +1102,16 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     int nits = 0;
     float self = 0.f;                                          // ui (row role) / vj (column role)
     // one half-step of this role: the dual, its history row (the next half-step's exchange array) and the shortcut's
-    // mismatch bits, OR-ed into mis[] per wave (both roles do, each with its own half of sinkhorn_fused_reg's `bits`)
+    // mismatch bits, OR-ed into mis[] per wave (both roles vote, each with the bits of its own dual)
     auto own_half_step = [&](int it, float& du) {
         const float sn = half_step<EPT, LPR, !COL>(c2, self, ho + (COL ? it + 1 : it) * NS, q, lw2);
         du = (active && q == 0) ? fabsf(sn - self) : 0.f;
         if (active && q == 0) hs[(it + 1) * NS + line] = sn;
         if (SHORTCUT && detect) {
-            const unsigned b = __float_as_uint(sn);
-            int bits = (b != __float_as_uint(self) ? 2 : 0) | (b != __float_as_uint(p2) ? 4 : 0) |
-                       (b != __float_as_uint(p3) ? 8 : 0) | (b != __float_as_uint(p4) ? 16 : 0);
+            int bits = 0;
+            shortcut_mismatch(bits, sn, self, p2, p3, p4);
             p4 = p3; p3 = p2; p2 = self;
-            if (!active) bits = 0;
-            int wb = 0;
-#pragma unroll
-            for (int pp = 1; pp <= 4; ++pp)
-                if (__builtin_amdgcn_ballot_w64((bits >> pp) & 1)) wb |= 1 << pp;
-            if ((t & 63) == 0 && wb) atomicOr(&mis[it & 3], wb);
+            shortcut_vote(bits, active, t, mis, it);
         }
         self = sn;
     };
@@ -1100,25 +1132,12 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
             if (a.thresh > err) break;
         }
         if (SHORTCUT && detect) {
-            const int mcur = mis[it & 3];
-            if (t == 0) mis[(it + 2) & 3] = 0;
-            int per = 0;
-#pragma unroll
-            for (int pp = 4; pp >= 1; --pp)
-                if (it - 1 >= pp && !((mprev >> pp) & 1)) per = pp;
-            mprev = mcur;
+            const int per = shortcut_period(mis, it, t, mprev);
             if (per) {
                 detect = false;
-                int first_stop = a.Lmin < 1 ? 1 : a.Lmin;
-                const int K1 = (L < first_stop ? L : first_stop) - 1;
+                const int K1 = shortcut_resume(L, a.Lmin, KCCOT_STOP_COUNT);
                 if (K1 > nits) {
-                    const int lo = nits - per + 1;
-                    for (int e = t; e < (K1 - nits) * n; e += blockDim.x) {
-                        const int k = nits + 1 + e / n, i = e % n;
-                        const int src = lo + (k - lo) % per;
-                        hu[k * NS + i] = hu[src * NS + i];
-                        hv[k * NS + i] = hv[src * NS + i];
-                    }
+                    fill_history_rows(hu, hv, NS, n, t, nits, K1, per);
                     __syncthreads();
                     self = hs[K1 * NS + (active ? line : 0)];
                     nits = K1;
@@ -1129,54 +1148,14 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     }
 
     KCCOT_STAMP_IF(true, 12);
-    // gan_utils.py:162-164: pi = exp((-C + u + v^T)/eps); cost = sum(pi * C): the row role's lanes, zeros from the others
+    // the final cost: the row role's lanes, zeros from the others
     const float* Vn = hv + nits * NS;
     const float* Un = hu + nits * NS;
     float part = 0.f;
-    if constexpr (!COL) {
-        if (active) {
-#pragma unroll
-            for (int m = 0; m < EPT; ++m) {
-                const int idx = q * EPT + m;
-                if (idx < n) {
-                    const float pi = __builtin_amdgcn_exp2f((self - c2[m]) + Vn[idx]);
-                    part += pi * C[(int64_t)line * n + idx];
-                }
-            }
-        }
-    }
+    if constexpr (!COL) part = cost_partial<EPT>(c2, self, Vn, C, n, line, q, active);
     const float cost = block_sum(part, red);
     if constexpr (!COL) {
-        if (t == 0) {
-            // (fence-free hand-off as in sinkhorn_fwd_body / sinkhorn_fused_reg: agent-scope store, drained, then the ticket)
-            __hip_atomic_store(a.cost_out + p, cost, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.nits_out[p] = nits;
-            a.nits_out[gridDim.x + p] = computed;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int tk = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk == (int)gridDim.x - 1) {
-                float c[NPROB];
-                if constexpr (NPROB == 3) {
-#pragma unroll
-                    for (int pp = 0; pp < 3; ++pp) c[pp] = __hip_atomic_load(a.cost_out + pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    float o[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        o[k] = __hip_atomic_load(a.cost_out + ((p + 1 + k) & 3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int pp = 0; pp < 4; ++pp) {
-                        const int k = (pp - p - 1) & 3;
-                        c[pp] = k == 0 ? o[0] : k == 1 ? o[1] : k == 2 ? o[2] : cost;
-                    }
-                }
-                float l = a.w[0] * c[0];
-#pragma unroll
-                for (int pp = 1; pp < NPROB; ++pp) l += a.w[pp] * c[pp];
-                a.loss_out[0] = l;
-                __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost, nits, computed, a.w, true);
     }
 
     // ---------------------------------------------------------------- reverse sweep
@@ -1189,13 +1168,7 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
         load_other<EPT>(oo, COL ? Un : Vn, q);
         float ss = 0.f;
 #pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const bool ok = active && (q * EPT + m) < n;
-            const float cc = ok ? c2[m] : 0.f;
-            const float pv = ok ? __builtin_amdgcn_exp2f(COL ? ((oo[m] - cc) + sf) : ((sf - cc) + oo[m])) : 0.f;
-            d[m] = COL ? 0.f : g * pv * (1.f - cc * LN2);
-            ss += pv * cc;
-        }
+        for (int m = 0; m < EPT; ++m) final_cost_adjoint<!COL>(c2[m], sf, oo[m], active && (q * EPT + m) < n, g, d[m], ss);
         ss = seg_sum<LPR>(ss);
         if (active && q == 0) (COL ? gv : gu)[line] = g * ss * LN2;
     }
@@ -1250,28 +1223,11 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     }
     if constexpr (COL) sweep_prio<KCCOT_SWEEP_PRIO == 3>(false);
     KCCOT_STAMP_IF(true, 14);
-    // dC = row-layout part + (column-layout part)^T
     float* dC = a.dC + (int64_t)p * n * n;
-    if constexpr (!COL) {
-        if (active) {
-#pragma unroll
-            for (int m = 0; m < EPT; ++m) {
-                const int idx = q * EPT + m;
-                if (idx < n) dC[(int64_t)line * n + idx] = d[m];
-            }
-        }
-    }
+    if constexpr (!COL) store_dc_rows<EPT>(dC, d, n, line, q, active);
     __threadfence_block();
     __syncthreads();
-    if constexpr (COL) {
-        if (active) {
-#pragma unroll
-            for (int m = 0; m < EPT; ++m) {
-                const int idx = q * EPT + m;
-                if (idx < n) dC[(int64_t)idx * n + line] += d[m];
-            }
-        }
-    }
+    if constexpr (COL) add_dc_cols<EPT>(dC, d, n, line, q, active);
 }
 
 template <int EPT, int LPR, bool SHORTCUT, int NPROB>
@@ -1515,29 +1471,30 @@ extern "C" int kccot_sinkhorn_fused_roles_eligible(int n, int L) {
     return 2 * sink_geom(n, true).threads <= SK_MAXT;
 }
 
-template <int EPT, int LPR, bool SC, int NP>
-static int launch_fused_roles_np(const SinkFusedArgs& a, size_t lds, hipStream_t st) {
-    if constexpr ((EPT == 4 && LPR == 16) || (EPT == 16 && LPR == 8)) {
-        return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused_roles: no <%d,%d> instance", EPT, LPR);
-    } else {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_fused_roles<EPT, LPR, SC, NP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
-            return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused_roles: cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL((sinkhorn_fused_roles<EPT, LPR, SC, NP>), dim3(NP), dim3(2 * ((a.n * LPR + 63) / 64 * 64)), lds, st, a);
-        return launch_status("sinkhorn_fused_roles");
-    }
+// one workgroup of `threads` per problem, the history in `lds` bytes of dynamic LDS
+// (`what` heads the error text, `name` is the kernel's name for launch_status)
+static int launch_fused_kernel(void (*kernel)(SinkFusedArgs), int threads, const char* what, const char* name, int nprob,
+                               const SinkFusedArgs& a, size_t lds, hipStream_t st) {
+    // on every launch: the attribute belongs to the current device's copy of the function (a per-process "done" flag
+    // would be wrong on a second device and racy between threads); it is a host-side table write
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) !=
+        hipSuccess)
+        return fail(KCCOT_EUNSUPPORTED, "%s: cannot raise the dynamic LDS limit", what);
+    hipLaunchKernelGGL(kernel, dim3(nprob), dim3(threads), lds, st, a);
+    return launch_status(name);
 }
 
 template <int EPT, int LPR, bool SC, int NP>
 static int launch_fused_np(const SinkFusedArgs& a, size_t lds, hipStream_t st) {
-    if (kccot_sinkhorn_fused_roles_eligible(a.n, a.L)) return launch_fused_roles_np<EPT, LPR, SC, NP>(a, lds, st);
-    // on every launch: the attribute belongs to the current device's copy of the function (a per-process "done" flag
-    // would be wrong on a second device and racy between threads); it is a host-side table write
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_fused_reg<EPT, LPR, SC, NP>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
-        return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL((sinkhorn_fused_reg<EPT, LPR, SC, NP>), dim3(NP), dim3((a.n * LPR + 63) / 64 * 64), lds, st, a);
-    return launch_status("sinkhorn_fused_reg");
+    const int tr = (a.n * LPR + 63) / 64 * 64;
+    if (kccot_sinkhorn_fused_roles_eligible(a.n, a.L)) {
+        if constexpr ((EPT == 4 && LPR == 16) || (EPT == 16 && LPR == 8))
+            return fail(KCCOT_EUNSUPPORTED, "sinkhorn_fused_roles: no <%d,%d> instance", EPT, LPR);
+        else
+            return launch_fused_kernel(sinkhorn_fused_roles<EPT, LPR, SC, NP>, 2 * tr, "sinkhorn_fused_roles", "sinkhorn_fused_roles", NP,
+                                       a, lds, st);
+    }
+    return launch_fused_kernel(sinkhorn_fused_reg<EPT, LPR, SC, NP>, tr, "sinkhorn_fused", "sinkhorn_fused_reg", NP, a, lds, st);
 }
 
 template <int EPT, int LPR, bool SC>

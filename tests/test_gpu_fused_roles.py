@@ -4,9 +4,9 @@ the four-problem entry of the mixed loss (kccot_mixed_sinkhorn_loss_fwd_f32 on a
 halves of nits_out, loss_out, dC and the ticket left at zero.
 
 Shapes -- the smallest at which each way of the split can go wrong: n = 64 (2 x 512 threads, the full workgroup); 33 and 40
-(the role boundary at 320 threads, pad lines and pad columns in both roles); 17 and 32 at 16 lanes per line; 64 at 4 lanes
-per line; 64 at 16 lanes per line and 100 with sinkhorn_fused_max_n = 128, where two roles do not fit 1024 threads and the
-one-role kernel must run under either setting."""
+(the role boundary at 320 threads, pad lines and pad columns in both roles); 16 (one entry per lane), 17 and 32 at 16 lanes
+per line; 64 at 4 lanes per line; 64 and 33 (pad columns) at 16 lanes per line and 100 with sinkhorn_fused_max_n = 128, where two
+roles do not fit 1024 threads and the one-role kernel must run under either setting."""
 import os
 
 import numpy as np
@@ -19,8 +19,8 @@ from oracle import gan_utils_np as o
 DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 # (n, sinkhorn_lanes_per_line, sinkhorn_fused_max_n, the role kernel runs)
-SHAPES = [(64, 0, 64, True), (33, 0, 64, True), (40, 0, 64, True), (17, 0, 64, True), (32, 0, 64, True), (64, 4, 64, True),
-          (64, 16, 64, False), (100, 0, 128, False)]
+SHAPES = [(64, 0, 64, True), (33, 0, 64, True), (40, 0, 64, True), (16, 0, 64, True), (17, 0, 64, True), (32, 0, 64, True),
+          (64, 4, 64, True), (64, 16, 64, False), (33, 16, 64, False), (100, 0, 128, False)]
 IDS = ["n%d_lanes%d" % s[:2] for s in SHAPES]
 # (L, Lmin, thresh): L = 1, 2, 7, 100 with Lmin = L, and an early stop after Lmin = 3
 ITERS = [(1, 1, 1e-2), (2, 2, 1e-2), (7, 7, 1e-2), (100, 100, 1e-2), (100, 3, 1e30)]
