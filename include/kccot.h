@@ -289,7 +289,9 @@ int kccot_pairwise_cost_bwd_f32(const float* g, const float* x, const float* y, 
  * iterations the kernel actually executed -- fewer when the fp32 state became bit-for-bit periodic
  * and the remaining iterations were skipped EXACTLY (option "sinkhorn_shortcut" = 0 disables that).
  * u_hist / v_hist [nprob,L,n] receive u and v after every executed iteration (needed by the
- * backward; pass NULL for a forward-only evaluation).  pi_out [nprob,n,n] optional.
+ * backward; pass NULL for a forward-only evaluation), in the units the solver carries them in: u / (eps ln 2)
+ * at n <= 128, u itself above; rows at and beyond nits_out[p] are not written and the backward never reads them.
+ * pi_out [nprob,n,n] optional.
  * ------------------------------------------------------------------------------------------- */
 size_t kccot_sinkhorn_workspace_bytes(int nprob, int n);
 int kccot_sinkhorn_fwd_f32(const float* C, int nprob, int n, float eps, int L, int Lmin,
