@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
-``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h`` and
-``include/kccot_smooth_causal3.h``).
+``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h``,
+``include/kccot_smooth_causal3.h`` and ``include/kccot_smooth_sigma.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -176,6 +176,14 @@ SMOOTH3C_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_smooth_sigma.h one to one (the gradient of the kernel smoothing w.r.t. its
+# bandwidth sigma: an extension outside the versioned surface of kccot.h).  axes_flags: axis bits and SMOOTH_CAUSAL_T only.
+SMOOTH_SIGMA_SIGNATURES = {
+    "kccot_smooth_dsigma_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kccot_smooth_dsigma_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -188,7 +196,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) +
                               list(CONDITIONAL_SIGNATURES.items()) + list(WEIGHT_GRAD_SIGNATURES.items()) +
-                              list(SMOOTH3C_SIGNATURES.items())):
+                              list(SMOOTH3C_SIGNATURES.items()) + list(SMOOTH_SIGMA_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
 // per axis plus the max/scale pass (algorithmic minimum: one read + one write in total).
 #include "common.h"
 #include "options.h"
+#include "smooth_internal.h"
 #include "../../include/kccot_smooth_causal3.h"
 #include <math.h>
 #include <float.h>
@@ -20,35 +21,6 @@
 #include <stdint.h>
 
 namespace kccot {
-
-constexpr int SM_MAXR = 7;
-
-struct Taps { float w[2 * SM_MAXR + 1]; int r; };
-
-// data_utils.py:483-491: kernel = exp(-0.5/sigma^2 * x^2) (fp32), normalised by its fp32 sum
-static Taps make_taps(float sigma, int r) {
-    Taps tp{};
-    tp.r = r;
-    const float coef = (float)(-0.5 / ((double)sigma * (double)sigma));
-    float sum = 0.f;
-    for (int d = -r; d <= r; ++d) { tp.w[d + r] = expf(coef * (float)(d * d)); sum += tp.w[d + r]; }
-    for (int d = 0; d <= 2 * r; ++d) tp.w[d] /= sum;
-    return tp;
-}
-
-// KCCOT_SMOOTH_CAUSAL_T (NOT reference behaviour: the reference has no one-sided smoothing).  w[d] = exp(-d^2 / (2 sigma^2)),
-// d = 0..r, is the non-negative half of the taps above before their normalisation (w[0] = 1); iz[t] = 1 / Z_t with
-// Z_t = w[0] + .. + w[min(r, t)] summed in fp32 in ascending d, t = 0..r (every t >= r has Z_r).  Entries behind r are zero.
-struct CausalTaps { float w[SM_MAXR + 1]; float iz[SM_MAXR + 1]; int r; };
-
-static CausalTaps make_causal_taps(float sigma, int r) {
-    CausalTaps ct{};
-    ct.r = r;
-    const float coef = (float)(-0.5 / ((double)sigma * (double)sigma));
-    float z = 0.f;
-    for (int d = 0; d <= r; ++d) { ct.w[d] = expf(coef * (float)(d * d)); z += ct.w[d]; ct.iz[d] = 1.0f / z; }
-    return ct;
-}
 
 __device__ __forceinline__ int reflect(int p, int len) { return p < 0 ? -p : (p >= len ? 2 * (len - 1) - p : p); }
 
@@ -2361,14 +2333,18 @@ static int smooth_bwd_stats(const float* gout, const float* out, int64_t n, cons
                             bool fold, float* stats_ext, hipStream_t st, float** res) {
     *res = (stats_only || stats_in) ? stats_ext : w.scal;
     if (stats_in || fold) return 0;
+    return smooth_maxnorm_stats(gout, out, n, w.pdot, w.pcnt, *res, st);
+}
+
+int kccot::smooth_maxnorm_stats(const float* gout, const float* out, int64_t n, float* pdot, float* pcnt, float* res, hipStream_t st) {
     int rc;
     const int64_t nb = (n + 255) / 256;
     const bool wide = (n % 4 == 0) && ((uintptr_t)gout % 16 == 0) && ((uintptr_t)out % 16 == 0) && nb >= 2048;
-    if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, w.pdot, w.pcnt);
-    else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, w.pdot, w.pcnt);
+    if (wide) hipLaunchKernelGGL(maxnorm_bwd_partial_v4, dim3(2048), dim3(256), 0, st, gout, out, n / 4, pdot, pcnt);
+    else hipLaunchKernelGGL(maxnorm_bwd_partial, dim3((unsigned)nb), dim3(256), 0, st, gout, out, n, pdot, pcnt);
     if ((rc = launch_status("maxnorm_bwd_partial"))) return rc;
-    hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)w.pdot, (const float*)w.pcnt,
-                       wide ? (int64_t)2048 : nb, *res);
+    hipLaunchKernelGGL(maxnorm_bwd_combine, dim3(1), dim3(1024), 0, st, (const float*)pdot, (const float*)pcnt,
+                       wide ? (int64_t)2048 : nb, res);
     return launch_status("maxnorm_bwd_combine");
 }
 

@@ -22,15 +22,79 @@ def _entry(axes):
     return lib.kccot_smooth_fwd_f32, lib.kccot_smooth_bwd_f32, lib.kccot_smooth_bwd_sharded_f32, axes
 
 
+def _sigma_bits(axes):
+    """`axes_flags` of kccot_smooth_dsigma_f32 (include/kccot_smooth_sigma.h) for an `axes` value: there the causal 3-D form
+    is spelled with the axis bits."""
+    if axes == CAUSAL3:
+        return _lib.SMOOTH_T | _lib.SMOOTH_H | _lib.SMOOTH_W | _lib.SMOOTH_CAUSAL_T
+    return axes
+
+
+def _fwd(x, sigma, radius, axes):
+    B, H, T, W, C = x.shape
+    out = _lib.empty_like(x)
+    mx = _lib.empty((1,), torch.float32, x.device)
+    ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), x)
+    fwd, _, _, bits = _entry(axes)
+    check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits, ptr(out), ptr(mx), ws, wsb, stream_of(x)), "smooth_fwd")
+    return out, mx
+
+
+def _bwd(g, out, mx, sigma, radius, axes):
+    B, H, T, W, C = out.shape
+    din = _lib.empty_like(out)
+    ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), out)
+    _, bwd, _, bits = _entry(axes)
+    check(bwd(ptr(g), ptr(out), ptr(mx), B, H, T, W, C, sigma, radius, bits, ptr(din), ws, wsb, stream_of(out)),
+          "smooth_bwd")
+    return din
+
+
+def _fwd_sharded(x, sigma, radius, axes, group):
+    import torch.distributed as dist
+    B, H, T, W, C = x.shape
+    out = _lib.empty_like(x)
+    mx = _lib.empty((1,), torch.float32, x.device)
+    ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), x)
+    fwd, _, _, bits = _entry(axes)
+    check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_NO_DIVIDE, ptr(out), ptr(mx), ws, wsb, stream_of(x)),
+          "smooth_fwd")
+    _all_reduce(mx, dist.ReduceOp.MAX, group)
+    check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_EXTERNAL_MAX, ptr(out), ptr(mx), ws, wsb,
+              stream_of(x)), "smooth_fwd")
+    return out, mx
+
+
+def _bwd_sharded(g, out, mx, sigma, radius, axes, group):
+    """(din, the two sums of the normalisation's adjoint over the whole batch)"""
+    import torch.distributed as dist
+    B, H, T, W, C = out.shape
+    din = _lib.empty_like(out)
+    stats = _lib.empty((2,), torch.float32, out.device)
+    ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), out)
+    _, _, bwd, bits = _entry(axes)
+    check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_STATS_ONLY, None, ws,
+              wsb, stream_of(out)), "smooth_bwd")
+    _all_reduce(stats, dist.ReduceOp.SUM, group)
+    check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_EXTERNAL_STATS,
+              ptr(din), ws, wsb, stream_of(out)), "smooth_bwd")
+    return din, stats
+
+
+def _dsigma(x, g, out, mx, stats, sigma, radius, axes, like):
+    """d loss / d sigma by kccot_smooth_dsigma_f32, in the shape, dtype and device of the sigma tensor `like`."""
+    B, H, T, W, C = out.shape
+    res = _lib.empty((1,), torch.float32, out.device)
+    ws, wsb = workspace(lib.kccot_smooth_dsigma_workspace_bytes(B, H, T, W, C), out)
+    check(lib.kccot_smooth_dsigma_f32(ptr(x), ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius,
+                                      _sigma_bits(axes), ptr(res), ws, wsb, stream_of(out)), "smooth_dsigma")
+    return res.reshape(like.shape).to(device=like.device, dtype=like.dtype)
+
+
 class _Smooth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sigma, radius, axes):
-        B, H, T, W, C = x.shape
-        out = _lib.empty_like(x)
-        mx = _lib.empty((1,), torch.float32, x.device)
-        ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), x)
-        fwd, _, _, bits = _entry(axes)
-        check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits, ptr(out), ptr(mx), ws, wsb, stream_of(x)), "smooth_fwd")
+        out, mx = _fwd(x, sigma, radius, axes)
         ctx.save_for_backward(out, mx)
         ctx.cfg = (sigma, radius, axes)
         return out
@@ -39,14 +103,7 @@ class _Smooth(torch.autograd.Function):
     def backward(ctx, g):
         out, mx = ctx.saved_tensors
         sigma, radius, axes = ctx.cfg
-        B, H, T, W, C = out.shape
-        g = g.contiguous()
-        din = _lib.empty_like(out)
-        ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), out)
-        _, bwd, _, bits = _entry(axes)
-        check(bwd(ptr(g), ptr(out), ptr(mx), B, H, T, W, C, sigma, radius, bits, ptr(din), ws, wsb, stream_of(out)),
-              "smooth_bwd")
-        return din, None, None, None
+        return _bwd(g.contiguous(), out, mx, sigma, radius, axes), None, None, None
 
 
 class _SmoothSharded(torch.autograd.Function):
@@ -58,38 +115,69 @@ class _SmoothSharded(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, sigma, radius, axes, group):
-        import torch.distributed as dist
-        B, H, T, W, C = x.shape
-        out = _lib.empty_like(x)
-        mx = _lib.empty((1,), torch.float32, x.device)
-        ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), x)
-        fwd, _, _, bits = _entry(axes)
-        check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_NO_DIVIDE, ptr(out), ptr(mx), ws, wsb, stream_of(x)),
-              "smooth_fwd")
-        _all_reduce(mx, dist.ReduceOp.MAX, group)
-        check(fwd(ptr(x), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_EXTERNAL_MAX, ptr(out), ptr(mx), ws, wsb,
-                  stream_of(x)), "smooth_fwd")
+        out, mx = _fwd_sharded(x, sigma, radius, axes, group)
         ctx.save_for_backward(out, mx)
         ctx.cfg = (sigma, radius, axes, group)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        import torch.distributed as dist
         out, mx = ctx.saved_tensors
         sigma, radius, axes, group = ctx.cfg
-        B, H, T, W, C = out.shape
+        return _bwd_sharded(g.contiguous(), out, mx, sigma, radius, axes, group)[0], None, None, None, None
+
+
+class _SmoothSigma(torch.autograd.Function):
+    """_Smooth with a LEARNABLE bandwidth: ``sigma`` is a one-element tensor that requires a gradient (any device, any float
+    dtype).  NOT reference behaviour (the reference anneals sigma by hand).  The forward reads the value of sigma on the
+    host (``float(sigma.detach())``: a synchronisation when sigma lives on the device), so this path can NOT be captured
+    into a hipGraph; out is bit-identical to the float-sigma call.  Backward: din by the same entry as _Smooth (the same
+    bits), d loss / d sigma by kccot_smooth_dsigma_f32 (include/kccot_smooth_sigma.h), returned in sigma's shape, dtype and
+    device.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, sigma_t, radius, axes):
+        sigma = float(sigma_t.detach())
+        out, mx = _fwd(x, sigma, radius, axes)
+        ctx.save_for_backward(x, out, mx, sigma_t)
+        ctx.cfg = (sigma, radius, axes)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, out, mx, sigma_t = ctx.saved_tensors
+        sigma, radius, axes = ctx.cfg
         g = g.contiguous()
-        din = _lib.empty_like(out)
-        stats = _lib.empty((2,), torch.float32, out.device)
-        ws, wsb = workspace(lib.kccot_smooth_workspace_bytes(B, H, T, W, C), out)
-        _, _, bwd, bits = _entry(axes)
-        check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_STATS_ONLY, None, ws,
-                  wsb, stream_of(out)), "smooth_bwd")
-        _all_reduce(stats, dist.ReduceOp.SUM, group)
-        check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, sigma, radius, bits | _lib.SMOOTH_EXTERNAL_STATS,
-                  ptr(din), ws, wsb, stream_of(out)), "smooth_bwd")
-        return din, None, None, None, None
+        din = _bwd(g, out, mx, sigma, radius, axes) if ctx.needs_input_grad[0] else None
+        ds = _dsigma(x, g, out, mx, None, sigma, radius, axes, sigma_t) if ctx.needs_input_grad[1] else None
+        return din, ds, None, None
+
+
+class _SmoothShardedSigma(torch.autograd.Function):
+    """_SmoothSharded with a learnable bandwidth (see _SmoothSigma; sigma is replicated on every rank).  Backward: the
+    stats-only pass, the all-reduce and din with the global sums as in _SmoothSharded, then kccot_smooth_dsigma_f32 with the
+    GLOBAL maximum and sums over this rank's shard.  The value returned for sigma is therefore this rank's PARTIAL of
+    d loss / d sigma: the sum over the ranks is the gradient of the whole batch.  That is the convention KCCOTTrainer._apply
+    uses for replicated parameters (local partials, summed by the gradient all-reduce); nothing is all-reduced here."""
+
+    @staticmethod
+    def forward(ctx, x, sigma_t, radius, axes, group):
+        sigma = float(sigma_t.detach())
+        out, mx = _fwd_sharded(x, sigma, radius, axes, group)
+        ctx.save_for_backward(x, out, mx, sigma_t)
+        ctx.cfg = (sigma, radius, axes, group)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, out, mx, sigma_t = ctx.saved_tensors
+        sigma, radius, axes, group = ctx.cfg
+        g = g.contiguous()
+        din, stats = _bwd_sharded(g, out, mx, sigma, radius, axes, group)
+        ds = _dsigma(x, g, out, mx, stats, sigma, radius, axes, sigma_t) if ctx.needs_input_grad[1] else None
+        return din, ds, None, None, None
 
 
 def _all_reduce(t, op, group):
@@ -121,6 +209,15 @@ class KernelSmoothing:
         self.group, self.sharded = group, bool(sharded or group is not None)
 
     def _apply(self, inputs, sigma, radius, axes):
+        """A float sigma, or a tensor that does not require a gradient, is a constant of the call.  A one-element tensor
+        that requires a gradient is learnable: _SmoothSigma / _SmoothShardedSigma return its gradient as well."""
+        if isinstance(sigma, torch.Tensor) and sigma.requires_grad:
+            if sigma.numel() != 1 or not sigma.is_floating_point():
+                raise ValueError("a learnable sigma is a 0-dim or one-element float tensor, got %s of shape %s"
+                                 % (sigma.dtype, tuple(sigma.shape)))
+            if self.sharded:
+                return _SmoothShardedSigma.apply(_video(inputs), sigma, radius, axes, self.group)
+            return _SmoothSigma.apply(_video(inputs), sigma, radius, axes)
         if self.sharded:
             return _SmoothSharded.apply(_video(inputs), float(sigma), radius, axes, self.group)
         return _Smooth.apply(_video(inputs), float(sigma), radius, axes)
