@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
 ``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h``,
-``include/kccot_smooth_causal3.h`` and ``include/kccot_smooth_sigma.h``).
+``include/kccot_smooth_causal3.h``, ``include/kccot_smooth_sigma.h`` and ``include/kccot_smooth_aniso.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -184,6 +184,18 @@ SMOOTH_SIGMA_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_smooth_aniso.h one to one (the anisotropic 3-D smoothing -- one bandwidth
+# and radius along T, another along H and W: an extension outside the versioned surface of kccot.h).  flags: SMOOTH_CAUSAL_T
+# and the protocol bits only.
+SMOOTH_ANISO_SIGNATURES = {
+    "kccot_smooth_aniso_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kccot_smooth_aniso_fwd_f32": (_i, [_fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_aniso_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_aniso_bwd_sharded_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_aniso_dsigma_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -196,7 +208,8 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) +
                               list(CONDITIONAL_SIGNATURES.items()) + list(WEIGHT_GRAD_SIGNATURES.items()) +
-                              list(SMOOTH3C_SIGNATURES.items()) + list(SMOOTH_SIGMA_SIGNATURES.items())):
+                              list(SMOOTH3C_SIGNATURES.items()) + list(SMOOTH_SIGMA_SIGNATURES.items()) +
+                              list(SMOOTH_ANISO_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -33,42 +33,6 @@ constexpr int DS_NT = 256;                  // threads of a dsigma_tile workgrou
 constexpr size_t DS_LDS_MAX = 60 * 1024;    // dynamic LDS a tiling may take (the static part is below 1 KB)
 constexpr unsigned DS_AXES = KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W;
 
-// symmetric axis: w = the forward's taps (make_taps), dw[d + r] = w_d (d^2 - mu2) / sigma^3
-struct SymD { float w[2 * SM_MAXR + 1]; float dw[2 * SM_MAXR + 1]; };
-// causal T: row min(t, r) holds v_{t,d} = w_d / Z_t and its derivative for d = 0..r; zero behind d = min(t, r)
-struct CausD { float v[SM_MAXR + 1][SM_MAXR + 1]; float dv[SM_MAXR + 1][SM_MAXR + 1]; };
-
-// fp64 from the fp32 value of sigma, rounded to fp32 at the end
-SymD make_sym_d(float sigma, int r) {
-    SymD s{};
-    const Taps tp = make_taps(sigma, r);
-    const double sg = (double)sigma;
-    double e[2 * SM_MAXR + 1], z = 0.0, mu2 = 0.0;
-    for (int d = -r; d <= r; ++d) { e[d + r] = exp(-(double)(d * d) / (2.0 * sg * sg)); z += e[d + r]; }
-    for (int d = -r; d <= r; ++d) mu2 += e[d + r] / z * (double)(d * d);
-    for (int d = -r; d <= r; ++d) {
-        s.w[d + r] = tp.w[d + r];
-        s.dw[d + r] = (float)(e[d + r] / z * ((double)(d * d) - mu2) / (sg * sg * sg));
-    }
-    return s;
-}
-
-CausD make_caus_d(float sigma, int r) {
-    CausD c{};
-    const CausalTaps ct = make_causal_taps(sigma, r);
-    const double sg = (double)sigma;
-    for (int t = 0; t <= r; ++t) {
-        double e[SM_MAXR + 1], z = 0.0, mu2 = 0.0;
-        for (int d = 0; d <= t; ++d) { e[d] = exp(-(double)(d * d) / (2.0 * sg * sg)); z += e[d]; }
-        for (int d = 0; d <= t; ++d) mu2 += e[d] / z * (double)(d * d);
-        for (int d = 0; d <= t; ++d) {
-            c.v[t][d] = ct.w[d] * ct.iz[t];
-            c.dv[t][d] = (float)(e[d] / z * ((double)(d * d) - mu2) / (sg * sg * sg));
-        }
-    }
-    return c;
-}
-
 struct DsArgs {
     const float* in;
     const float* gout;

@@ -180,6 +180,142 @@ class _SmoothShardedSigma(torch.autograd.Function):
         return din, ds, None, None, None
 
 
+# ---- the anisotropic 3-D smoothing (include/kccot_smooth_aniso.h): cfg = (sigma_t, radius_t, sigma_s, radius_s, flags)
+
+def _aniso_ws(t):
+    B, H, T, W, C = t.shape
+    return workspace(lib.kccot_smooth_aniso_workspace_bytes(B, H, T, W, C), t)
+
+
+def _aniso_fwd(x, cfg, group=None, sharded=False):
+    st, rt, ss, rs, flags = cfg
+    B, H, T, W, C = x.shape
+    out = _lib.empty_like(x)
+    mx = _lib.empty((1,), torch.float32, x.device)
+    ws, wsb = _aniso_ws(x)
+
+    def call(extra):
+        check(lib.kccot_smooth_aniso_fwd_f32(ptr(x), B, H, T, W, C, st, rt, ss, rs, flags | extra, ptr(out), ptr(mx), ws, wsb,
+                                             stream_of(x)), "smooth_aniso_fwd")
+    if not sharded:
+        call(0)
+    else:
+        import torch.distributed as dist
+        call(_lib.SMOOTH_NO_DIVIDE)
+        _all_reduce(mx, dist.ReduceOp.MAX, group)
+        call(_lib.SMOOTH_EXTERNAL_MAX)
+    return out, mx
+
+
+def _aniso_bwd(g, out, mx, cfg):
+    st, rt, ss, rs, flags = cfg
+    B, H, T, W, C = out.shape
+    din = _lib.empty_like(out)
+    ws, wsb = _aniso_ws(out)
+    check(lib.kccot_smooth_aniso_bwd_f32(ptr(g), ptr(out), ptr(mx), B, H, T, W, C, st, rt, ss, rs, flags, ptr(din), ws, wsb,
+                                         stream_of(out)), "smooth_aniso_bwd")
+    return din
+
+
+def _aniso_bwd_sharded(g, out, mx, cfg, group, want_din=True):
+    """(din, the two sums of the normalisation's adjoint over the whole batch)"""
+    import torch.distributed as dist
+    st, rt, ss, rs, flags = cfg
+    B, H, T, W, C = out.shape
+    stats = _lib.empty((2,), torch.float32, out.device)
+    ws, wsb = _aniso_ws(out)
+    bwd = lib.kccot_smooth_aniso_bwd_sharded_f32
+    check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, st, rt, ss, rs, flags | _lib.SMOOTH_STATS_ONLY, None, ws,
+              wsb, stream_of(out)), "smooth_aniso_bwd")
+    _all_reduce(stats, dist.ReduceOp.SUM, group)
+    din = None
+    if want_din:
+        din = _lib.empty_like(out)
+        check(bwd(ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, st, rt, ss, rs, flags | _lib.SMOOTH_EXTERNAL_STATS,
+                  ptr(din), ws, wsb, stream_of(out)), "smooth_aniso_bwd")
+    return din, stats
+
+
+def _aniso_dsigma(x, g, out, mx, stats, cfg):
+    """{d loss / d sigma_t, d loss / d sigma_s} by kccot_smooth_aniso_dsigma_f32: two device floats"""
+    st, rt, ss, rs, flags = cfg
+    B, H, T, W, C = out.shape
+    res = _lib.empty((2,), torch.float32, out.device)
+    ws, wsb = _aniso_ws(out)
+    check(lib.kccot_smooth_aniso_dsigma_f32(ptr(x), ptr(g), ptr(out), ptr(mx), ptr(stats), B, H, T, W, C, st, rt, ss, rs, flags,
+                                            ptr(res), ws, wsb, stream_of(out)), "smooth_aniso_dsigma")
+    return res
+
+
+def _sigma_value(sigma):
+    return float(sigma.detach()) if isinstance(sigma, torch.Tensor) else float(sigma)
+
+
+def _aniso_forward(ctx, x, sigma_t, sigma_s, radius_t, radius_s, flags, group, sharded):
+    cfg = (_sigma_value(sigma_t), radius_t, _sigma_value(sigma_s), radius_s, flags)
+    out, mx = _aniso_fwd(x, cfg, group, sharded)
+    learn = [isinstance(s, torch.Tensor) and s.requires_grad for s in (sigma_t, sigma_s)]
+    ctx.save_for_backward(x if any(learn) else None, out, mx)
+    ctx.cfg, ctx.group, ctx.sharded = cfg, group, sharded
+    ctx.like = [s if l else None for s, l in zip((sigma_t, sigma_s), learn)]
+    return out
+
+
+def _aniso_backward(ctx, g):
+    """(din, d sigma_t, d sigma_s): only what was asked for is computed"""
+    x, out, mx = ctx.saved_tensors
+    g = g.contiguous()
+    want_din = ctx.needs_input_grad[0]
+    want_sig = [ctx.needs_input_grad[1 + i] and ctx.like[i] is not None for i in (0, 1)]
+    din, stats = None, None
+    if ctx.sharded:
+        din, stats = _aniso_bwd_sharded(g, out, mx, ctx.cfg, ctx.group, want_din)
+    elif want_din:
+        din = _aniso_bwd(g, out, mx, ctx.cfg)
+    ds = [None, None]
+    if any(want_sig):
+        res = _aniso_dsigma(x, g, out, mx, stats, ctx.cfg)
+        for i in (0, 1):
+            if want_sig[i]:
+                like = ctx.like[i]
+                ds[i] = res[i].reshape(like.shape).to(device=like.device, dtype=like.dtype)
+    return din, ds[0], ds[1]
+
+
+class _SmoothAniso(torch.autograd.Function):
+    """The anisotropic 3-D smoothing (include/kccot_smooth_aniso.h).  NOT reference behaviour.  ``sigma_t`` / ``sigma_s``: a
+    float (a constant of the call) or a one-element tensor that requires a gradient (learnable); the value of a tensor is
+    read on the host (a synchronisation when it lives on the device), so the learnable path can NOT be captured into a
+    hipGraph.  out and din come from the same entry points, and are the same bits, whether or not a sigma is learnable.
+    d loss / d sigma by kccot_smooth_aniso_dsigma_f32, in the sigma's shape, dtype and device; only the requested
+    gradients are computed.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, sigma_t, sigma_s, radius_t, radius_s, flags):
+        return _aniso_forward(ctx, x, sigma_t, sigma_s, radius_t, radius_s, flags, None, False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _aniso_backward(ctx, g) + (None, None, None)
+
+
+class _SmoothAnisoSharded(torch.autograd.Function):
+    """_SmoothAniso for a batch that is sharded over the ranks of ``group`` (see _SmoothSharded): the forward is NO_DIVIDE ->
+    all-reduce(MAX) -> EXTERNAL_MAX, the backward STATS_ONLY -> all-reduce(SUM) -> EXTERNAL_STATS.  The values returned for
+    learnable sigmas are this rank's PARTIALS of d loss / d sigma (the GLOBAL maximum and sums over this rank's shard), the
+    convention of _SmoothShardedSigma: nothing is all-reduced for them here."""
+
+    @staticmethod
+    def forward(ctx, x, sigma_t, sigma_s, radius_t, radius_s, flags, group):
+        return _aniso_forward(ctx, x, sigma_t, sigma_s, radius_t, radius_s, flags, group, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return _aniso_backward(ctx, g) + (None, None, None, None)
+
+
 def _all_reduce(t, op, group):
     import torch.distributed as dist
     if dist.get_backend(group) == "gloo" and t.is_cuda:       # CPU rehearsal backend: staged through the host
@@ -266,6 +402,26 @@ class KernelSmoothing:
         symmetric Gaussian with REFLECT borders, then / global max.  All three axes use the SPATIAL radius, as
         gaussian_convolution3D does."""
         return self._apply(inputs, sigma, self.spatial_radius, CAUSAL3)
+
+    def anisotropic_gaussian_convolution3D(self, inputs, sigma_t, sigma_s, causal=False):
+        """NOT reference behaviour.  The 3-D smoothing with SEPARATE bandwidths and radii for time and space
+        (include/kccot_smooth_aniso.h): along T the Gaussian of ``sigma_t`` with the TEMPORAL radius -- unlike
+        gaussian_convolution3D and causal_gaussian_convolution3D, which use the spatial radius on T as the reference does --
+        and along H and W the Gaussian of ``sigma_s`` with the spatial radius, REFLECT borders, then / global max.
+        ``causal=True``: along T the past-only stencil of causal_temporal_convolution instead (truncated, renormalised
+        window, no padding, s[0] = x[0]).  A radius of 0 makes that axis group the identity.
+        Each sigma is a float, a tensor that does not require a gradient (both constants of the call), or a one-element
+        float tensor that requires a gradient (learnable: its gradient is returned as well); either, both or neither."""
+        for name, s in (("sigma_t", sigma_t), ("sigma_s", sigma_s)):
+            if isinstance(s, torch.Tensor) and s.requires_grad and (s.numel() != 1 or not s.is_floating_point()):
+                raise ValueError("a learnable %s is a 0-dim or one-element float tensor, got %s of shape %s"
+                                 % (name, s.dtype, tuple(s.shape)))
+        sigma_t, sigma_s = (s if isinstance(s, torch.Tensor) and s.requires_grad else float(s) for s in (sigma_t, sigma_s))
+        flags = _lib.SMOOTH_CAUSAL_T if causal else 0
+        if self.sharded:
+            return _SmoothAnisoSharded.apply(_video(inputs), sigma_t, sigma_s, self.temporal_radius, self.spatial_radius, flags,
+                                             self.group)
+        return _SmoothAniso.apply(_video(inputs), sigma_t, sigma_s, self.temporal_radius, self.spatial_radius, flags)
 
     def annealing_sigma(self, init_sigma, step, decay_steps=500, decay_rate=0.975):
         """data_utils.py:584-586."""

@@ -93,7 +93,7 @@ class KCCOTTrainer:
                  g_state_size=8, d_state_size=8, g_filter_size=8, d_filter_size=8, z_channels=128, bn=True,
                  lr=5e-4, warmup=10000, sinkhorn_eps=0.8, sinkhorn_l=100, scaling_coef=15.0, reg_penalty=1.0,
                  kernel="none", device="cuda", seed=1, group=None, mixed_sinkhorn=False,
-                 bi_causal=False, conditional_bandwidth=None):
+                 bi_causal=False, conditional_bandwidth=None, temporal_kernel_size=6, spatial_kernel_size=6):
         # defaults = kernel_train.py:363-409
         # mixed_sinkhorn=True: the loss is COT-GAN's mixed Sinkhorn divergence over two minibatches
         # (gan_utils.compute_mixed_sinkhorn_loss) -- what the reference's --mixed_sinkhorn flag (:393) names but never runs
@@ -138,7 +138,9 @@ class KCCOTTrainer:
         self.kernel_choice = kernel
         self.convolution_mode = gan.convolution_mode()      # 'miopen' or 'native:...' (the slow fallback; see gan.py)
         # :216; data-parallel: the division is by the maximum of the GLOBAL batch, as in the single-process run
-        self.gaussian_kernel = KernelSmoothing(temporal_kernel_size=6, spatial_kernel_size=6, group=group, sharded=data_parallel)
+        # (the two sizes matter apart only to kernel="3d_aniso" / "3d_aniso_causal": every other 3-D form uses the spatial one on T)
+        self.gaussian_kernel = KernelSmoothing(temporal_kernel_size=temporal_kernel_size, spatial_kernel_size=spatial_kernel_size,
+                                               group=group, sharded=data_parallel)
         mk = dict(z_width=4, z_height=4, bn=bn, nchannel=channels)
         self.context_encoder = gan.VideoEncoderConvLSTM(batch_size, int_time_steps, self.pred_time_steps, g_state_size,
                                                         x_width, x_height, filter_size=g_filter_size, **mk).to(self.device)
@@ -214,6 +216,11 @@ class KCCOTTrainer:
             return self.gaussian_kernel.gaussian_convolution3D(v, sigma)
         if self.kernel_choice == "3d_causal":                                    # not in the reference: causal along T, symmetric in space
             return self.gaussian_kernel.causal_gaussian_convolution3D(v, sigma)
+        if self.kernel_choice in ("3d_aniso", "3d_aniso_causal"):                # not in the reference: sigma = (sigma_t, sigma_s)
+            if not isinstance(sigma, (tuple, list)) or len(sigma) != 2:
+                raise ValueError("kernel=%r takes sigma as a pair (sigma_t, sigma_s), got %r" % (self.kernel_choice, sigma))
+            return self.gaussian_kernel.anisotropic_gaussian_convolution3D(v, sigma[0], sigma[1],
+                                                                           causal=self.kernel_choice == "3d_aniso_causal")
         return v
 
     def _forward_mixed(self, real_in, real_pred, real_in_p, real_pred_p, sigma, generator_grad=True):
@@ -366,7 +373,10 @@ class KCCOTTrainer:
                 pending = x
                 continue
             it_counts += 1
-            sig = (self.gaussian_kernel.annealing_sigma(init_sigma, it_counts) if decaying_sigma else init_sigma)  # :308-311
+            if decaying_sigma and isinstance(init_sigma, (tuple, list)):         # kernel="3d_aniso*": each component anneals
+                sig = tuple(self.gaussian_kernel.annealing_sigma(s0, it_counts) for s0 in init_sigma)
+            else:
+                sig = (self.gaussian_kernel.annealing_sigma(init_sigma, it_counts) if decaying_sigma else init_sigma)  # :308-311
             if self.mixed_sinkhorn:
                 real_data, real_data_p = (v.to(self.device, torch.float32) for v in (pending, x))
                 pending = None
