@@ -1,6 +1,7 @@
 """ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
 ``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h``,
-``include/kccot_smooth_causal3.h``, ``include/kccot_smooth_sigma.h`` and ``include/kccot_smooth_aniso.h``).
+``include/kccot_smooth_causal3.h``, ``include/kccot_smooth_sigma.h``, ``include/kccot_smooth_aniso.h`` and
+``include/kccot_metrics.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -196,6 +197,15 @@ SMOOTH_ANISO_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_metrics.h one to one (per-frame SSIM with its adjoint w.r.t. the generated
+# video, and the mean squared error behind PSNR: an extension outside the versioned surface of kccot.h)
+METRICS_SIGNATURES = {
+    "kccot_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "kccot_ssim_fwd_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_ssim_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _fp, _fp, _sz, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -209,7 +219,7 @@ def _load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) +
                               list(CONDITIONAL_SIGNATURES.items()) + list(WEIGHT_GRAD_SIGNATURES.items()) +
                               list(SMOOTH3C_SIGNATURES.items()) + list(SMOOTH_SIGMA_SIGNATURES.items()) +
-                              list(SMOOTH_ANISO_SIGNATURES.items())):
+                              list(SMOOTH_ANISO_SIGNATURES.items()) + list(METRICS_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -347,6 +347,20 @@ class KCCOTTrainer:
             return kd.sharded_rbf_mmd2(real, fake, group=self.group)
         return _mmd.rbf_mmd2(real, fake)
 
+    @torch.no_grad()
+    def evaluate(self, test_data, data_range=1.0, win_size=11, ssim_sigma=1.5):
+        """Sample quality, not part of the reference's loop (it publishes no such figure): ``sample(test_data)``, then
+        ``metrics.frame_metrics`` of the ``pred_time_steps`` predicted frames against the same frames of ``test_data``
+        [B,H,T,W,C].  Returns ``{"ssim": [pred_time_steps], "psnr": [pred_time_steps]}``, the batch means per predicted step
+        (a step with a frame identical to the truth has psnr = +inf).  Data-parallel runs: THIS rank's batch only, nothing is
+        all-reduced.  No gradient, no optimiser step; it draws z from the torch RNG as ``sample`` does."""
+        from . import metrics
+        test_data = test_data.to(self.device, torch.float32)
+        k = self.int_time_steps
+        fake = self.sample(test_data)[:, :, k:].contiguous()
+        s, p = metrics.frame_metrics(test_data[:, :, k:].contiguous(), fake, data_range, win_size, ssim_sigma)
+        return {"ssim": s.mean(0), "psnr": p.mean(0)}
+
     @staticmethod
     def sample_image(videos, max_rows=10):
         """kernel_train.py:349-351: [B,H,T,W,C] -> one image [1, min(10,B)*H, W*T, C], a row of frames per sample."""
