@@ -38,11 +38,13 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * LN2; }
 
 // Diagnostic build only (-DKCCOT_DIAG, libkccot_diag.so, tools/diag_sinkhorn.py): in-kernel
-// s_memtime stamps of one half-step.  The product library contains no stamp.
+// s_memtime stamps of one half-step.  The product library contains no stamp.  The buffer is [problem, 16 waves,
+// KCCOT_DIAG_SLOTS]; the slots of the fused kernels are listed in tools/diag_sinkhorn.py.
 #ifdef KCCOT_DIAG
 #ifndef KCCOT_DIAG_IT
 #define KCCOT_DIAG_IT 50
 #endif
+#define KCCOT_DIAG_SLOTS 32
 #define KCCOT_STAMP(SLOT) KCCOT_STAMP_IF(it == KCCOT_DIAG_IT, SLOT)
 #define KCCOT_STAMP_IF(COND, SLOT)                                                                \
     do {                                                                                          \
@@ -51,12 +53,19 @@ __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_log
             __builtin_amdgcn_sched_barrier(0);                                                    \
             asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt_)::"memory");          \
             __builtin_amdgcn_sched_barrier(0);                                                    \
-            if ((threadIdx.x & 63) == 0) a.diag[(blockIdx.x * 16 + (threadIdx.x >> 6)) * 16 + (SLOT)] = tt_; \
+            if ((threadIdx.x & 63) == 0) a.diag[(blockIdx.x * 16 + (threadIdx.x >> 6)) * KCCOT_DIAG_SLOTS + (SLOT)] = tt_; \
         }                                                                                         \
+    } while (0)
+// the kernel's last stamp: taken once the wave's own stores and loads have completed
+#define KCCOT_STAMP_DRAINED(SLOT)                                                                 \
+    do {                                                                                          \
+        if (a.diag) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                              \
+        KCCOT_STAMP_IF(true, SLOT);                                                               \
     } while (0)
 #else
 #define KCCOT_STAMP(SLOT) do {} while (0)
 #define KCCOT_STAMP_IF(COND, SLOT) do {} while (0)
+#define KCCOT_STAMP_DRAINED(SLOT) do {} while (0)
 #endif
 
 struct SinkArgs {
@@ -266,22 +275,54 @@ __device__ __forceinline__ void fill_history_rows(float* hu, float* hv, int NS, 
 }
 
 // gan_utils.py:162-164 in the fused kernels: pi = exp((-C + u + v^T)/eps); cost = sum(pi * C) over a row-layout lane's
-// entries (C re-read: L2-resident).  sinkhorn_fwd_body keeps its own loop, which also writes and poisons the plan.
+// entries.  craw[] holds the lane's elements of C as the prologue loaded them (load_costs_raw): no global access stands
+// between the two loops.  sinkhorn_fwd_body keeps its own loop, which also writes and poisons the plan.
 template <int EPT>
-__device__ __forceinline__ float cost_partial(const float (&crow)[EPT], float ui, const float* v, const float* C, int n,
-                                              int line, int q, bool active) {
+__device__ __forceinline__ float cost_partial(const float (&crow)[EPT], const float (&craw)[EPT], float ui, const float* v,
+                                              int n, int q, bool active) {
+    // no branch per entry: the duals arrive in one vector read (pad columns of a history row are zero) and an entry past the
+    // edge is skipped by a select, which leaves the sum of the others, in their order, as it was
+    float ov[EPT];
+    load_other<EPT>(ov, v, q);
     float part = 0.f;
-    if (active) {
 #pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = q * EPT + m;
-            if (idx < n) {
-                const float pi = __builtin_amdgcn_exp2f((ui - crow[m]) + v[idx]);
-                part += pi * C[(int64_t)line * n + idx];
-            }
-        }
+    for (int m = 0; m < EPT; ++m) {
+        const float pi = __builtin_amdgcn_exp2f((ui - crow[m]) + ov[m]);
+        const float sum = part + pi * craw[m];
+        part = (active && q * EPT + m < n) ? sum : part;
     }
     return part;
+}
+// one orientation of load_costs that also keeps the elements themselves (0 past the edge) for cost_partial
+template <int EPT, bool ROW>
+__device__ __forceinline__ void load_costs_raw(const float* C, int n, int line, int q, float k2, float (&c2)[EPT],
+                                               float (&craw)[EPT]) {
+#pragma unroll
+    for (int m = 0; m < EPT; ++m) {
+        const int idx = q * EPT + m;
+        const bool ok = line < n && idx < n;
+        craw[m] = ok ? C[ROW ? (int64_t)line * n + idx : (int64_t)idx * n + line] : 0.f;
+        c2[m] = ok ? craw[m] * k2 : INFINITY;
+    }
+}
+template <int EPT, bool ROW>
+__device__ __forceinline__ void load_costs_raw(const float* C, int n, int line, int q, float k2, float (&c2)[EPT]) {
+    float craw[EPT];
+    load_costs_raw<EPT, ROW>(C, n, line, q, k2, c2, craw);
+}
+
+// The cost of a fused problem, by the one thread that hands it off: the waves' partial sums (wave_sum of cost_partial, parked
+// in red[] in front of the barrier of the dC transpose) added in wave order to + 0.0f, as block_sum adds them.
+// All 16 words are read at once (a loop over nw is one LDS round trip per wave, on the thread the kernel's end waits for);
+// the words of waves that do not exist are skipped by a select.
+__device__ __forceinline__ float cost_of_waves(const float* red, int nw) {
+    float v[16];
+#pragma unroll
+    for (int w = 0; w < 16; ++w) v[w] = red[w];
+    float r = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) r = w < nw ? r + v[w] : r;
+    return r;
 }
 
 // Thread 0 of problem p publishes its cost and iteration counts; with `combine`, the last of the NPROB workgroups to arrive
@@ -346,8 +387,32 @@ __device__ __forceinline__ void final_cost_adjoint(float c2, float self, float o
     ss += pv * cc;
 }
 
-// dC = row-layout part + (column-layout part)^T: the row lanes store, the column lanes add behind the caller's
-// __threadfence_block(); __syncthreads();
+// dC = row-layout part + (column-layout part)^T in the fused kernels.  The transpose goes through LDS: the column lanes park
+// their entries in an n x n tile at pitch n + 1 (park_dc_cols), the caller's lds_barrier() follows, the row lanes add the
+// transposed entries to their own (take_dc_cols; x + y has the same bits whichever side adds) and store every row once
+// (store_dc_rows).  The tile lies on the dual history, which is dead by then: every wave is behind the sweep's last barrier
+// (with no iteration at all, behind the barrier that follows the last read of row 0); the host sizes the dynamic LDS for the
+// larger of the two (fused_lds_bytes).  Pad lines and pad columns are neither written nor read.
+template <int EPT>
+__device__ __forceinline__ void park_dc_cols(float* tile, const float (&dcol)[EPT], int n, int line, int q, bool active) {
+    if (active) {
+#pragma unroll
+        for (int m = 0; m < EPT; ++m) {
+            const int idx = q * EPT + m;
+            if (idx < n) tile[idx * (n + 1) + line] = dcol[m];
+        }
+    }
+}
+template <int EPT>
+__device__ __forceinline__ void take_dc_cols(const float* tile, float (&drow)[EPT], int n, int line, int q, bool active) {
+    // every read is issued before the first is waited for: an entry past the edge reads word 0 of the tile instead (its sum is
+    // never stored)
+#pragma unroll
+    for (int m = 0; m < EPT; ++m) {
+        const int idx = q * EPT + m;
+        drow[m] += tile[(active && idx < n) ? line * (n + 1) + idx : 0];
+    }
+}
 template <int EPT>
 __device__ __forceinline__ void store_dc_rows(float* dC, const float (&drow)[EPT], int n, int line, int q, bool active) {
     if (active) {
@@ -355,16 +420,6 @@ __device__ __forceinline__ void store_dc_rows(float* dC, const float (&drow)[EPT
         for (int m = 0; m < EPT; ++m) {
             const int idx = q * EPT + m;
             if (idx < n) dC[(int64_t)line * n + idx] = drow[m];
-        }
-    }
-}
-template <int EPT>
-__device__ __forceinline__ void add_dc_cols(float* dC, const float (&dcol)[EPT], int n, int line, int q, bool active) {
-    if (active) {
-#pragma unroll
-        for (int m = 0; m < EPT; ++m) {
-            const int idx = q * EPT + m;
-            if (idx < n) dC[(int64_t)idx * n + line] += dcol[m];
         }
     }
 }
@@ -838,7 +893,7 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     extern __shared__ __attribute__((aligned(16))) float hist[];
     __shared__ __attribute__((aligned(16))) float gu[SK_MAXN + 16 * 16];
     __shared__ __attribute__((aligned(16))) float gv[SK_MAXN + 16 * 16];
-    __shared__ float red[16];
+    __shared__ __attribute__((aligned(16))) float red[16];
     __shared__ int mis[4];
     const int p = blockIdx.x, n = a.n, L = a.L;
     const int t = threadIdx.x, line = t / LPR, q = t % LPR;
@@ -848,8 +903,14 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     float* hu = hist;                                          // row k: U_k (k = 0 .. L), row 0 = 0
     float* hv = hist + (size_t)(L + 1) * NS;
 
-    float crow[EPT], ccol[EPT];
-    load_costs<EPT, LPR>(C, n, line, q, k2, crow, ccol);
+    KCCOT_STAMP_IF(true, 16);                                  // 16 .. 11: the prologue
+    const int nw = blockDim.x >> 6;                            // read with the kernel's other arguments, not in the tail
+    // d(sum_p w[p] cost[p]) / d cost[p] at dLoss = 1.  An indexed scalar load: taken here, with the prologue's loads, so that
+    // the sweep's first adjoints do not wait for it between the loops.
+    const float g = a.w[p];
+    float crow[EPT], ccol[EPT], craw[EPT];                     // craw: the row orientation's elements, for the final cost
+    load_costs_raw<EPT, true>(C, n, line, q, k2, crow, craw);
+    load_costs_raw<EPT, false>(C, n, line, q, k2, ccol);
     // row 0 and the pad columns [n, NS) of every row are zero (a pad dual pairs with c2 = +inf -> exp2(-inf) = 0)
     for (int i = t; i < NS; i += blockDim.x) { hu[i] = 0.f; hv[i] = 0.f; }
     if (NS > n) {
@@ -921,12 +982,15 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     KCCOT_STAMP_IF(true, 12);
     const float* Vn = hv + nits * NS;
     const float* Un = hu + nits * NS;
-    const float part = cost_partial<EPT>(crow, ui, Vn, C, n, line, q, active);
-    const float cost = block_sum(part, red);
-    if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost, nits, computed, a.w, true);
+    // The final cost is formed and handed off BEHIND the sweep, which needs neither (g = a.w[p] is a constant, nits is in a
+    // register): here each wave only sums its lanes' parts, from registers and LDS.  Between the two loops there is no global
+    // access, no wait for one, and one barrier (the one in front of the sweep, which the adjoints below need).
+    // (<16,8>, n > 64 under option "sinkhorn_fused_max_n" = 128, runs at the 128-VGPR cap of 1024 threads and spilled before;
+    // its scratch grows from 144-148 to 188-200 bytes per lane.  A form that re-read C here instead spilled as much.)
+    const float psum = wave_sum(cost_partial<EPT>(crow, craw, ui, Vn, n, q, active));
+    KCCOT_STAMP_IF(true, 17);
 
     // ---------------------------------------------------------------- reverse sweep (sinkhorn_bwd_body on LDS history)
-    const float g = a.w[p];                                   // d(sum_p w[p] cost[p]) / d cost[p] at dLoss = 1
     const int lsafe = active ? line : 0;
     float drow[EPT], dcol[EPT];
     {
@@ -945,7 +1009,8 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
         sv = seg_sum<LPR>(sv);
         if (active && q == 0) { gu[line] = g * su * LN2; gv[line] = g * sv * LN2; }
     }
-    __syncthreads();
+    KCCOT_STAMP_IF(true, 20);
+    lds_barrier();
     // The plans Q_t (pass A) and P_t (pass B) depend on the HISTORY only, not on the running gradients: the dependent
     // chain of a half-step is gv -> 8 multiply-adds -> DPP sum -> gu.  Their exp2 are therefore evaluated one pass
     // AHEAD, in the shadow of the LDS round trip that follows every barrier (ds_read of the gradients): the same
@@ -1012,10 +1077,18 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     }
     KCCOT_STAMP_IF(true, 14);
     float* dC = a.dC + (int64_t)p * n * n;
+    // dC through the LDS tile (park_dc_cols), and the waves' cost sums with it: one barrier, every row stored once, no global
+    // load.  Thread 0 hands the cost off last, behind its own row stores: its drain waits for stores the kernel's end waits
+    // for anyway, and no other wave waits for thread 0 any more.
+    park_dc_cols<EPT>(hist, dcol, n, line, q, active);
+    if ((t & 63) == 0) red[t >> 6] = psum;
+    lds_barrier();
+    KCCOT_STAMP_IF(true, 21);
+    take_dc_cols<EPT>(hist, drow, n, line, q, active);
     store_dc_rows<EPT>(dC, drow, n, line, q, active);
-    __threadfence_block();
-    __syncthreads();
-    add_dc_cols<EPT>(dC, dcol, n, line, q, active);
+    if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost_of_waves(red, nw), nits, computed, a.w, true);
+    KCCOT_STAMP_IF(true, 19);
+    KCCOT_STAMP_DRAINED(22);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1073,13 +1146,11 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     float* hs = COL ? hv : hu;
     const float* ho = COL ? hu : hv;
 
+    KCCOT_STAMP_IF(true, 16);
     float c2[EPT];                                             // C * k2 in this role's orientation (load_costs)
-#pragma unroll
-    for (int m = 0; m < EPT; ++m) {
-        const int idx = q * EPT + m;
-        const bool ok = line < n && idx < n;
-        c2[m] = ok ? C[COL ? (int64_t)idx * n + line : (int64_t)line * n + idx] * k2 : INFINITY;
-    }
+    float craw[EPT];                                           // the elements themselves: the row role's, for the final cost
+    const float g = a.w[p];                                    // loaded here, not between the loops (see sinkhorn_fused_reg)
+    load_costs_raw<EPT, !COL>(C, n, line, q, k2, c2, craw);
     // row 0, the pad columns, gu / gv and mis zeroed, by every thread of both roles (the prologue of sinkhorn_fused_reg)
     for (int i = t; i < NS; i += blockDim.x) { hu[i] = 0.f; hv[i] = 0.f; }
     if (NS > n) {
@@ -1151,15 +1222,13 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     // the final cost: the row role's lanes, zeros from the others
     const float* Vn = hv + nits * NS;
     const float* Un = hu + nits * NS;
-    float part = 0.f;
-    if constexpr (!COL) part = cost_partial<EPT>(c2, self, Vn, C, n, line, q, active);
-    const float cost = block_sum(part, red);
-    if constexpr (!COL) {
-        if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost, nits, computed, a.w, true);
-    }
+    // formed and handed off behind the sweep (see sinkhorn_fused_reg): no global access, no wait for one and one barrier
+    // between the two loops
+    float psum = 0.f;
+    if constexpr (!COL) psum = wave_sum(cost_partial<EPT>(c2, craw, self, Vn, n, q, active));
+    KCCOT_STAMP_IF(true, 17);
 
     // ---------------------------------------------------------------- reverse sweep
-    const float g = a.w[p];
     const int lsafe = active ? line : 0;
     float d[EPT];                                              // drow (row role) / dcol (column role)
     {
@@ -1172,7 +1241,8 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
         ss = seg_sum<LPR>(ss);
         if (active && q == 0) (COL ? gv : gu)[line] = g * ss * LN2;
     }
-    __syncthreads();
+    KCCOT_STAMP_IF(true, 20);
+    lds_barrier();
     float pl[EPT];                                             // Q_t (row role, plan_a) / P_t (column role, plan_b)
     auto plan = [&](int it) {
         // row:    Q_it[line][q*EPT+m] = exp2((U_it,line - lw2 - c) + V_it,col)
@@ -1224,10 +1294,21 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     if constexpr (COL) sweep_prio<KCCOT_SWEEP_PRIO == 3>(false);
     KCCOT_STAMP_IF(true, 14);
     float* dC = a.dC + (int64_t)p * n * n;
-    if constexpr (!COL) store_dc_rows<EPT>(dC, d, n, line, q, active);
-    __threadfence_block();
-    __syncthreads();
-    if constexpr (COL) add_dc_cols<EPT>(dC, d, n, line, q, active);
+    // dC through the LDS tile, the waves' cost sums with it (the column waves' + 0.0f keep block_sum's sum): one barrier.
+    // Behind it the row role adds the transposed entries and stores every row once; the column role has nothing left to do,
+    // so its first thread forms the cost and hands it off while the rows are stored.  No wave waits for that thread.
+    if constexpr (COL) park_dc_cols<EPT>(hist, d, n, line, q, active);
+    if ((t & 63) == 0) red[t >> 6] = psum;
+    lds_barrier();
+    KCCOT_STAMP_IF(true, 21);
+    if constexpr (!COL) {
+        take_dc_cols<EPT>(hist, d, n, line, q, active);
+        store_dc_rows<EPT>(dC, d, n, line, q, active);
+    } else {
+        if (tr == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost_of_waves(red, TR >> 5), nits, computed, a.w, true);
+        KCCOT_STAMP_IF(true, 19);
+    }
+    KCCOT_STAMP_DRAINED(22);
 }
 
 template <int EPT, int LPR, bool SHORTCUT, int NPROB>
@@ -1236,7 +1317,7 @@ __global__ __launch_bounds__(SK_MAXT) void sinkhorn_fused_roles(SinkFusedArgs a)
     extern __shared__ __attribute__((aligned(16))) float hist[];
     __shared__ __attribute__((aligned(16))) float gu[SK_MAXN + 16 * 16];
     __shared__ __attribute__((aligned(16))) float gv[SK_MAXN + 16 * 16];
-    __shared__ float red[16];
+    __shared__ __attribute__((aligned(16))) float red[16];
     __shared__ int mis[4];
     const int TR = blockDim.x >> 1;                            // threads per role, a multiple of 64: the role is wave-uniform
     if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >= TR)) fused_roles_body<EPT, LPR, SHORTCUT, NPROB, true>(a, hist, gu, gv, red, mis, TR);
@@ -1443,13 +1524,20 @@ extern "C" int kccot_mixed_divergence_bwd_f32(const float* gloss, float* gcost3_
 
 // ---- fused solve + reverse sweep (sinkhorn_fused_reg) -------------------------------------------------
 #ifdef KCCOT_DIAG
-// diagnostic twin only (tools/diag_sinkhorn.py): the device buffer [nprob,16 waves,16 slots] that the fused kernels stamp
+// diagnostic twin only (tools/diag_sinkhorn.py): the device buffer [nprob,16 waves,KCCOT_DIAG_SLOTS] that the fused kernels stamp
 static unsigned long long* g_fused_stamps = nullptr;
 extern "C" void kccot_diag_fused_stamps(void* buf) { g_fused_stamps = static_cast<unsigned long long*>(buf); }
 #endif
 static size_t fused_hist_bytes(int n, int L) {
     const SinkGeom g = sink_geom(n, true);
     return (size_t)2 * ((size_t)L + 1) * g.lpr * g.ept * sizeof(float);
+}
+// the dynamic LDS of a fused launch: the history, or the n x (n + 1) tile of the dC transpose that takes its place behind
+// the sweep (park_dc_cols), whichever is larger -- at L = 1 the history is 1 KB and the tile 16 KB.  The tile is at most
+// 128 x 129 floats = 64.5 KB, so it never adds to what the eligibility rule admits.
+static size_t fused_lds_bytes(int n, int L) {
+    const size_t hist = fused_hist_bytes(n, L), tile = (size_t)n * ((size_t)n + 1) * sizeof(float);
+    return hist > tile ? hist : tile;
 }
 
 extern "C" int kccot_sinkhorn_fused_eligible(int n, int L) {
@@ -1471,7 +1559,7 @@ extern "C" int kccot_sinkhorn_fused_roles_eligible(int n, int L) {
     return 2 * sink_geom(n, true).threads <= SK_MAXT;
 }
 
-// one workgroup of `threads` per problem, the history in `lds` bytes of dynamic LDS
+// one workgroup of `threads` per problem, the history and then the dC tile in `lds` bytes of dynamic LDS (fused_lds_bytes)
 // (`what` heads the error text, `name` is the kernel's name for launch_status)
 static int launch_fused_kernel(void (*kernel)(SinkFusedArgs), int threads, const char* what, const char* name, int nprob,
                                const SinkFusedArgs& a, size_t lds, hipStream_t st) {
@@ -1533,7 +1621,7 @@ int kccot::sinkhorn_fused_weighted(const float* C, int nprob, const float* w, in
 #ifdef KCCOT_DIAG
     a.diag = g_fused_stamps;
 #endif
-    const size_t lds = fused_hist_bytes(n, L);
+    const size_t lds = fused_lds_bytes(n, L);
     return sink_shortcut_enabled() ? dispatch_fused<true>(g, a, nprob, lds, st) : dispatch_fused<false>(g, a, nprob, lds, st);
 }
 
