@@ -54,6 +54,18 @@ int kccot_ssim_fwd_f32(const float* x, const float* y, int B, int H, int T, int 
 int kccot_ssim_bwd_f32(const float* g, const float* x, const float* y, int B, int H, int T, int W, int C, float sigma,
                        int radius, float data_range, float* dy, void* ws, size_t ws_bytes, kccot_stream_t stream);
 
+/* The tiling kccot_ssim_fwd_f32 (backward = 0) or kccot_ssim_bwd_f32 (backward != 0) would launch at this shape and radius: a
+ * pure host function (no device call, no GPU needed) that runs the very planner of the launch, for tests and tools that must
+ * know which tiling a case reaches.  The kernel is ssim_walk<radius, backward>.  Applies the argument checks of those entry
+ * points that concern these arguments, with the same codes (KCCOT_EINVAL also for out == NULL).  out receives
+ * KCCOT_SSIM_PLAN_INTS ints:
+ *   [0] [1] [2]  wt, ct: the columns (of the map forward, of dy backward) and the channels of a tile; hs: the rows of a segment
+ *   [3]          nt: the threads of a workgroup
+ *   [4] [5] [6]  ntw, ntc, nseg: column tiles, channel tiles, segments along H
+ *   [7]          the grid = B * T * nseg * ntw * ntc workgroups */
+#define KCCOT_SSIM_PLAN_INTS 8
+int kccot_ssim_plan(int B, int H, int T, int W, int C, int radius, int backward, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,20 @@ int kccot_smooth_aniso_dsigma_f32(const float* in, const float* gout, const floa
                                   float sigma_s, int radius_s, unsigned flags, float* dsigma_out, void* ws, size_t ws_bytes,
                                   kccot_stream_t stream);
 
+/* The tiling an entry point above would launch at this shape, radii and flags: a pure host function (no device call, no GPU
+ * needed) that runs the very planner of the launch, for tests and tools that must know which instantiation of the tile kernel a
+ * case reaches.  job: 0 the forward, 1 the adjoint (either backward entry point), 2 dsigma; any other value is KCCOT_EINVAL.
+ * Applies the argument checks of that job's entry points that concern these arguments, with the same codes (KCCOT_EINVAL also for
+ * out == NULL); of flags only KCCOT_SMOOTH_CAUSAL_T changes the tiling.  out receives KCCOT_SMOOTH_ANISO_PLAN_INTS ints:
+ *   [0]        1 when the call launches the tile kernel; 0 when it does not (job 2 with both radii 0: both results are exactly
+ *              0) -- every other entry is then 0
+ *   [1] [2] [3]  the instantiation aniso_tile<RS, NI, JOB>: RS = radius_s, NI = owned positions per thread, JOB = job
+ *   [4..7]     the tile extents tt, wt, ct along T, W, C and the segment hs along H
+ *   [8..11]    the piece counts ntt, ntw, ntc, nseg
+ *   [12]       the grid = B * nseg * ntt * ntw * ntc workgroups */
+#define KCCOT_SMOOTH_ANISO_PLAN_INTS 13
+int kccot_smooth_aniso_plan(int B, int H, int T, int W, int C, int radius_t, int radius_s, unsigned flags, int job, int* out);
+
 #ifdef __cplusplus
 }
 #endif

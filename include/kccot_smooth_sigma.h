@@ -46,6 +46,21 @@ int kccot_smooth_dsigma_f32(const float* in, const float* gout, const float* out
                             int B, int H, int T, int W, int C, float sigma, int radius, unsigned axes_flags,
                             float* dsigma_out, void* ws, size_t ws_bytes, kccot_stream_t stream);
 
+/* The tiling kccot_smooth_dsigma_f32 would launch at this shape, radius and axes_flags: a pure host function (no device call,
+ * no GPU needed) that runs the very planner of the launch, for tests and tools that must know which instantiation of the tile
+ * kernel a case reaches.  Applies the argument checks of kccot_smooth_dsigma_f32 that concern these arguments, with the same
+ * codes (KCCOT_EINVAL also for out == NULL).  out receives KCCOT_SMOOTH_DSIGMA_PLAN_INTS ints:
+ *   [0]       1 when the call launches the tile kernel; 0 when it does not (radius 0, or no axis bit: the result is exactly
+ *             0) -- every other entry is then 0
+ *   [1] [2]   the instantiation dsigma_tile<R, NI>: R = radius, NI = owned positions per thread
+ *   [3..6]    the tile extents tt, wt, ct along T, W, C and the segment hs along H
+ *   [7..10]   the piece counts ntt, ntw, ntc, nseg
+ *   [11]      the grid = B' * nseg * ntt * ntw * ntc workgroups
+ *   [12..16]  B', H', T', W', C': the kernel's view of the shape, in which [3..11] are expressed: an axis that is not smoothed
+ *             has been merged into its neighbour (W into C when W is not smoothed, B into H when H is not). */
+#define KCCOT_SMOOTH_DSIGMA_PLAN_INTS 17
+int kccot_smooth_dsigma_plan(int B, int H, int T, int W, int C, int radius, unsigned axes_flags, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,7 @@ SMOOTH3C_SIGNATURES = {
 SMOOTH_SIGMA_SIGNATURES = {
     "kccot_smooth_dsigma_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kccot_smooth_dsigma_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_dsigma_plan": (_i, [_i, _i, _i, _i, _i, _i, _u, _fp]),      # host only; out: DSIGMA_PLAN_INTS ints
 }
 
 
@@ -194,6 +195,7 @@ SMOOTH_ANISO_SIGNATURES = {
     "kccot_smooth_aniso_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
     "kccot_smooth_aniso_bwd_sharded_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
     "kccot_smooth_aniso_dsigma_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _i, _u, _fp, _fp, _sz, _fp]),
+    "kccot_smooth_aniso_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _u, _i, _fp]),      # host only; out: ANISO_PLAN_INTS ints
 }
 
 
@@ -203,11 +205,43 @@ METRICS_SIGNATURES = {
     "kccot_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "kccot_ssim_fwd_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _fp, _fp, _fp, _sz, _fp]),
     "kccot_ssim_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _i, _f, _fp, _fp, _sz, _fp]),
+    "kccot_ssim_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _fp]),      # host only; out: SSIM_PLAN_INTS ints
 }
 
 
 class KccotError(RuntimeError):
     pass
+
+
+# ---- the host-only plan queries: which tiling, and which instantiation of the tile kernel, a launch would use (no device
+# call: they work without a GPU).  The field names are those of the headers.
+DSIGMA_PLAN_INTS, ANISO_PLAN_INTS, SSIM_PLAN_INTS = 17, 13, 8
+_DSIGMA_PLAN = ("launches", "R", "NI", "tt", "wt", "ct", "hs", "ntt", "ntw", "ntc", "nseg", "grid", "Bv", "Hv", "Tv", "Wv", "Cv")
+_ANISO_PLAN = ("launches", "RS", "NI", "job", "tt", "wt", "ct", "hs", "ntt", "ntw", "ntc", "nseg", "grid")
+_SSIM_PLAN = ("wt", "ct", "hs", "nt", "ntw", "ntc", "nseg", "grid")
+ANISO_JOBS = {"fwd": 0, "adj": 1, "dsigma": 2}
+
+
+def _plan(fn, names, what, *args):
+    out = (_i * len(names))()
+    check(fn(*args, out), what)
+    return dict(zip(names, out))
+
+
+def smooth_dsigma_plan(shape, radius, axes_flags):
+    """kccot_smooth_dsigma_plan as a dict (include/kccot_smooth_sigma.h)"""
+    return _plan(lib.kccot_smooth_dsigma_plan, _DSIGMA_PLAN, "smooth_dsigma_plan", *shape, radius, axes_flags)
+
+
+def smooth_aniso_plan(shape, radius_t, radius_s, causal, job):
+    """kccot_smooth_aniso_plan as a dict (include/kccot_smooth_aniso.h); job: "fwd", "adj" or "dsigma" """
+    return _plan(lib.kccot_smooth_aniso_plan, _ANISO_PLAN, "smooth_aniso_plan", *shape, radius_t, radius_s,
+                 SMOOTH_CAUSAL_T if causal else 0, ANISO_JOBS[job])
+
+
+def ssim_plan(shape, radius, backward):
+    """kccot_ssim_plan as a dict (include/kccot_metrics.h)"""
+    return _plan(lib.kccot_ssim_plan, _SSIM_PLAN, "ssim_plan", *shape, radius, int(bool(backward)))
 
 
 def _load():

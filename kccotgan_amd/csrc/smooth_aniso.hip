@@ -606,25 +606,52 @@ int an_check(const AnCall& c, unsigned allowed) {
     return 0;
 }
 
-int an_check_ws(const AnCall& c) {
-    const size_t need = AnWs(c.B, c.H, c.T, c.W, c.C).total;
-    if (!c.ws || c.ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", c.who, c.ws_bytes, need);
+int an_check_size(const AnCall& c) {
     if ((c.n() + 255) / 256 > 0x7fffffff || (int64_t)c.T * c.W * c.C > 0x7fffffff ||
         (int64_t)c.B * ((c.n() / c.B + AN_SB - 1) / AN_SB) > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", c.who);
     return 0;
 }
 
-// one walk: the geometry and the tables of the job, the grid checked against its area of the workspace
-int an_walk(const AnCall& c, int job, AnArgs a, const AnAreas& w, int64_t* grid = nullptr) {
-    const AnPlan pl = an_plan(c.B, c.H, c.T, c.W, c.C, c.rt, c.rs, c.causal(), job);
-    if (!pl.ok || (size_t)pl.grid * 2 * sizeof(double) > w.lay.part)        // (the layout was sized from this very plan)
-        return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radii (%d, %d)", c.who, c.B, c.H, c.T, c.W, c.C, c.rt, c.rs);
-    if (grid) *grid = pl.grid;
+int an_check_ws(const AnCall& c) {
+    const size_t need = AnWs(c.B, c.H, c.T, c.W, c.C).total;
+    if (!c.ws || c.ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", c.who, c.ws_bytes, need);
+    return an_check_size(c);
+}
+
+// the flag bits the entry points of a job take (`sharded`: the two-call backward)
+unsigned an_allowed(int job, bool sharded = false) {
+    if (job == JOB_FWD) return KCCOT_SMOOTH_CAUSAL_T | KCCOT_SMOOTH_NO_DIVIDE | KCCOT_SMOOTH_EXTERNAL_MAX;
+    if (job == JOB_ADJ && sharded) return KCCOT_SMOOTH_CAUSAL_T | KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS;
+    return KCCOT_SMOOTH_CAUSAL_T;
+}
+
+int an_check_fwd_flags(const AnCall& c) {
+    if ((c.flags & KCCOT_SMOOTH_NO_DIVIDE) && (c.flags & KCCOT_SMOOTH_EXTERNAL_MAX))
+        return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_EXTERNAL_MAX and KCCOT_SMOOTH_NO_DIVIDE are exclusive", c.who);
+    return 0;
+}
+
+// does the dsigma entry launch aniso_tile at all (else both results are exactly 0)
+bool an_dsigma_launches(int rt, int rs) { return rt > 0 || rs > 0; }
+
+AnPlan an_plan_of(const AnCall& c, int job) { return an_plan(c.B, c.H, c.T, c.W, c.C, c.rt, c.rs, c.causal(), job); }
+
+// the tile geometry of a plan: what the launch hands the kernel and what kccot_smooth_aniso_plan reports
+void an_geometry(AnArgs& a, const AnCall& c, const AnPlan& pl) {
     a.H = c.H; a.T = c.T; a.W = c.W; a.C = c.C;
     a.tt = pl.tt; a.wt = pl.wt; a.ct = pl.ct; a.hs = pl.hs;
     a.ntt = (c.T + pl.tt - 1) / pl.tt; a.ntw = (c.W + pl.wt - 1) / pl.wt; a.ntc = (c.C + pl.ct - 1) / pl.ct;
     a.nseg = (c.H + pl.hs - 1) / pl.hs;
     a.rt = c.rt;
+}
+
+// one walk: the geometry and the tables of the job, the grid checked against its area of the workspace
+int an_walk(const AnCall& c, int job, AnArgs a, const AnAreas& w, int64_t* grid = nullptr) {
+    const AnPlan pl = an_plan_of(c, job);
+    if (!pl.ok || (size_t)pl.grid * 2 * sizeof(double) > w.lay.part)        // (the layout was sized from this very plan)
+        return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radii (%d, %d)", c.who, c.B, c.H, c.T, c.W, c.C, c.rt, c.rs);
+    if (grid) *grid = pl.grid;
+    an_geometry(a, c, pl);
     const SymD ss = make_sym_d(c.sigma_s, c.rs);
     for (int k = 0; k <= 2 * c.rs; ++k) { a.ws[k] = ss.w[k]; a.dws[k] = ss.dw[k]; }
     if (job == JOB_ADJ) {
@@ -663,7 +690,7 @@ int an_walk(const AnCall& c, int job, AnArgs a, const AnAreas& w, int64_t* grid 
 int an_bwd(const AnCall& c, const float* gout, const float* out, const float* max_in, float* stats_ext, float* din) {
     const bool stats_only = (c.flags & KCCOT_SMOOTH_STATS_ONLY) != 0, stats_in = (c.flags & KCCOT_SMOOTH_EXTERNAL_STATS) != 0;
     int rc;
-    if ((rc = an_check(c, KCCOT_SMOOTH_CAUSAL_T | (stats_ext ? KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS : 0u)))) return rc;
+    if ((rc = an_check(c, an_allowed(JOB_ADJ, stats_ext != nullptr)))) return rc;
     if (!gout || !out || !max_in || (!stats_only && !din)) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
     if ((rc = an_check_ws(c))) return rc;
     const AnAreas w(c);
@@ -681,6 +708,27 @@ int an_bwd(const AnCall& c, const float* gout, const float* out, const float* ma
 
 using namespace kccot;
 
+extern "C" int kccot_smooth_aniso_plan(int B, int H, int T, int W, int C, int radius_t, int radius_s, unsigned flags, int job, int* out) {
+    // (the sigmas and the workspace play no part in the tiling: placeholders that pass their checks)
+    const AnCall c{"smooth_aniso_plan", B, H, T, W, C, 1.f, 1.f, radius_t, radius_s, flags, nullptr, 0, nullptr};
+    int rc;
+    if (job != JOB_FWD && job != JOB_ADJ && job != JOB_DSIG) return fail(KCCOT_EINVAL, "%s: job %d is none of 0 (forward), 1 (adjoint), 2 (dsigma)", c.who, job);
+    // the adjoint: the bits of either backward entry point
+    if ((rc = an_check(c, an_allowed(job, job == JOB_ADJ)))) return rc;
+    if (job == JOB_FWD && (rc = an_check_fwd_flags(c))) return rc;
+    if (!out) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
+    if ((rc = an_check_size(c))) return rc;
+    for (int k = 0; k < KCCOT_SMOOTH_ANISO_PLAN_INTS; ++k) out[k] = 0;
+    if (job == JOB_DSIG && !an_dsigma_launches(radius_t, radius_s)) return 0;
+    const AnPlan pl = an_plan_of(c, job);
+    if (!pl.ok) return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radii (%d, %d)", c.who, B, H, T, W, C, radius_t, radius_s);
+    AnArgs a{};
+    an_geometry(a, c, pl);
+    const int v[KCCOT_SMOOTH_ANISO_PLAN_INTS] = {1, radius_s, pl.ni, job, a.tt, a.wt, a.ct, a.hs, a.ntt, a.ntw, a.ntc, a.nseg, (int)pl.grid};
+    for (int k = 0; k < KCCOT_SMOOTH_ANISO_PLAN_INTS; ++k) out[k] = v[k];
+    return 0;
+}
+
 extern "C" size_t kccot_smooth_aniso_workspace_bytes(int B, int H, int T, int W, int C) {
     if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return 0;
     return AnWs(B, H, T, W, C).total;
@@ -692,8 +740,8 @@ extern "C" int kccot_smooth_aniso_fwd_f32(const float* in, int B, int H, int T, 
     const AnCall c{"smooth_aniso_fwd", B, H, T, W, C, sigma_t, sigma_s, radius_t, radius_s, flags, ws, ws_bytes, (hipStream_t)stream};
     const bool nodiv = (flags & KCCOT_SMOOTH_NO_DIVIDE) != 0, ext = (flags & KCCOT_SMOOTH_EXTERNAL_MAX) != 0;
     int rc;
-    if ((rc = an_check(c, KCCOT_SMOOTH_CAUSAL_T | KCCOT_SMOOTH_NO_DIVIDE | KCCOT_SMOOTH_EXTERNAL_MAX))) return rc;
-    if (nodiv && ext) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_EXTERNAL_MAX and KCCOT_SMOOTH_NO_DIVIDE are exclusive", c.who);
+    if ((rc = an_check(c, an_allowed(JOB_FWD)))) return rc;
+    if ((rc = an_check_fwd_flags(c))) return rc;
     if (!in || !out || !max_inout) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
     if (in == out) return fail(KCCOT_EINVAL, "%s: in-place smoothing is not supported", c.who);
     if ((rc = an_check_ws(c))) return rc;
@@ -725,7 +773,7 @@ extern "C" int kccot_smooth_aniso_bwd_sharded_f32(const float* gout, const float
                                                   kccot_stream_t stream) {
     const AnCall c{"smooth_aniso_bwd_sharded", B, H, T, W, C, sigma_t, sigma_s, radius_t, radius_s, flags, ws, ws_bytes, (hipStream_t)stream};
     const unsigned both = KCCOT_SMOOTH_STATS_ONLY | KCCOT_SMOOTH_EXTERNAL_STATS;
-    const int rc = an_check_flags(c, KCCOT_SMOOTH_CAUSAL_T | both);
+    const int rc = an_check_flags(c, an_allowed(JOB_ADJ, true));
     if (rc) return rc;
     if (!(flags & both) || (flags & both) == both)
         return fail(KCCOT_EINVAL, "%s: exactly one of KCCOT_SMOOTH_STATS_ONLY and KCCOT_SMOOTH_EXTERNAL_STATS", c.who);
@@ -739,12 +787,12 @@ extern "C" int kccot_smooth_aniso_dsigma_f32(const float* in, const float* gout,
                                              void* ws, size_t ws_bytes, kccot_stream_t stream) {
     const AnCall c{"smooth_aniso_dsigma", B, H, T, W, C, sigma_t, sigma_s, radius_t, radius_s, flags, ws, ws_bytes, (hipStream_t)stream};
     int rc;
-    if ((rc = an_check(c, KCCOT_SMOOTH_CAUSAL_T))) return rc;
+    if ((rc = an_check(c, an_allowed(JOB_DSIG)))) return rc;
     if (!in || !gout || !out || !max_in || !dsigma_out) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
     if ((rc = an_check_ws(c))) return rc;
     const AnAreas w(c);
     int64_t nparts = 0;
-    if (radius_t > 0 || radius_s > 0) {
+    if (an_dsigma_launches(radius_t, radius_s)) {
         const float* stats = stats_in;
         if (!stats) {
             if ((rc = an_stats(c, gout, out, w, w.scal()))) return rc;

@@ -326,11 +326,76 @@ int launch_tile(const DsPlan& pl, const DsArgs& a, hipStream_t st) {
     }
 }
 
+// the tile geometry of a plan in the kernel's view of the shape: what the launch hands the kernel and what
+// kccot_smooth_dsigma_plan reports
+void ds_geometry(DsArgs& a, const DsShape& s, const DsPlan& pl) {
+    a.H = s.H; a.T = s.T; a.W = s.W; a.C = s.C;
+    a.tt = pl.tt; a.wt = pl.wt; a.ct = pl.ct; a.hs = pl.hs;
+    a.ntt = (s.T + pl.tt - 1) / pl.tt; a.ntw = (s.W + pl.wt - 1) / pl.wt; a.ntc = (s.C + pl.ct - 1) / pl.ct;
+    a.nseg = (s.H + pl.hs - 1) / pl.hs;
+    a.doT = s.doT; a.doW = s.doW; a.doH = s.doH; a.causal = s.causal;
+}
+
+// does this call launch dsigma_tile at all (else the result is exactly 0)
+bool ds_launches(int radius, unsigned axes_flags) { return radius > 0 && (axes_flags & DS_AXES); }
+
+// the checks of the flags; then (ds_check_dims) those of the shape and the radius.  sigma: NULL where the caller has none (the
+// plan query)
+int ds_check_flags(const char* who, unsigned axes_flags) {
+    if (axes_flags & KCCOT_SMOOTH_NO_DIVIDE) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_NO_DIVIDE is not an axis flag", who);
+    if (axes_flags & KCCOT_SMOOTH_EXTERNAL_MAX) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_EXTERNAL_MAX is not an axis flag", who);
+    if (axes_flags & KCCOT_SMOOTH_STATS_ONLY) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_STATS_ONLY is not an axis flag", who);
+    if (axes_flags & KCCOT_SMOOTH_EXTERNAL_STATS)
+        return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_EXTERNAL_STATS is not an axis flag (hand the sums in through stats_in)", who);
+    if (axes_flags & ~(DS_AXES | KCCOT_SMOOTH_CAUSAL_T)) return fail(KCCOT_EINVAL, "%s: unknown flag bits 0x%x", who, axes_flags);
+    if ((axes_flags & KCCOT_SMOOTH_CAUSAL_T) && !(axes_flags & KCCOT_SMOOTH_T))
+        return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_CAUSAL_T needs KCCOT_SMOOTH_T", who);
+    return 0;
+}
+
+int ds_check_dims(const char* who, int B, int H, int T, int W, int C, int radius, unsigned axes_flags, const float* sigma) {
+    if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", who, B, H, T, W, C);
+    if (radius < 0 || radius > SM_MAXR) return fail(KCCOT_EINVAL, "%s: radius %d outside 0..%d", who, radius, SM_MAXR);
+    if (sigma && !(*sigma > 0.f)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", who);
+    const bool causal = (axes_flags & KCCOT_SMOOTH_CAUSAL_T) != 0;
+    // REFLECT padding needs pad < dim; a causal T has no padding: any radius, radius >= T included
+    if (((axes_flags & KCCOT_SMOOTH_T) && !causal && radius >= T) || ((axes_flags & KCCOT_SMOOTH_H) && radius >= H) ||
+        ((axes_flags & KCCOT_SMOOTH_W) && radius >= W))
+        return fail(KCCOT_EINVAL, "%s: REFLECT padding needs radius < the length of every symmetric axis", who);
+    return 0;
+}
+
+int ds_check_size(const char* who, int B, int H, int T, int W, int C) {
+    const int64_t n = (int64_t)((size_t)B * H * T * W * C);
+    if ((n + 255) / 256 > 0x7fffffff || (int64_t)T * W * C > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", who);
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace kccot
 
 using namespace kccot;
+
+extern "C" int kccot_smooth_dsigma_plan(int B, int H, int T, int W, int C, int radius, unsigned axes_flags, int* out) {
+    const char* who = "smooth_dsigma_plan";
+    int rc;
+    if ((rc = ds_check_flags(who, axes_flags))) return rc;
+    if (!out) return fail(KCCOT_EINVAL, "%s: null pointer", who);
+    if ((rc = ds_check_dims(who, B, H, T, W, C, radius, axes_flags, nullptr))) return rc;
+    if ((rc = ds_check_size(who, B, H, T, W, C))) return rc;
+    for (int k = 0; k < KCCOT_SMOOTH_DSIGMA_PLAN_INTS; ++k) out[k] = 0;
+    if (!ds_launches(radius, axes_flags)) return 0;
+    const DsShape s = ds_shape(B, H, T, W, C, axes_flags, radius);
+    const DsPlan pl = ds_plan(s, radius);
+    if (!pl.ok) return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radius %d", who, B, H, T, W, C, radius);
+    DsArgs a{};
+    ds_geometry(a, s, pl);
+    const int v[KCCOT_SMOOTH_DSIGMA_PLAN_INTS] = {1, radius, pl.ni, a.tt, a.wt, a.ct, a.hs, a.ntt, a.ntw, a.ntc, a.nseg, (int)pl.grid,
+                                                  s.B, a.H, a.T, a.W, a.C};
+    for (int k = 0; k < KCCOT_SMOOTH_DSIGMA_PLAN_INTS; ++k) out[k] = v[k];
+    return 0;
+}
 
 extern "C" size_t kccot_smooth_dsigma_workspace_bytes(int B, int H, int T, int W, int C) {
     if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return 0;
@@ -342,27 +407,14 @@ extern "C" int kccot_smooth_dsigma_f32(const float* in, const float* gout, const
                                        unsigned axes_flags, float* dsigma_out, void* ws, size_t ws_bytes, kccot_stream_t stream) {
     const char* who = "smooth_dsigma";
     hipStream_t st = (hipStream_t)stream;
-    if (axes_flags & KCCOT_SMOOTH_NO_DIVIDE) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_NO_DIVIDE is not an axis flag", who);
-    if (axes_flags & KCCOT_SMOOTH_EXTERNAL_MAX) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_EXTERNAL_MAX is not an axis flag", who);
-    if (axes_flags & KCCOT_SMOOTH_STATS_ONLY) return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_STATS_ONLY is not an axis flag", who);
-    if (axes_flags & KCCOT_SMOOTH_EXTERNAL_STATS)
-        return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_EXTERNAL_STATS is not an axis flag (hand the sums in through stats_in)", who);
-    if (axes_flags & ~(DS_AXES | KCCOT_SMOOTH_CAUSAL_T)) return fail(KCCOT_EINVAL, "%s: unknown flag bits 0x%x", who, axes_flags);
-    if ((axes_flags & KCCOT_SMOOTH_CAUSAL_T) && !(axes_flags & KCCOT_SMOOTH_T))
-        return fail(KCCOT_EINVAL, "%s: KCCOT_SMOOTH_CAUSAL_T needs KCCOT_SMOOTH_T", who);
+    int rc;
+    if ((rc = ds_check_flags(who, axes_flags))) return rc;
     if (!in || !gout || !out || !max_in || !dsigma_out) return fail(KCCOT_EINVAL, "%s: null pointer", who);
-    if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return fail(KCCOT_EINVAL, "%s: bad shape [%d,%d,%d,%d,%d]", who, B, H, T, W, C);
-    if (radius < 0 || radius > SM_MAXR) return fail(KCCOT_EINVAL, "%s: radius %d outside 0..%d", who, radius, SM_MAXR);
-    if (!(sigma > 0.f)) return fail(KCCOT_EINVAL, "%s: sigma must be > 0", who);
-    const bool causal = (axes_flags & KCCOT_SMOOTH_CAUSAL_T) != 0;
-    // REFLECT padding needs pad < dim; a causal T has no padding: any radius, radius >= T included
-    if (((axes_flags & KCCOT_SMOOTH_T) && !causal && radius >= T) || ((axes_flags & KCCOT_SMOOTH_H) && radius >= H) ||
-        ((axes_flags & KCCOT_SMOOTH_W) && radius >= W))
-        return fail(KCCOT_EINVAL, "%s: REFLECT padding needs radius < the length of every symmetric axis", who);
+    if ((rc = ds_check_dims(who, B, H, T, W, C, radius, axes_flags, &sigma))) return rc;
     const DsWs lay(B, H, T, W, C);
     if (!ws || ws_bytes < lay.total) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", who, ws_bytes, lay.total);
+    if ((rc = ds_check_size(who, B, H, T, W, C))) return rc;
     const int64_t n = (int64_t)((size_t)B * H * T * W * C);
-    if ((n + 255) / 256 > 0x7fffffff || (int64_t)T * W * C > 0x7fffffff) return fail(KCCOT_EUNSUPPORTED, "%s: tensor too large", who);
 
     char* base = reinterpret_cast<char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     double* part = reinterpret_cast<double*>(base);
@@ -371,24 +423,19 @@ extern "C" int kccot_smooth_dsigma_f32(const float* in, const float* gout, const
     float* pcnt = reinterpret_cast<float*>(base + lay.part + lay.scal + lay.blk);
 
     int64_t nparts = 0;
-    if (radius > 0 && (axes_flags & DS_AXES)) {
-        int rc;
+    if (ds_launches(radius, axes_flags)) {
         const float* stats = stats_in;
         if (!stats) {
             if ((rc = smooth_maxnorm_stats(gout, out, n, pdot, pcnt, scal, st))) return rc;
             stats = scal;
         }
-        DsShape s = ds_shape(B, H, T, W, C, axes_flags, radius);
+        const DsShape s = ds_shape(B, H, T, W, C, axes_flags, radius);
         const DsPlan pl = ds_plan(s, radius);
         if (!pl.ok || (size_t)pl.grid * sizeof(double) > lay.part)      // (the layout was sized from this very plan)
             return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radius %d", who, B, H, T, W, C, radius);
         DsArgs a{};
         a.in = in; a.gout = gout; a.out = out; a.mx = max_in; a.stats = stats; a.part = part;
-        a.H = s.H; a.T = s.T; a.W = s.W; a.C = s.C;
-        a.tt = pl.tt; a.wt = pl.wt; a.ct = pl.ct; a.hs = pl.hs;
-        a.ntt = (s.T + pl.tt - 1) / pl.tt; a.ntw = (s.W + pl.wt - 1) / pl.wt; a.ntc = (s.C + pl.ct - 1) / pl.ct;
-        a.nseg = (s.H + pl.hs - 1) / pl.hs;
-        a.doT = s.doT; a.doW = s.doW; a.doH = s.doH; a.causal = s.causal;
+        ds_geometry(a, s, pl);
         a.sd = make_sym_d(sigma, radius);
         if (s.causal) a.cd = make_caus_d(sigma, radius);
         switch (radius) {

@@ -291,11 +291,18 @@ int ss_check(const SsCall& c) {
     return 0;
 }
 
-// after the argument checks: too large to index, then the workspace
-int ss_check_size(const SsCall& c, const SsPlan& pl) {
+// too large to index: the entry points and kccot_ssim_plan
+int ss_check_index(const SsCall& c, const SsPlan& pl) {
     if ((int64_t)c.B * c.T > 0x7fffffff || (int64_t)c.W * c.C > 0x7fffffff || pl.tiles > 0x7fffffff || pl.grid > 0x7fffffff ||
         (double)c.B * c.H * c.T * (double)c.W * c.C > 4e18)
         return fail(KCCOT_EUNSUPPORTED, "%s: tensor [%d,%d,%d,%d,%d] too large to index", c.who, c.B, c.H, c.T, c.W, c.C);
+    return 0;
+}
+
+// after the argument checks: too large to index, then the workspace
+int ss_check_size(const SsCall& c, const SsPlan& pl) {
+    const int rc = ss_check_index(c, pl);
+    if (rc) return rc;
     const size_t need = ss_ws_bytes(c.B, c.H, c.T, c.W, c.C);
     if (!c.ws || c.ws_bytes < need) return fail(KCCOT_EWORKSPACE, "%s: workspace %zu < required %zu", c.who, c.ws_bytes, need);
     return 0;
@@ -339,6 +346,19 @@ bool ss_overlap(const float* p, const float* q, double n) {
 }  // namespace kccot
 
 using namespace kccot;
+
+extern "C" int kccot_ssim_plan(int B, int H, int T, int W, int C, int radius, int backward, int* out) {
+    // (sigma, data_range and the workspace play no part in the tiling: placeholders that pass their checks)
+    const SsCall c{"ssim_plan", B, H, T, W, C, 1.f, radius, 1.f, nullptr, 0, nullptr};
+    int rc;
+    if ((rc = ss_check(c))) return rc;
+    if (!out) return fail(KCCOT_EINVAL, "%s: null pointer", c.who);
+    const SsPlan pl = ss_plan(B, H, T, W, C, radius, backward != 0);
+    if ((rc = ss_check_index(c, pl))) return rc;
+    const int v[KCCOT_SSIM_PLAN_INTS] = {pl.wt, pl.ct, pl.hs, pl.nt, pl.ntw, pl.ntc, pl.nseg, (int)pl.grid};
+    for (int k = 0; k < KCCOT_SSIM_PLAN_INTS; ++k) out[k] = v[k];
+    return 0;
+}
 
 extern "C" size_t kccot_ssim_workspace_bytes(int B, int H, int T, int W, int C) {
     if (B <= 0 || H <= 0 || T <= 0 || W <= 0 || C <= 0) return 0;

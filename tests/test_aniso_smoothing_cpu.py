@@ -15,7 +15,7 @@ import smooth_aniso_oracle as ao
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["kccot_smooth_aniso_bwd_f32", "kccot_smooth_aniso_bwd_sharded_f32", "kccot_smooth_aniso_dsigma_f32",
-         "kccot_smooth_aniso_fwd_f32", "kccot_smooth_aniso_workspace_bytes"]
+         "kccot_smooth_aniso_fwd_f32", "kccot_smooth_aniso_plan", "kccot_smooth_aniso_workspace_bytes"]
 
 
 def _decls(header):

@@ -14,7 +14,7 @@ import torch
 import smooth_sigma_oracle as so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["kccot_smooth_dsigma_f32", "kccot_smooth_dsigma_workspace_bytes"]
+NAMES = ["kccot_smooth_dsigma_f32", "kccot_smooth_dsigma_plan", "kccot_smooth_dsigma_workspace_bytes"]
 
 
 def _decls(header):

@@ -16,7 +16,7 @@ import torch
 import ssim_oracle as so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["kccot_ssim_bwd_f32", "kccot_ssim_fwd_f32", "kccot_ssim_workspace_bytes"]
+NAMES = ["kccot_ssim_bwd_f32", "kccot_ssim_fwd_f32", "kccot_ssim_plan", "kccot_ssim_workspace_bytes"]
 
 
 def _decls(header):
@@ -238,3 +238,24 @@ def test_the_reference_alone_stays_inside_the_caps(shape, win, sigma, kind):
         d_err = float((so.adjoint(g, x, y, sigma, r).double() - d_ref).abs().max()) / float(d_ref.abs().max())
         print("%s %s win %d: float32 adjoint err / max %.3e" % (kind, shape, win, d_err))
         assert d_err <= so.CAP_DY
+
+
+@pytest.mark.parametrize("r", range(8))
+def test_flat_adjoint_in_float32_stays_inside_the_cap_except_at_radius_0(r):
+    """The condition under which tests/test_gpu_tile_instantiations.py bounds the adjoint on the FLAT input by CAP_DY: the oracle
+    in float32 against itself in float64, on that module's own inputs (the radius cases of tests/tile_plan_cases.py, seeds 71 and
+    72, sigma 1.5).  Radii 1..7 stay inside the cap; radius 0 does not -- one tap of weight 1 makes the three variances
+    differences of equal numbers, float32 leaves rounding noise there (the kernel writes exact zeros) -- so the GPU module
+    leaves the flat adjoint at radius 0 out."""
+    import tile_plan_cases as tp
+    shape = tp.SSIM_SHAPE_R
+    assert [c[1] for c in tp.SSIM_CASES if "radius" in c[3]] == [shape] * 8
+    x, y = so.inputs("flat", shape, 71)
+    g = so.upstream(shape, 72)
+    ref = so.adjoint(g.double(), x.double(), y.double(), 1.5, r)
+    err = float((so.adjoint(g, x, y, 1.5, r).double() - ref).abs().max()) / float(ref.abs().max())
+    print("flat %s r %d: float32 adjoint err / max %.3e (cap %.1e)" % (shape, r, err, so.CAP_DY))
+    if r == 0:
+        assert err > so.CAP_DY, "the flat adjoint at radius 0 can join the GPU module's cases now"
+    else:
+        assert err <= so.CAP_DY
