@@ -146,27 +146,57 @@ __device__ __forceinline__ void keep_in_regs(float (&r)[N]) {
 // adds per entry instead of add/add/mul/mul, exp2/log2 are single hardware instructions, and the
 // two-wide vector type lets hipcc issue packed v_pk_add_f32.  The iterates are the same numbers in
 // other units; only fp32 rounding differs (the duals are O(1e3) with an ulp of 1e-4 either way).
-template <int EPT, int LPR, bool ROW>
-__device__ __forceinline__ float half_step(const float (&c2)[EPT], float self, const float* other, int q, float lw2) {
-    float o[EPT];
-    load_other<EPT>(o, other, q);
-    float y[EPT];
-    if constexpr (EPT >= 2) {
-#pragma unroll
-        for (int m = 0; m < EPT; m += 2) {
-            f32x2 cc = {c2[m], c2[m + 1]}, oo = {o[m], o[m + 1]}, ss = {self, self};
-            const f32x2 t = ROW ? ((ss - cc) + oo) : ((oo - cc) + ss);
-            y[m] = t.x; y[m + 1] = t.y;
-        }
-    } else {
-        y[0] = ROW ? ((self - c2[0]) + o[0]) : ((o[0] - c2[0]) + self);
-    }
+// Trims of the forward half-step (profiles/sinkhorn_forward_trim_ab.json), a bit mask for experiment builds:
+// in the role kernel 1 the DPP max as one asm statement (in the one-role kernel it measured +2 us: not there), and in the
+// role kernel's instances without the shortcut
+// 2 |du| formed off the chain and only when the stop rule reads it, 4 running row addresses, 16 the add tree on two-wide pairs;
+// 32 (experiment, not in the product) |du| of sinkhorn_fused_reg and sinkhorn_fwd_body only when the stop rule reads it.
+// (8 was the row role's self - c2 formed off the chain: measured slower, source not kept.)
+#ifndef KCCOT_FWD_TRIM
+#define KCCOT_FWD_TRIM 23
+#endif
+
+// The DPP max of a line's lanes as ONE asm statement.  common.h's seg_max is one statement per step, and behind every
+// statement whose result the next instruction reads hipcc pads a wait state of its own (it cannot see what the statement
+// wrote with): three s_nop 0 on the chain of the half-step at eight lanes per line.  As one statement the steps keep the
+// s_nop 1 the DPP read of a fresh VALU result needs, and one pad is left, behind the last.  Same instructions on the same
+// operands, same bits.
+#define KCCOT_DPP_MAX_STEP(CTRL) "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
+template <int LPR>
+__device__ __forceinline__ float seg_max_chain(float v) {
+    if constexpr (LPR >= 16)
+        asm volatile(KCCOT_DPP_MAX_STEP("quad_perm:[1,0,3,2]") KCCOT_DPP_MAX_STEP("quad_perm:[2,3,0,1]")
+                     KCCOT_DPP_MAX_STEP("row_half_mirror") KCCOT_DPP_MAX_STEP("row_mirror") : "+v"(v));
+    else if constexpr (LPR >= 8)
+        asm volatile(KCCOT_DPP_MAX_STEP("quad_perm:[1,0,3,2]") KCCOT_DPP_MAX_STEP("quad_perm:[2,3,0,1]")
+                     KCCOT_DPP_MAX_STEP("row_half_mirror") : "+v"(v));
+    else if constexpr (LPR >= 4)
+        asm volatile(KCCOT_DPP_MAX_STEP("quad_perm:[1,0,3,2]") KCCOT_DPP_MAX_STEP("quad_perm:[2,3,0,1]") : "+v"(v));
+    else if constexpr (LPR >= 2)
+        asm volatile(KCCOT_DPP_MAX_STEP("quad_perm:[1,0,3,2]") : "+v"(v));
+    return v;
+}
+
+// The LDS address of a word of a __shared__ array, and back: a 32-bit value that a loop can carry, move on and pin in a VGPR
+// (keep_in_regs) where a pointer expression would be formed again from the loop counter in front of every access.
+typedef __attribute__((address_space(3))) float lds_float;
+__device__ __forceinline__ unsigned lds_address(const float* p) { return (unsigned)(size_t)(const lds_float*)p; }
+__device__ __forceinline__ float* lds_pointer(unsigned a) { return (float*)(lds_float*)(size_t)a; }
+
+// no stamp: the half-step of every product kernel (the diagnostic twin of the role kernel passes its own, see fused_roles_body)
+struct NoStamp { __device__ __forceinline__ void operator()(int) const {} };
+
+// The half-step behind its entries y[] = (U_i - c2_ij) + V_j: max, shifted exp2, sum, log2, new dual.  stamp(0) is called once
+// the line's max is known, stamp(1) once its sum is (half_step calls stamp(-1) once the duals have arrived).
+template <int EPT, int LPR, bool PAIRS = false, bool ONE_MAX = false, typename STAMP = NoStamp>
+__device__ __forceinline__ float half_step_lse(const float (&y)[EPT], float self, float lw2, STAMP stamp = STAMP()) {
     float mx = y[0];
 #pragma unroll
     for (int m = 1; m < EPT; ++m) mx = fmaxf(mx, y[m]);
-    mx = seg_max<LPR>(mx);
+    mx = ONE_MAX ? seg_max_chain<LPR>(mx) : seg_max<LPR>(mx);
     // tf.reduce_logsumexp: a non-finite max is replaced by 0
     const float shift = (mx > -INFINITY && mx < INFINITY) ? mx : 0.f;
+    stamp(0);
     float e[EPT];
     if constexpr (EPT >= 2) {
         const f32x2 sh = {shift, shift};
@@ -181,13 +211,51 @@ __device__ __forceinline__ float half_step(const float (&c2)[EPT], float self, c
         e[0] = __builtin_amdgcn_exp2f(y[0] - shift);
     }
     // pairwise tree: log2(EPT) dependent adds instead of EPT
+    if constexpr (PAIRS && EPT >= 4) {
+        // The same tree with its two halves side by side: below its last level the tree adds within e[0 .. EPT/2) and within
+        // e[EPT/2 .. EPT) by one pattern, so the pairs {e[k], e[k + EPT/2]} go through it as two-wide adds (v_pk_add_f32) and
+        // the last level adds the two lanes of pair 0.  Same operands in every add, same bits.  hipcc finds this form by itself
+        // in the callers that index the history rows by the loop counter and loses it with the running offsets of the role
+        // kernel, which therefore asks for it (PAIRS); every other caller keeps the loop below.
+        constexpr int H = EPT / 2;
+        f32x2 pe[H];
 #pragma unroll
-    for (int w = 1; w < EPT; w *= 2)
+        for (int k = 0; k < H; ++k) pe[k] = f32x2{e[k], e[k + H]};
 #pragma unroll
-        for (int m = 0; m + w < EPT; m += 2 * w) e[m] += e[m + w];
+        for (int w = 1; w < H; w *= 2)
+#pragma unroll
+            for (int m = 0; m + w < H; m += 2 * w) pe[m] += pe[m + w];
+        e[0] = pe[0].x + pe[0].y;
+    } else {
+#pragma unroll
+        for (int w = 1; w < EPT; w *= 2)
+#pragma unroll
+            for (int m = 0; m + w < EPT; m += 2 * w) e[m] += e[m + w];
+    }
     const float s = seg_sum<LPR>(e[0]);
+    stamp(1);
     const float lse2 = __builtin_amdgcn_logf(s) + shift;
     return (lw2 - lse2) + self;   // gan_utils.py:154,156 in log2 units
+}
+
+template <int EPT, int LPR, bool ROW, bool PAIRS = false, bool ONE_MAX = false, typename STAMP = NoStamp>
+__device__ __forceinline__ float half_step(const float (&c2)[EPT], float self, const float* other, int q, float lw2,
+                                           STAMP stamp = STAMP()) {
+    float o[EPT];
+    load_other<EPT>(o, other, q);
+    stamp(-1);                                                 // the other role's duals have arrived
+    float y[EPT];
+    if constexpr (EPT >= 2) {
+#pragma unroll
+        for (int m = 0; m < EPT; m += 2) {
+            f32x2 cc = {c2[m], c2[m + 1]}, oo = {o[m], o[m + 1]}, ss = {self, self};
+            const f32x2 t = ROW ? ((ss - cc) + oo) : ((oo - cc) + ss);
+            y[m] = t.x; y[m + 1] = t.y;
+        }
+    } else {
+        y[0] = ROW ? ((self - c2[0]) + o[0]) : ((o[0] - c2[0]) + self);
+    }
+    return half_step_lse<EPT, LPR, PAIRS, ONE_MAX>(y, self, lw2, stamp);
 }
 
 // c2 = C * k2 in both orientations; entries past the matrix edge are +inf (-> exp2(-inf) = 0)
@@ -311,6 +379,16 @@ __device__ __forceinline__ void load_costs_raw(const float* C, int n, int line, 
     load_costs_raw<EPT, ROW>(C, n, line, q, k2, c2, craw);
 }
 
+// A NaN cost or NaN entry of dC leaves the register kernels for n <= 64 (fused bodies, sinkhorn_fwd_body, sinkhorn_bwd_body below
+// 16 entries per lane) as the quiet NaN 0x7fc00000.  A change of behaviour on non-finite inputs: before, the sign of such a NaN
+// was whatever the kernel's arithmetic left.  NOT covered: the dual histories, the plan, the sweep kernels at 16 entries per lane
+// (n > 64: sinkhorn_bwd_body there is at its register cap, and the select moved its sweep loop and its spills), the multi-CU and
+// streaming kernels.  Which operand's NaN an add or a
+// multiply hands on follows the operand order hipcc picks for a commutative operation, per kernel and per build, so the sign of
+// a NaN result differed between the fused and the two-launch forms and moved with unrelated changes of a loop
+// (tests/test_gpu_forward_trim.py, non-finite cost matrices).  One compare and one select per stored word, behind the loops.
+__device__ __forceinline__ float canonical_nan(float x) { return x != x ? __uint_as_float(0x7fc00000u) : x; }
+
 // The cost of a fused problem, by the one thread that hands it off: the waves' partial sums (wave_sum of cost_partial, parked
 // in red[] in front of the barrier of the dC transpose) added in wave order to + 0.0f, as block_sum adds them.
 // All 16 words are read at once (a loop over nw is one LDS round trip per wave, on the thread the kernel's end waits for);
@@ -419,7 +497,7 @@ __device__ __forceinline__ void store_dc_rows(float* dC, const float (&drow)[EPT
 #pragma unroll
         for (int m = 0; m < EPT; ++m) {
             const int idx = q * EPT + m;
-            if (idx < n) dC[(int64_t)line * n + idx] = drow[m];
+            if (idx < n) dC[(int64_t)line * n + idx] = canonical_nan(drow[m]);
         }
     }
 }
@@ -480,7 +558,8 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
         KCCOT_STAMP(0);
         const float un = half_step<EPT, LPR, true>(crow, ui, v_s, q, lwu);
         KCCOT_STAMP(1);
-        const float du = (active && q == 0) ? fabsf(un - ui) : 0.f;
+        float du = 0.f;
+        if (!(KCCOT_FWD_TRIM & 32) || (((a.stop_mode == KCCOT_STOP_INDEX) ? it >= a.Lmin : it + 1 >= a.Lmin) && it + 1 < a.L)) du = (active && q == 0) ? fabsf(un - ui) : 0.f;
         int bits = 0;
         if (SHORTCUT && detect) {
             shortcut_mismatch(bits, un, ui, pu2, pu3, pu4);
@@ -569,7 +648,7 @@ __device__ __forceinline__ void sinkhorn_fwd_body(const SinkArgs& a) {
     if (t == 0) {
         // with loss_out, the last of the three workgroups to arrive combines the costs (gan_utils.py:225)
         const float w[3] = {2.0f, -1.0f, -1.0f};
-        publish_cost<3>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost, nits, computed, w, a.loss_out != nullptr);
+        publish_cost<3>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, canonical_nan(cost), nits, computed, w, a.loss_out != nullptr);
     }
 }
 
@@ -842,7 +921,8 @@ __device__ __forceinline__ void sinkhorn_bwd_body(const SinkBwdArgs& a) {
 #pragma unroll
         for (int m = 0; m < EPT; ++m) {
             const int idx = q * EPT + m;
-            if (idx < n) dC[(int64_t)idx * n + line] += dcol[m];
+            if constexpr (EPT < 16) { if (idx < n) dC[(int64_t)idx * n + line] = canonical_nan(dC[(int64_t)idx * n + line] + dcol[m]); }
+            else { if (idx < n) dC[(int64_t)idx * n + line] += dcol[m]; }
         }
     }
 }
@@ -937,7 +1017,8 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     for (int it = 0; it < L; ++it) {
         KCCOT_STAMP(9);
         const float un = half_step<EPT, LPR, true>(crow, ui, hv + it * NS, q, lw2);
-        const float du = (active && q == 0) ? fabsf(un - ui) : 0.f;
+        float du = 0.f;
+        if (!(KCCOT_FWD_TRIM & 32) || (it + 1 >= a.Lmin && it + 1 < L)) du = (active && q == 0) ? fabsf(un - ui) : 0.f;
         int bits = 0;
         if (SHORTCUT && detect) {
             shortcut_mismatch(bits, un, ui, pu2, pu3, pu4);
@@ -1086,7 +1167,7 @@ __global__ __launch_bounds__(LPR * SK_MAXN < SK_MAXT ? LPR * SK_MAXN : SK_MAXT) 
     KCCOT_STAMP_IF(true, 21);
     take_dc_cols<EPT>(hist, drow, n, line, q, active);
     store_dc_rows<EPT>(dC, drow, n, line, q, active);
-    if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost_of_waves(red, nw), nits, computed, a.w, true);
+    if (t == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, canonical_nan(cost_of_waves(red, nw)), nits, computed, a.w, true);
     KCCOT_STAMP_IF(true, 19);
     KCCOT_STAMP_DRAINED(22);
 }
@@ -1172,19 +1253,54 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
     float p2 = 0.f, p3 = 0.f, p4 = 0.f;
     int nits = 0;
     float self = 0.f;                                          // ui (row role) / vj (column role)
-    // one half-step of this role: the dual, its history row (the next half-step's exchange array) and the shortcut's
-    // mismatch bits, OR-ed into mis[] per wave (both roles vote, each with the bits of its own dual)
+    // One half-step of this role: the dual, its history row (the next half-step's exchange array) and the shortcut's
+    // mismatch bits, OR-ed into mis[] per wave (both roles vote, each with the bits of its own dual).
+    // In the forward only one role works per half-step and all 16 waves wait for its eight, two to a SIMD and one vector port:
+    // every instruction between the barrier that opens a role's half-step and the barrier that ends it is paid by the whole
+    // workgroup (tools/forward_issue_budget.py counts them).  So what the half-step does not need is done in the OTHER
+    // role's half-step (off_chain), pinned between that half-step's two barriers:
+    //   - the addresses of the row read and the row written are running LDS addresses (rb, wb), moved on by one row there,
+    //     not it * NS formed behind the barrier in front of the read and in front of the write;
+    //   - |du| (the stop rule's term, row role) is formed there too, and only in an iteration whose stop rule reads it.
+    // The instances with the shortcut keep the parent's forms: there these cost two to four registers, and a solve that
+    // jumps leaves this loop after a handful of iterations.
+    constexpr bool RUNNING = (KCCOT_FWD_TRIM & 4) && !SHORTCUT;
+    constexpr bool DU_OFF_CHAIN = (KCCOT_FWD_TRIM & 2) && !SHORTCUT;
+    constexpr bool PAIRS = (KCCOT_FWD_TRIM & 16) && !SHORTCUT;
+    constexpr bool ONE_MAX = (KCCOT_FWD_TRIM & 1) != 0;      // every role instance; the other callers of half_step keep seg_max
+    unsigned rb = lds_address(ho + (COL ? NS : 0) + q * EPT);  // this lane's entries of the row the next half-step reads
+    unsigned wb = lds_address(hs + NS + line);                 // the line's word of the row it writes
+    float prev = 0.f;                                          // the dual before the last half-step
     auto own_half_step = [&](int it, float& du) {
-        const float sn = half_step<EPT, LPR, !COL>(c2, self, ho + (COL ? it + 1 : it) * NS, q, lw2);
-        du = (active && q == 0) ? fabsf(sn - self) : 0.f;
-        if (active && q == 0) hs[(it + 1) * NS + line] = sn;
+        (void)du;
+        const float* other = RUNNING ? lds_pointer(rb) : ho + (COL ? it + 1 : it) * NS + q * EPT;
+        const float sn = half_step<EPT, LPR, !COL, PAIRS, ONE_MAX>(c2, self, other, 0, lw2, [&](int k) { (void)k; KCCOT_STAMP(24 + k); });
+        if constexpr (!DU_OFF_CHAIN) du = (active && q == 0) ? fabsf(sn - self) : 0.f;
+        if (active && q == 0) {
+            if constexpr (RUNNING) *lds_pointer(wb) = sn;
+            else hs[(it + 1) * NS + line] = sn;
+        }
+        KCCOT_STAMP(26);
         if (SHORTCUT && detect) {
             int bits = 0;
             shortcut_mismatch(bits, sn, self, p2, p3, p4);
             p4 = p3; p3 = p2; p2 = self;
             shortcut_vote(bits, active, t, mis, it);
         }
+        if constexpr (DU_OFF_CHAIN) prev = self;
         self = sn;
+    };
+    // this role's work of the half-step in which the other role is on the chain; the empty asm statements hold it between
+    // the two barriers around them (a barrier orders memory operations, not register arithmetic: see keep_in_regs)
+    auto off_chain = [&](int it, float& du) {
+        if constexpr (RUNNING) asm volatile("" : "+v"(self), "+v"(rb), "+v"(wb));
+        if constexpr (DU_OFF_CHAIN && !COL) {
+            if (it + 1 >= a.Lmin && it + 1 < L) du = (active && q == 0) ? fabsf(self - prev) : 0.f;
+        }
+        if constexpr (RUNNING) {
+            rb += NS * 4; wb += NS * 4;
+            asm volatile("" : "+v"(rb), "+v"(wb));
+        }
     };
     // ---------------------------------------------------------------- forward
     KCCOT_STAMP_IF(true, 11);
@@ -1193,9 +1309,12 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
         float du = 0.f;
         if constexpr (!COL) own_half_step(it, du);
         lds_barrier();
+        KCCOT_STAMP(27);
         if constexpr (COL) { float dv; own_half_step(it, dv); }
+        else off_chain(it, du);
         lds_barrier();
         KCCOT_STAMP(10);
+        if constexpr (COL) { float dv; off_chain(it, dv); }
         nits = it + 1;
         ++computed;
         if (nits >= a.Lmin && it + 1 < L) {                   // gan_utils.py:157-160 (sum over the row role's du)
@@ -1207,7 +1326,7 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
             if (per) {
                 detect = false;
                 const int K1 = shortcut_resume(L, a.Lmin, KCCOT_STOP_COUNT);
-                if (K1 > nits) {
+                if (K1 > nits) {                              // (no running addresses to move: RUNNING implies !SHORTCUT)
                     fill_history_rows(hu, hv, NS, n, t, nits, K1, per);
                     __syncthreads();
                     self = hs[K1 * NS + (active ? line : 0)];
@@ -1305,7 +1424,7 @@ __device__ __forceinline__ void fused_roles_body(const SinkFusedArgs& a, float* 
         take_dc_cols<EPT>(hist, d, n, line, q, active);
         store_dc_rows<EPT>(dC, d, n, line, q, active);
     } else {
-        if (tr == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, cost_of_waves(red, TR >> 5), nits, computed, a.w, true);
+        if (tr == 0) publish_cost<NPROB>(a.cost_out, a.nits_out, a.loss_out, a.ticket, p, canonical_nan(cost_of_waves(red, TR >> 5)), nits, computed, a.w, true);
         KCCOT_STAMP_IF(true, 19);
     }
     KCCOT_STAMP_DRAINED(22);

@@ -33,7 +33,10 @@ def fused_stamps(roles, launches=20):
     16: kernel entry (16 -> 11 the prologue); between the loops (12 -> 13): 17 the cost's partial sums are formed, 20 the
     final-cost adjoint is written, 13 behind the barrier that opens the sweep; behind the sweep (14 -> 22): 21 behind the
     barrier of the dC transpose, 19 the cost hand-off has returned (the publishing wave), 22 the wave's stores have completed
-    (kernel exit).  Every stamp costs about 40 cycles itself."""
+    (kernel exit).  The role kernel's forward iteration 50: 9 the iteration starts (the row role leaves the barrier that closed
+    iteration 49), 27 behind the iteration's first barrier, 10 behind its second; in the role that is on the chain between two of
+    these, 23 the other role's duals have arrived (only in builds that form self - c2 off the chain, KCCOT_FWD_TRIM & 8), 24 the
+    line's max is known, 25 its sum, 26 the new dual is written.  Every stamp costs about 40 cycles itself."""
     lib.kccot_sinkhorn_divergence_fused_f32.argtypes = [vp, ci, cf, ci, ci, cf, vp, vp, vp, vp, vp, vp]
     lib.kccot_set_option.argtypes = [ctypes.c_char_p, ci]
     lib.kccot_diag_fused_stamps.argtypes = [vp]
@@ -72,6 +75,14 @@ if FUSED:
                   " | behind the sweep %.0f (to the transpose barrier's exit %.0f, stores completed %.0f) | entry to exit %.0f cycles" % (
                       name, seg(16, 11), seg(11, 12), seg(12, 13), seg(12, 17), seg(17, 20), seg(20, 13), seg(13, 14), seg(14, 22),
                       seg(14, 21), seg(21, 22), seg(16, 22)))
+        if roles:
+            # forward iteration 50 by role: the half-step of the role that is on the chain, and what the other role sees
+            for name, ws, a in (("row waves", list(range(nw // 2)), 9), ("column waves", list(range(nw // 2, nw)), 27)):
+                seg = lambda x, y: float(np.mean(d[:, ws, y] - d[:, ws, x])) if (d[:, ws, x] != 0).all() and (d[:, ws, y] != 0).all() else float("nan")
+                print("  %-12s forward half-step: barrier exit -> duals read %.0f -> max known %.0f (from the barrier exit) -> sum known %.0f -> "
+                      "dual written %.0f -> next barrier exit %.0f | the other role's half-step (barrier to barrier) %.0f cycles" % (
+                          name, seg(a, 23), seg(a, 24), seg(24, 25), seg(25, 26), seg(26, 27 if a == 9 else 10),
+                          seg(27, 10) if a == 9 else seg(9, 27)))
         t0, t1 = d[:, :nw, 16].min(axis=1), d[:, :nw, 22].max(axis=1)
         seg_all = lambda a, b: float(np.mean(d[:, :nw, b].max(axis=1) - d[:, :nw, a].min(axis=1)))
         print("  workgroup    first entry to last exit %.0f cycles: prologue %.0f, forward %.0f, between the loops %.0f, sweep %.0f, behind the sweep %.0f"
