@@ -2,8 +2,10 @@
 // one radius for all three axes): s = A_h(sigma_s, r_s) A_w(sigma_s, r_s) A_t(sigma_t, r_t) x, out = s / max s, its adjoint and
 // the two bandwidth gradients.  Nothing here goes through the dispatch ladder of smooth.hip.
 //
-// aniso_tile: ONE tile walk (the one of dsigma_tile, smooth_sigma.hip) serves the three jobs.  A workgroup owns, of one sample,
-// a tile of tt rows of T, wt columns of W and ct channels, and a segment of hs image rows, and walks along H.  Per plane: the
+// aniso_tile: ONE tile walk (the one of dsigma_tile, smooth_sigma.hip; what the two files share -- the tiling rule tile_plan, the
+// geometry of a plan, the largest-grid search behind the workspace size, REFLECT and tile_combine -- lives in tile_walk.h)
+// serves the three jobs.  A workgroup owns, of one sample, a tile of tt rows of T, wt columns of W and ct channels, and a
+// segment of hs image rows, and walks along H.  Per plane: the
 // piece with its T and W halo goes global -> LDS X (through a table of offsets within a plane, built once) -> T stencil over
 // the piece and its column halo (r_t is a run-time argument: this stage reads LDS only) -> LDS A -> W stencil at the owned
 // positions (NI per thread) -> (2 RS + 1)-deep REGISTER windows per owned position -> H stencil -> the job's epilogue.  RS, the
@@ -20,11 +22,12 @@
 //   JOB_DSIG  three fields, F (smoothed so far), G_t and G_s (differentiated once along T / along H|W):
 //                 T:  F = K_t x, G_t = K'_t x          W:  G_s = K'_w F, F <- K_w F, G_t <- K_w G_t
 //                 H:  dsigma_t element = K_h G_t,      dsigma_s element = K_h G_s + K'_h F
-//             each times u, summed in fp64 per thread; two fp64 partials per workgroup, combined by aniso_combine (one
+//             each times u, summed in fp64 per thread; two fp64 partials per workgroup, combined by tile_combine (one
 //             workgroup, fixed order).  No float atomics anywhere: the same call gives the same bits.
 // Every shape and every (r_t, r_s) in 0..7 x 0..7 finds a tiling (all extents of the tile can shrink to 1): no staged form.
 #include "common.h"
 #include "smooth_internal.h"
+#include "tile_walk.h"
 #include "../../include/kccot_smooth_aniso.h"
 #include <float.h>
 #include <math.h>
@@ -34,7 +37,7 @@ namespace kccot {
 
 namespace {
 
-constexpr int AN_NT = 256;                  // threads of an aniso_tile workgroup
+constexpr int AN_NT = TILE_NT;              // threads of an aniso_tile workgroup
 constexpr size_t AN_LDS_MAX = 56 * 1024;    // dynamic LDS a tiling may take (the static part is 3.2 KB)
 constexpr int AN_TW = 2 * SM_MAXR + 1;      // taps of a table row; the centre tap sits at SM_MAXR
 constexpr int AN_TR = 2 * SM_MAXR + 3;      // rows of a table
@@ -115,19 +118,12 @@ struct AnArgs {
     float* res;             // JOB_FWD: s; JOB_ADJ: din
     float* bmax;            // JOB_FWD: one maximum per workgroup
     double* part;           // JOB_DSIG: two partials per workgroup
-    int H, T, W, C;
-    int tt, wt, ct, hs;     // tile extents along T, W, C and the segment along H
-    int ntt, ntw, ntc, nseg;
+    TileGeom g;
     int rt, tb, ta;         // T radius; halo rows before / after the piece
     int kind_t, halo_t;     // ROW_* of the T table; HALO_* of the T halo (W and H: REFLECT, JOB_ADJ: ZERO)
     float ws[AN_TW], dws[AN_TW];    // JOB_FWD / JOB_DSIG: the uniform spatial taps (centre RS) and their derivative
     AxTab tab[3];           // [0] T;  [1] JOB_DSIG: the derivative T table, JOB_ADJ: W;  [2] JOB_ADJ: H
 };
-
-__device__ __forceinline__ int an_reflect(int p, int len) {
-    p = p < 0 ? -p : (p >= len ? 2 * (len - 1) - p : p);
-    return p < 0 ? 0 : (p > len - 1 ? len - 1 : p);     // (positions only a masked output of a ragged tile asks for)
-}
 
 template <int RS, int NI, int JOB>
 __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
@@ -138,34 +134,35 @@ __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
     constexpr int NW = 2 * RS + 1;
     constexpr bool ADJ = JOB == JOB_ADJ, DSIG = JOB == JOB_DSIG;
     const int tid = threadIdx.x;
+    const TileGeom& G = a.g;
     int blk = blockIdx.x;
-    const int tc = blk % a.ntc; blk /= a.ntc;
-    const int tw = blk % a.ntw; blk /= a.ntw;
-    const int ttile = blk % a.ntt; blk /= a.ntt;
-    const int seg = blk % a.nseg, b = blk / a.nseg;
-    const int t0 = ttile * a.tt, w0 = tw * a.wt, c0 = tc * a.ct, h0 = seg * a.hs, h1 = min(h0 + a.hs, a.H);
-    const int tb = a.tb, ta = a.ta, ct = a.ct, pitch = (a.wt + 2 * RS) * ct, nrx = a.tt + tb + ta;
-    const int nx = nrx * pitch, na = a.tt * pitch;
+    const int tc = blk % G.ntc; blk /= G.ntc;
+    const int tw = blk % G.ntw; blk /= G.ntw;
+    const int ttile = blk % G.ntt; blk /= G.ntt;
+    const int seg = blk % G.nseg, b = blk / G.nseg;
+    const int t0 = ttile * G.tt, w0 = tw * G.wt, c0 = tc * G.ct, h0 = seg * G.hs, h1 = min(h0 + G.hs, G.H);
+    const int tb = a.tb, ta = a.ta, ct = G.ct, pitch = (G.wt + 2 * RS) * ct, nrx = G.tt + tb + ta;
+    const int nx = nrx * pitch, na = G.tt * pitch;
     float* X = an_lds;                                      // nrx x pitch: the plane piece with its halo
     int* xoff = reinterpret_cast<int*>(an_lds + nx);        // its offsets within a plane; -1 = outside the tensor (JOB_ADJ)
     float* A = an_lds + 2 * nx;                             // tt x pitch: F behind the T stage
     float* A1 = A + na;                                     // tt x pitch: G_t behind the T stage (JOB_DSIG)
-    const int64_t P = (int64_t)a.T * a.W * a.C;
+    const int64_t P = (int64_t)G.T * G.W * G.C;
 
     for (int e = tid; e < nx; e += AN_NT) {
         const int row = e / pitch, col = e - row * pitch, wc = col / ct, cc = col - wc * ct;
         const int traw = t0 - tb + row, wraw = w0 - RS + wc;
         int tg, wg;
         bool inside = true;
-        if (a.halo_t == HALO_REFLECT) tg = an_reflect(traw, a.T);
+        if (a.halo_t == HALO_REFLECT) tg = tile_reflect(traw, G.T);
         else {
-            inside = traw >= 0 && traw < a.T;
-            tg = traw < 0 ? 0 : (traw > a.T - 1 ? a.T - 1 : traw);
+            inside = traw >= 0 && traw < G.T;
+            tg = traw < 0 ? 0 : (traw > G.T - 1 ? G.T - 1 : traw);
         }
-        if (ADJ) { inside = inside && wraw >= 0 && wraw < a.W; wg = inside ? wraw : 0; }
-        else wg = an_reflect(wraw, a.W);
-        const int cg = min(c0 + cc, a.C - 1);
-        xoff[e] = (ADJ && !inside) ? -1 : (tg * a.W + wg) * a.C + cg;
+        if (ADJ) { inside = inside && wraw >= 0 && wraw < G.W; wg = inside ? wraw : 0; }
+        else wg = tile_reflect(wraw, G.W);
+        const int cg = min(c0 + cc, G.C - 1);
+        xoff[e] = (ADJ && !inside) ? -1 : (tg * G.W + wg) * G.C + cg;
     }
     for (int i = tid; i < AN_TR * AN_TW; i += AN_NT) {
         tabs[0][i] = (&a.tab[0].t[0][0])[i];
@@ -175,17 +172,17 @@ __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
     // owned positions of the tile: fixed for the whole walk
     int aoff[NI], goff[NI], roww[NI];
     bool ok[NI];
-    const int items = a.tt * a.wt * ct;
+    const int items = G.tt * G.wt * ct;
 #pragma unroll
     for (int n = 0; n < NI; ++n) {
         int i = tid + AN_NT * n;
         const bool in_tile = i < items;
         i = in_tile ? i : 0;
-        const int tr = i / (a.wt * ct), rem = i - tr * (a.wt * ct), wl = rem / ct, cl = rem - wl * ct;
-        ok[n] = in_tile && t0 + tr < a.T && w0 + wl < a.W && c0 + cl < a.C;
+        const int tr = i / (G.wt * ct), rem = i - tr * (G.wt * ct), wl = rem / ct, cl = rem - wl * ct;
+        ok[n] = in_tile && t0 + tr < G.T && w0 + wl < G.W && c0 + cl < G.C;
         aoff[n] = tr * pitch + (wl + RS) * ct + cl;
-        goff[n] = ok[n] ? ((t0 + tr) * a.W + w0 + wl) * a.C + c0 + cl : 0;
-        roww[n] = ADJ ? an_row(w0 + wl, a.W, RS, ROW_BORDER) * AN_TW + SM_MAXR : 0;
+        goff[n] = ok[n] ? ((t0 + tr) * G.W + w0 + wl) * G.C + c0 + cl : 0;
+        roww[n] = ADJ ? an_row(w0 + wl, G.W, RS, ROW_BORDER) * AN_TW + SM_MAXR : 0;
     }
     float m = 1.f, corr = 0.f;
     if (ADJ || DSIG) {
@@ -204,7 +201,7 @@ __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
     float vmax = -FLT_MAX;
     const int q256 = AN_NT / pitch, r256 = AN_NT - q256 * pitch;
     const int ntaps = tb + ta + 1, tap0 = SM_MAXR - tb;
-    const int64_t sample = (int64_t)b * a.H * P;
+    const int64_t sample = (int64_t)b * G.H * P;
     for (int hp = h0 - RS; hp < h1 + RS; ++hp) {
         const int hout = hp - RS;                   // the plane this step completes
         // JOB_DSIG: its gout / out, issued first, needed last
@@ -219,10 +216,10 @@ __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
                 }
             }
         }
-        const bool plane = !ADJ || (hp >= 0 && hp < a.H);       // JOB_ADJ: u is zero outside the tensor (uniform)
+        const bool plane = !ADJ || (hp >= 0 && hp < G.H);       // JOB_ADJ: u is zero outside the tensor (uniform)
         float fv[NI], tv[DSIG ? NI : 1], sv[DSIG ? NI : 1];
         if (plane) {
-            const int64_t base = sample + (int64_t)(ADJ ? hp : an_reflect(hp, a.H)) * P;
+            const int64_t base = sample + (int64_t)(ADJ ? hp : tile_reflect(hp, G.H)) * P;
             __syncthreads();                        // the tables (first step); the T stage of the step before has read X
             if (ADJ) {
                 const float* gp = a.gout + base;
@@ -240,7 +237,7 @@ __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
             {
                 int row = tid / pitch, col = tid - row * pitch;
                 for (int e = tid; e < na; e += AN_NT) {
-                    const int tr = an_row(t0 + row, a.T, a.rt, a.kind_t) * AN_TW + tap0;
+                    const int tr = an_row(t0 + row, G.T, a.rt, a.kind_t) * AN_TW + tap0;
                     const float* c = X + e;
                     float f = 0.f, g = 0.f;
                     for (int k = 0; k < ntaps; ++k) {
@@ -281,7 +278,7 @@ __global__ __launch_bounds__(AN_NT) void aniso_tile(AnArgs a) {
             for (int n = 0; n < NI; ++n) fv[n] = 0.f;
         }
         // ---- the H windows and the H stencil
-        const int rowh = ADJ ? an_row(hout, a.H, RS, ROW_BORDER) * AN_TW + SM_MAXR - RS : 0;
+        const int rowh = ADJ ? an_row(hout, G.H, RS, ROW_BORDER) * AN_TW + SM_MAXR - RS : 0;
 #pragma unroll
         for (int n = 0; n < NI; ++n) {
             if constexpr (RS > 0) {
@@ -346,22 +343,6 @@ __global__ __launch_bounds__(256) void aniso_divide(float* __restrict__ out, int
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) out[e] = out[e] / m;
 }
 
-// one workgroup: thread i adds the partials of workgroups i, i + 1024, .. in that order, then a fixed tree; a component whose
-// axis group has radius 0 is written as 0
-__global__ __launch_bounds__(1024) void aniso_combine(const double* __restrict__ part, int64_t nparts, int has_t, int has_s,
-                                                      float* __restrict__ res) {
-    __shared__ double red[2][1024];
-    double s0 = 0.0, s1 = 0.0;
-    for (int64_t i = threadIdx.x; i < nparts; i += 1024) { s0 += part[2 * i]; s1 += part[2 * i + 1]; }
-    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) { red[0][threadIdx.x] += red[0][threadIdx.x + w]; red[1][threadIdx.x] += red[1][threadIdx.x + w]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { res[0] = has_t ? (float)red[0][0] : 0.f; res[1] = has_s ? (float)red[1][0] : 0.f; }
-}
-
 // The two batch sums of the normalisation's adjoint, {sum gout*out, #(out == 1)}, taken PER SAMPLE and then added over the
 // samples in fp32 in sample order.  smooth_maxnorm_stats cuts the flat tensor into blocks that straddle samples and rounds once
 // at the end, so the sums of two shards added on the host differ from its one-call sum in the last bit, and with them every din
@@ -423,59 +404,17 @@ __global__ __launch_bounds__(256) void aniso_stats_total(const float* __restrict
 }
 
 // ---- the tiling ----------------------------------------------------------------------------------------------------------------
-struct AnPlan { int tt, wt, ct, hs, ni; size_t lds; int64_t grid; bool ok; };
-
 // owned positions per thread, one of 1, 2, 4, 8: a position costs a window of 2 rs + 1 registers, JOB_DSIG three of them, so
 // NI falls as rs grows (JOB_DSIG: 3 NI (2 rs + 1) <= 90; JOB_FWD: NI (2 rs + 1) <= 60).  JOB_ADJ keeps JOB_DSIG's limits: with
 // 8 positions at rs = 3 (a per-position tap row and two loads per halo element on top of the window) it measured 1.5 times
 // SLOWER at configs[3] than with 4.
 constexpr int an_max_ni(int rs, int job) { return job == JOB_FWD ? (rs <= 3 ? 8 : 4) : (rs <= 1 ? 8 : (rs <= 3 ? 4 : 2)); }
 
-AnPlan an_plan(int B, int H, int T, int W, int C, int rt, int rs, bool causal, int job) {
-    AnPlan best{};
-    double best_cost = 1e300;
-    // the halo rows of T: symmetric both sides; causal behind the piece (forward, dsigma) or ahead of it (adjoint)
+// what tile_plan (tile_walk.h) searches for a job: the raw shape; the halo rows of T symmetric both sides, causal behind the
+// piece (forward, dsigma) or ahead of it (adjoint); a second field behind the T stage for JOB_DSIG
+TileSearch an_search(int B, int H, int T, int W, int C, int rt, int rs, bool causal, int job) {
     const int tb = causal ? (job == JOB_ADJ ? 0 : rt) : rt, ta = causal ? (job == JOB_ADJ ? rt : 0) : rt;
-    const int64_t max_items = (int64_t)an_max_ni(rs, job) * AN_NT;
-    // halving cuts of every extent; the first (largest) tile of equal cost wins
-    for (int ct = C;; ct = (ct + 1) / 2) {
-        for (int wt = W;; wt = (wt + 1) / 2) {
-            for (int tt = T;; tt = (tt + 1) / 2) {
-                const int64_t items = (int64_t)tt * wt * ct;
-                const int64_t pitch = (int64_t)(wt + 2 * rs) * ct;
-                const int64_t lds = (2 * (int64_t)(tt + tb + ta) * pitch + (job == JOB_DSIG ? 2 : 1) * (int64_t)tt * pitch) * 4;
-                if (items <= max_items && lds <= (int64_t)AN_LDS_MAX) {
-                    int ni = 1;
-                    while ((int64_t)ni * AN_NT < items) ni *= 2;
-                    const int64_t ntile = (int64_t)((T + tt - 1) / tt) * ((W + wt - 1) / wt) * ((C + ct - 1) / ct);
-                    for (int hs = H;; hs = (hs + 1) / 2) {
-                        const int nseg = (H + hs - 1) / hs;
-                        const int64_t grid = (int64_t)B * nseg * ntile;
-                        // reads per owned element: the three halos; the ragged last tiles and the idle lanes of a tile that
-                        // does not fill its NI x 256 positions; a channel cut leaves ct of every C consecutive floats useful
-                        const double ragged = (double)ntile * (double)items * nseg * hs / ((double)T * W * C * H);
-                        const double idle = (double)(ni * AN_NT) / (double)items;
-                        const double strided = (double)(C < 16 ? C : 16) / (double)(ct < 16 ? ct : 16);
-                        const double over = (1.0 + (double)(tb + ta) / tt) * (1.0 + 2.0 * rs / wt) * (1.0 + 2.0 * rs / hs) * ragged *
-                                            idle * strided;
-                        // workgroups the chip (256 CUs) should see: two per CU where a shorter segment costs halo planes,
-                        // eight where it costs nothing (the choice of smooth_sigma.hip)
-                        const double fill = (double)grid / (rs ? 512.0 : 2048.0);
-                        const double cost = over * (fill >= 1.0 ? 1.0 : 1.0 / fill);
-                        if (cost < best_cost && grid <= 0x7fffffff) {
-                            best_cost = cost;
-                            best = AnPlan{tt, wt, ct, hs, ni, (size_t)lds, grid, true};
-                        }
-                        if (hs == 1) break;
-                    }
-                }
-                if (tt == 1) break;
-            }
-            if (wt == 1) break;
-        }
-        if (ct == 1) break;
-    }
-    return best;
+    return TileSearch{B, H, T, W, C, tb, ta, rs, rs, (int64_t)an_max_ni(rs, job) * AN_NT, job == JOB_DSIG ? 2 : 1, AN_LDS_MAX, true};
 }
 
 // Workspace: [16 bytes per workgroup of the LARGEST grid any (job, r_t, r_s, causal) plan launches at this shape: the block
@@ -486,20 +425,13 @@ struct AnWs {
     size_t part, scal, blk, smp, total;
     int bps;        // workgroups per sample of aniso_stats_partial
     AnWs(int B, int H, int T, int W, int C) {
-        // (the search over every plan is about a million steps: the last shape's answer is kept per thread)
-        static thread_local struct { int key[5]; int64_t g; } last = {{0, 0, 0, 0, 0}, 0};
-        int64_t g = 1;
-        if (last.key[0] == B && last.key[1] == H && last.key[2] == T && last.key[3] == W && last.key[4] == C) g = last.g;
-        else {
+        static thread_local TileGridCache last{};       // (the search over every plan is about a million steps)
+        const int64_t g = tile_largest_grid(last, B, H, T, W, C, [&](auto visit) {
             for (int job = JOB_FWD; job <= JOB_DSIG; ++job)
                 for (int rt = 0; rt <= SM_MAXR; ++rt)
                     for (int rs = 0; rs <= SM_MAXR; ++rs)
-                        for (int causal = 0; causal <= 1; ++causal) {
-                            const AnPlan p = an_plan(B, H, T, W, C, rt, rs, causal != 0, job);
-                            if (p.ok && p.grid > g) g = p.grid;
-                        }
-            last = {{B, H, T, W, C}, g};
-        }
+                        for (int causal = 0; causal <= 1; ++causal) visit(tile_plan(an_search(B, H, T, W, C, rt, rs, causal != 0, job)));
+        });
         const int64_t n = (int64_t)((size_t)B * H * T * W * C);
         part = up256((size_t)g * 2 * sizeof(double));
         scal = 256;
@@ -512,7 +444,7 @@ struct AnWs {
 };
 
 template <int RS, int NI, int JOB>
-int launch_tile_job(const AnPlan& pl, const AnArgs& a, hipStream_t st) {
+int launch_tile_job(const TilePlan& pl, const AnArgs& a, hipStream_t st) {
     if constexpr (NI > an_max_ni(RS, JOB)) return fail(KCCOT_EUNSUPPORTED, "smooth_aniso: no kernel for %d positions per thread at radius_s %d", NI, RS);
     else {
         hipLaunchKernelGGL((aniso_tile<RS, NI, JOB>), dim3((unsigned)pl.grid), dim3(AN_NT), pl.lds, st, a);
@@ -521,14 +453,14 @@ int launch_tile_job(const AnPlan& pl, const AnArgs& a, hipStream_t st) {
 }
 
 template <int RS, int NI>
-int launch_tile_ni(int job, const AnPlan& pl, const AnArgs& a, hipStream_t st) {
+int launch_tile_ni(int job, const TilePlan& pl, const AnArgs& a, hipStream_t st) {
     if (job == JOB_FWD) return launch_tile_job<RS, NI, JOB_FWD>(pl, a, st);
     if (job == JOB_ADJ) return launch_tile_job<RS, NI, JOB_ADJ>(pl, a, st);
     return launch_tile_job<RS, NI, JOB_DSIG>(pl, a, st);
 }
 
 template <int RS>
-int launch_tile_rs(int job, const AnPlan& pl, const AnArgs& a, hipStream_t st) {
+int launch_tile_rs(int job, const TilePlan& pl, const AnArgs& a, hipStream_t st) {
     switch (pl.ni) {
         case 1: return launch_tile_ni<RS, 1>(job, pl, a, st);
         case 2: return launch_tile_ni<RS, 2>(job, pl, a, st);
@@ -634,24 +566,17 @@ int an_check_fwd_flags(const AnCall& c) {
 // does the dsigma entry launch aniso_tile at all (else both results are exactly 0)
 bool an_dsigma_launches(int rt, int rs) { return rt > 0 || rs > 0; }
 
-AnPlan an_plan_of(const AnCall& c, int job) { return an_plan(c.B, c.H, c.T, c.W, c.C, c.rt, c.rs, c.causal(), job); }
-
-// the tile geometry of a plan: what the launch hands the kernel and what kccot_smooth_aniso_plan reports
-void an_geometry(AnArgs& a, const AnCall& c, const AnPlan& pl) {
-    a.H = c.H; a.T = c.T; a.W = c.W; a.C = c.C;
-    a.tt = pl.tt; a.wt = pl.wt; a.ct = pl.ct; a.hs = pl.hs;
-    a.ntt = (c.T + pl.tt - 1) / pl.tt; a.ntw = (c.W + pl.wt - 1) / pl.wt; a.ntc = (c.C + pl.ct - 1) / pl.ct;
-    a.nseg = (c.H + pl.hs - 1) / pl.hs;
-    a.rt = c.rt;
-}
+TileSearch an_search_of(const AnCall& c, int job) { return an_search(c.B, c.H, c.T, c.W, c.C, c.rt, c.rs, c.causal(), job); }
 
 // one walk: the geometry and the tables of the job, the grid checked against its area of the workspace
 int an_walk(const AnCall& c, int job, AnArgs a, const AnAreas& w, int64_t* grid = nullptr) {
-    const AnPlan pl = an_plan_of(c, job);
+    const TileSearch q = an_search_of(c, job);
+    const TilePlan pl = tile_plan(q);
     if (!pl.ok || (size_t)pl.grid * 2 * sizeof(double) > w.lay.part)        // (the layout was sized from this very plan)
         return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radii (%d, %d)", c.who, c.B, c.H, c.T, c.W, c.C, c.rt, c.rs);
     if (grid) *grid = pl.grid;
-    an_geometry(a, c, pl);
+    a.g = tile_geometry(q, pl);
+    a.rt = c.rt;
     const SymD ss = make_sym_d(c.sigma_s, c.rs);
     for (int k = 0; k <= 2 * c.rs; ++k) { a.ws[k] = ss.w[k]; a.dws[k] = ss.dw[k]; }
     if (job == JOB_ADJ) {
@@ -720,11 +645,11 @@ extern "C" int kccot_smooth_aniso_plan(int B, int H, int T, int W, int C, int ra
     if ((rc = an_check_size(c))) return rc;
     for (int k = 0; k < KCCOT_SMOOTH_ANISO_PLAN_INTS; ++k) out[k] = 0;
     if (job == JOB_DSIG && !an_dsigma_launches(radius_t, radius_s)) return 0;
-    const AnPlan pl = an_plan_of(c, job);
+    const TileSearch q = an_search_of(c, job);
+    const TilePlan pl = tile_plan(q);
     if (!pl.ok) return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radii (%d, %d)", c.who, B, H, T, W, C, radius_t, radius_s);
-    AnArgs a{};
-    an_geometry(a, c, pl);
-    const int v[KCCOT_SMOOTH_ANISO_PLAN_INTS] = {1, radius_s, pl.ni, job, a.tt, a.wt, a.ct, a.hs, a.ntt, a.ntw, a.ntc, a.nseg, (int)pl.grid};
+    const TileGeom g = tile_geometry(q, pl);
+    const int v[KCCOT_SMOOTH_ANISO_PLAN_INTS] = {1, radius_s, pl.ni, job, g.tt, g.wt, g.ct, g.hs, g.ntt, g.ntw, g.ntc, g.nseg, (int)pl.grid};
     for (int k = 0; k < KCCOT_SMOOTH_ANISO_PLAN_INTS; ++k) out[k] = v[k];
     return 0;
 }
@@ -802,6 +727,8 @@ extern "C" int kccot_smooth_aniso_dsigma_f32(const float* in, const float* gout,
         a.in = in; a.gout = gout; a.outf = out; a.mx = max_in; a.stats = stats; a.part = w.part();
         if ((rc = an_walk(c, JOB_DSIG, a, w, &nparts))) return rc;
     }
-    hipLaunchKernelGGL(aniso_combine, dim3(1), dim3(1024), 0, c.st, (const double*)w.part(), nparts, radius_t > 0, radius_s > 0, dsigma_out);
-    return launch_status("aniso_combine");
+    // (a component whose axis group has radius 0 is written as 0)
+    hipLaunchKernelGGL(tile_combine<2>, dim3(1), dim3(1024), 0, c.st, (const double*)w.part(), nparts,
+                       (radius_t > 0 ? 1u : 0u) | (radius_s > 0 ? 2u : 0u), dsigma_out);
+    return launch_status("tile_combine");
 }

@@ -1,5 +1,6 @@
 // What smooth.hip, smooth_sigma.hip and smooth_aniso.hip share: the host-side taps of the Gaussian stencils and the two-pass form of the
-// max-normalisation adjoint's batch sums.
+// max-normalisation adjoint's batch sums.  (What the two tile walks of smooth_sigma.hip and smooth_aniso.hip share beyond that --
+// the tiling rule, the geometry of a plan, REFLECT, the combine kernel -- is in tile_walk.h.)
 #pragma once
 #include "common.h"
 #include <math.h>

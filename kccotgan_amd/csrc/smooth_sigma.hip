@@ -17,10 +17,13 @@
 // global memory: `in`, `gout` and `out` are read once, `in` again for the halos ((tt+2R)/tt, (wt+2R)/wt and (hs+2R)/hs of
 // it; R/tt for the causal T).  Every shape finds a tiling (all three extents of the tile can shrink to 1), so there is no
 // staged form.
-// The sum: one fp64 partial per workgroup into the workspace, dsigma_combine (one workgroup, fixed order, fp64) writes the
+// The sum: one fp64 partial per workgroup into the workspace, tile_combine (one workgroup, fixed order, fp64) writes the
 // fp32 result.  No float atomics anywhere: the same call gives the same bits.
+// What this file shares with smooth_aniso.hip lives in tile_walk.h: the tiling rule (tile_plan), the geometry of a plan
+// (TileGeom), the largest-grid search behind the workspace size, REFLECT and tile_combine.
 #include "common.h"
 #include "smooth_internal.h"
+#include "tile_walk.h"
 #include "../../include/kccot_smooth_sigma.h"
 #include <math.h>
 #include <stdint.h>
@@ -29,7 +32,7 @@ namespace kccot {
 
 namespace {
 
-constexpr int DS_NT = 256;                  // threads of a dsigma_tile workgroup
+constexpr int DS_NT = TILE_NT;              // threads of a dsigma_tile workgroup
 constexpr size_t DS_LDS_MAX = 60 * 1024;    // dynamic LDS a tiling may take (the static part is below 1 KB)
 constexpr unsigned DS_AXES = KCCOT_SMOOTH_T | KCCOT_SMOOTH_H | KCCOT_SMOOTH_W;
 
@@ -40,18 +43,11 @@ struct DsArgs {
     const float* mx;        // device scalar: the maximum the forward divided by
     const float* stats;     // {sum gout*out, n_ties}
     double* part;           // one partial per workgroup
-    int H, T, W, C;         // (an axis that is not smoothed may have been merged into its outer neighbour by the host)
-    int tt, wt, ct, hs;     // tile extents along T, W, C and the segment along H
-    int ntt, ntw, ntc, nseg;
+    TileGeom g;             // (an axis that is not smoothed may have been merged into its outer neighbour by the host)
     int doT, doW, doH, causal;
     SymD sd;
     CausD cd;
 };
-
-__device__ __forceinline__ int reflect_clamp(int p, int len) {
-    p = p < 0 ? -p : (p >= len ? 2 * (len - 1) - p : p);
-    return p < 0 ? 0 : (p > len - 1 ? len - 1 : p);     // (positions only a masked output of a ragged tile asks for)
-}
 
 template <int R, int NI>
 __global__ __launch_bounds__(DS_NT) void dsigma_tile(DsArgs a) {
@@ -61,28 +57,29 @@ __global__ __launch_bounds__(DS_NT) void dsigma_tile(DsArgs a) {
     constexpr int NW = 2 * R + 1;
     const int tid = threadIdx.x;
     const bool doT = a.doT, doW = a.doW, doH = a.doH, causal = a.causal;
+    const TileGeom& G = a.g;
     int blk = blockIdx.x;
-    const int tc = blk % a.ntc; blk /= a.ntc;
-    const int tw = blk % a.ntw; blk /= a.ntw;
-    const int ttile = blk % a.ntt; blk /= a.ntt;
-    const int seg = blk % a.nseg, b = blk / a.nseg;
-    const int t0 = ttile * a.tt, w0 = tw * a.wt, c0 = tc * a.ct, h0 = seg * a.hs, h1 = min(h0 + a.hs, a.H);
+    const int tc = blk % G.ntc; blk /= G.ntc;
+    const int tw = blk % G.ntw; blk /= G.ntw;
+    const int ttile = blk % G.ntt; blk /= G.ntt;
+    const int seg = blk % G.nseg, b = blk / G.nseg;
+    const int t0 = ttile * G.tt, w0 = tw * G.wt, c0 = tc * G.ct, h0 = seg * G.hs, h1 = min(h0 + G.hs, G.H);
     const int rw = doW ? R : 0, tbefore = doT ? R : 0, tafter = (doT && !causal) ? R : 0;
-    const int ct = a.ct, pitch = (a.wt + 2 * rw) * ct, nrx = a.tt + tbefore + tafter;
-    const int nx = nrx * pitch, na = a.tt * pitch;
+    const int ct = G.ct, pitch = (G.wt + 2 * rw) * ct, nrx = G.tt + tbefore + tafter;
+    const int nx = nrx * pitch, na = G.tt * pitch;
     float* X = ds_lds;                                      // nrx x pitch: the plane piece with its halo
     int* xoff = reinterpret_cast<int*>(ds_lds + nx);        // its offsets within a plane
     float* A = ds_lds + 2 * nx;                             // tt x pitch: F behind the T stage
     float* A1 = A + na;                                     // tt x pitch: G behind the T stage
-    const int64_t P = (int64_t)a.T * a.W * a.C;
-    const float* inb = a.in + (int64_t)b * a.H * P;
+    const int64_t P = (int64_t)G.T * G.W * G.C;
+    const float* inb = a.in + (int64_t)b * G.H * P;
 
     for (int e = tid; e < nx; e += DS_NT) {
         const int row = e / pitch, col = e - row * pitch, wc = col / ct, cc = col - wc * ct;
         int tg = t0 - tbefore + row;
-        tg = causal ? (tg < 0 ? 0 : (tg > a.T - 1 ? a.T - 1 : tg)) : reflect_clamp(tg, a.T);
-        const int wg = reflect_clamp(w0 - rw + wc, a.W), cg = min(c0 + cc, a.C - 1);
-        xoff[e] = (tg * a.W + wg) * a.C + cg;
+        tg = causal ? (tg < 0 ? 0 : (tg > G.T - 1 ? G.T - 1 : tg)) : tile_reflect(tg, G.T);
+        const int wg = tile_reflect(w0 - rw + wc, G.W), cg = min(c0 + cc, G.C - 1);
+        xoff[e] = (tg * G.W + wg) * G.C + cg;
     }
     if (tid < (SM_MAXR + 1) * (SM_MAXR + 1)) {
         (&cv[0][0])[tid] = (&a.cd.v[0][0])[tid];
@@ -91,16 +88,16 @@ __global__ __launch_bounds__(DS_NT) void dsigma_tile(DsArgs a) {
     // owned positions of the tile: fixed for the whole walk
     int aoff[NI], goff[NI];
     bool ok[NI];
-    const int items = a.tt * a.wt * ct;
+    const int items = G.tt * G.wt * ct;
 #pragma unroll
     for (int n = 0; n < NI; ++n) {
         int i = tid + DS_NT * n;
         const bool in_tile = i < items;
         i = in_tile ? i : 0;
-        const int tr = i / (a.wt * ct), rem = i - tr * (a.wt * ct), wl = rem / ct, cl = rem - wl * ct;
-        ok[n] = in_tile && t0 + tr < a.T && w0 + wl < a.W && c0 + cl < a.C;
+        const int tr = i / (G.wt * ct), rem = i - tr * (G.wt * ct), wl = rem / ct, cl = rem - wl * ct;
+        ok[n] = in_tile && t0 + tr < G.T && w0 + wl < G.W && c0 + cl < G.C;
         aoff[n] = tr * pitch + (wl + rw) * ct + cl;
-        goff[n] = ok[n] ? ((t0 + tr) * a.W + w0 + wl) * a.C + c0 + cl : 0;
+        goff[n] = ok[n] ? ((t0 + tr) * G.W + w0 + wl) * G.C + c0 + cl : 0;
     }
     const float m = a.mx[0];
     const float corr = a.stats[1] > 0.f ? a.stats[0] / (m * a.stats[1]) : 0.f;
@@ -120,11 +117,11 @@ __global__ __launch_bounds__(DS_NT) void dsigma_tile(DsArgs a) {
         for (int n = 0; n < NI; ++n) {
             gv[n] = 0.f; ov[n] = 0.f;
             if (hout >= h0 && ok[n]) {
-                const int64_t o = ((int64_t)b * a.H + hout) * P + goff[n];
+                const int64_t o = ((int64_t)b * G.H + hout) * P + goff[n];
                 gv[n] = a.gout[o]; ov[n] = a.out[o];
             }
         }
-        const float* inp = inb + (int64_t)reflect_clamp(hp, a.H) * P;
+        const float* inp = inb + (int64_t)tile_reflect(hp, G.H) * P;
         __syncthreads();                            // the table (first step); the T stage of the step before has read X
         for (int e = tid; e < nx; e += DS_NT) X[e] = inp[xoff[e]];
         __syncthreads();
@@ -198,20 +195,6 @@ __global__ __launch_bounds__(DS_NT) void dsigma_tile(DsArgs a) {
     if (tid == 0) a.part[blockIdx.x] = (wpart[0] + wpart[1]) + (wpart[2] + wpart[3]);
 }
 
-// one workgroup: thread i adds partials i, i + 1024, .. in that order, then a fixed tree; nparts = 0 writes 0
-__global__ __launch_bounds__(1024) void dsigma_combine(const double* __restrict__ part, int64_t nparts, float* __restrict__ res) {
-    __shared__ double red[1024];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < nparts; i += 1024) s += part[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) res[0] = (float)red[0];
-}
-
 // ---- the tiling ----------------------------------------------------------------------------------------------------------------
 struct DsShape { int B, H, T, W, C; bool doT, doW, doH, causal; };
 
@@ -226,55 +209,14 @@ DsShape ds_shape(int B, int H, int T, int W, int C, unsigned axes, int radius) {
     return s;
 }
 
-struct DsPlan { int tt, wt, ct, hs, ni; size_t lds; int64_t grid; bool ok; };
-
 // owned positions per thread: two windows of 2r+1 registers each, held to ~110 registers
 constexpr int ds_max_ni(int radius) { return radius <= 3 ? 8 : (radius == 4 ? 6 : (radius == 5 ? 5 : 4)); }
 
-DsPlan ds_plan(const DsShape& s, int radius) {
-    DsPlan best{};
-    double best_cost = 1e300;
-    const int rw = s.doW ? radius : 0, rh = s.doH ? radius : 0;
-    const int tb = s.doT ? radius : 0, ta = (s.doT && !s.causal) ? radius : 0;
-    const int64_t max_items = (int64_t)ds_max_ni(radius) * DS_NT;
-    // halving cuts of every extent; the first (largest) tile of equal cost wins
-    for (int ct = s.C;; ct = (ct + 1) / 2) {
-        for (int wt = s.W;; wt = (wt + 1) / 2) {
-            for (int tt = s.T;; tt = (tt + 1) / 2) {
-                const int64_t items = (int64_t)tt * wt * ct;
-                const int64_t pitch = (int64_t)(wt + 2 * rw) * ct;
-                const int64_t lds = (2 * (int64_t)(tt + tb + ta) * pitch + 2 * (int64_t)tt * pitch) * 4;
-                if (items <= max_items && lds <= (int64_t)DS_LDS_MAX) {
-                    const int ni = (int)((items + DS_NT - 1) / DS_NT);
-                    const int64_t ntile = (int64_t)((s.T + tt - 1) / tt) * ((s.W + wt - 1) / wt) * ((s.C + ct - 1) / ct);
-                    for (int hs = s.H;; hs = (hs + 1) / 2) {
-                        const int64_t grid = (int64_t)s.B * ((s.H + hs - 1) / hs) * ntile;
-                        // reads per owned element: the three halos; the ragged last tiles and the idle lanes of a tile that
-                        // does not fill its NI x 256 positions; a channel cut leaves ct of every C consecutive floats useful
-                        const int nseg = (s.H + hs - 1) / hs;
-                        const double ragged = (double)ntile * (double)items * nseg * hs / ((double)s.T * s.W * s.C * s.H);
-                        const double idle = (double)(ni * DS_NT) / (double)items;
-                        const double strided = (double)(s.C < 16 ? s.C : 16) / (double)(ct < 16 ? ct : 16);
-                        const double over = (1.0 + (double)(tb + ta) / tt) * (1.0 + 2.0 * rw / wt) * (1.0 + 2.0 * rh / hs) * ragged *
-                                            idle * strided;
-                        // workgroups per CU (256 CUs) the chip should see: two where a shorter segment costs halo planes, eight
-                        // where it costs nothing (no H window); the measurements are in DESIGN.md section 4.5.3
-                        const double fill = (double)grid / (s.doH ? 512.0 : 2048.0);
-                        const double cost = over * (fill >= 1.0 ? 1.0 : 1.0 / fill);
-                        if (cost < best_cost && grid <= 0x7fffffff) {
-                            best_cost = cost;
-                            best = DsPlan{tt, wt, ct, hs, ni, (size_t)lds, grid, true};
-                        }
-                        if (hs == 1) break;
-                    }
-                }
-                if (tt == 1) break;
-            }
-            if (wt == 1) break;
-        }
-        if (ct == 1) break;
-    }
-    return best;
+// what tile_plan (tile_walk.h) searches for this call: the halo of every smoothed axis, two fields (F and G) behind the T stage
+TileSearch ds_search(const DsShape& s, int radius) {
+    const int rt = s.doT ? radius : 0;
+    return TileSearch{s.B, s.H, s.T, s.W, s.C, rt, s.causal ? 0 : rt, s.doW ? radius : 0, s.doH ? radius : 0,
+                      (int64_t)ds_max_ni(radius) * DS_NT, 2, DS_LDS_MAX, false};
 }
 
 // Workspace: [one fp64 partial per workgroup of the LARGEST grid any (radius, axes) plan launches at this shape]
@@ -282,19 +224,13 @@ DsPlan ds_plan(const DsShape& s, int radius) {
 struct DsWs {
     size_t part, scal, blk, total;
     DsWs(int B, int H, int T, int W, int C) {
-        // (the search over every plan is a few hundred thousand steps: the last shape's answer is kept per thread)
-        static thread_local struct { int key[5]; int64_t g; } last = {{0, 0, 0, 0, 0}, 0};
-        int64_t g = 1;
-        if (last.key[0] == B && last.key[1] == H && last.key[2] == T && last.key[3] == W && last.key[4] == C) g = last.g;
-        else {
+        static thread_local TileGridCache last{};       // (the search over every plan is a few hundred thousand steps)
+        const int64_t g = tile_largest_grid(last, B, H, T, W, C, [&](auto visit) {
             for (int radius = 1; radius <= SM_MAXR; ++radius)
                 for (unsigned axes = 1; axes <= DS_AXES; ++axes)
-                    for (unsigned causal = 0; causal <= ((axes & KCCOT_SMOOTH_T) ? 1u : 0u); ++causal) {
-                        const DsPlan p = ds_plan(ds_shape(B, H, T, W, C, axes | (causal ? KCCOT_SMOOTH_CAUSAL_T : 0u), radius), radius);
-                        if (p.ok && p.grid > g) g = p.grid;
-                    }
-            last = {{B, H, T, W, C}, g};
-        }
+                    for (unsigned causal = 0; causal <= ((axes & KCCOT_SMOOTH_T) ? 1u : 0u); ++causal)
+                        visit(tile_plan(ds_search(ds_shape(B, H, T, W, C, axes | (causal ? KCCOT_SMOOTH_CAUSAL_T : 0u), radius), radius)));
+        });
         const int64_t n = (int64_t)((size_t)B * H * T * W * C);
         part = up256((size_t)g * sizeof(double));
         scal = 256;
@@ -304,7 +240,7 @@ struct DsWs {
 };
 
 template <int R, int NI>
-int launch_tile_ni(const DsPlan& pl, const DsArgs& a, hipStream_t st) {
+int launch_tile_ni(const TilePlan& pl, const DsArgs& a, hipStream_t st) {
     if constexpr (NI > ds_max_ni(R)) return fail(KCCOT_EUNSUPPORTED, "smooth_dsigma: no kernel for %d positions per thread at radius %d", NI, R);
     else {
         hipLaunchKernelGGL((dsigma_tile<R, NI>), dim3((unsigned)pl.grid), dim3(DS_NT), pl.lds, st, a);
@@ -313,7 +249,7 @@ int launch_tile_ni(const DsPlan& pl, const DsArgs& a, hipStream_t st) {
 }
 
 template <int R>
-int launch_tile(const DsPlan& pl, const DsArgs& a, hipStream_t st) {
+int launch_tile(const TilePlan& pl, const DsArgs& a, hipStream_t st) {
     switch (pl.ni) {
         case 1: return launch_tile_ni<R, 1>(pl, a, st);
         case 2: return launch_tile_ni<R, 2>(pl, a, st);
@@ -324,16 +260,6 @@ int launch_tile(const DsPlan& pl, const DsArgs& a, hipStream_t st) {
         case 7: return launch_tile_ni<R, 7>(pl, a, st);
         default: return launch_tile_ni<R, 8>(pl, a, st);
     }
-}
-
-// the tile geometry of a plan in the kernel's view of the shape: what the launch hands the kernel and what
-// kccot_smooth_dsigma_plan reports
-void ds_geometry(DsArgs& a, const DsShape& s, const DsPlan& pl) {
-    a.H = s.H; a.T = s.T; a.W = s.W; a.C = s.C;
-    a.tt = pl.tt; a.wt = pl.wt; a.ct = pl.ct; a.hs = pl.hs;
-    a.ntt = (s.T + pl.tt - 1) / pl.tt; a.ntw = (s.W + pl.wt - 1) / pl.wt; a.ntc = (s.C + pl.ct - 1) / pl.ct;
-    a.nseg = (s.H + pl.hs - 1) / pl.hs;
-    a.doT = s.doT; a.doW = s.doW; a.doH = s.doH; a.causal = s.causal;
 }
 
 // does this call launch dsigma_tile at all (else the result is exactly 0)
@@ -387,12 +313,12 @@ extern "C" int kccot_smooth_dsigma_plan(int B, int H, int T, int W, int C, int r
     for (int k = 0; k < KCCOT_SMOOTH_DSIGMA_PLAN_INTS; ++k) out[k] = 0;
     if (!ds_launches(radius, axes_flags)) return 0;
     const DsShape s = ds_shape(B, H, T, W, C, axes_flags, radius);
-    const DsPlan pl = ds_plan(s, radius);
+    const TileSearch q = ds_search(s, radius);
+    const TilePlan pl = tile_plan(q);
     if (!pl.ok) return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radius %d", who, B, H, T, W, C, radius);
-    DsArgs a{};
-    ds_geometry(a, s, pl);
-    const int v[KCCOT_SMOOTH_DSIGMA_PLAN_INTS] = {1, radius, pl.ni, a.tt, a.wt, a.ct, a.hs, a.ntt, a.ntw, a.ntc, a.nseg, (int)pl.grid,
-                                                  s.B, a.H, a.T, a.W, a.C};
+    const TileGeom g = tile_geometry(q, pl);
+    const int v[KCCOT_SMOOTH_DSIGMA_PLAN_INTS] = {1, radius, pl.ni, g.tt, g.wt, g.ct, g.hs, g.ntt, g.ntw, g.ntc, g.nseg, (int)pl.grid,
+                                                  s.B, g.H, g.T, g.W, g.C};
     for (int k = 0; k < KCCOT_SMOOTH_DSIGMA_PLAN_INTS; ++k) out[k] = v[k];
     return 0;
 }
@@ -430,12 +356,14 @@ extern "C" int kccot_smooth_dsigma_f32(const float* in, const float* gout, const
             stats = scal;
         }
         const DsShape s = ds_shape(B, H, T, W, C, axes_flags, radius);
-        const DsPlan pl = ds_plan(s, radius);
+        const TileSearch q = ds_search(s, radius);
+        const TilePlan pl = tile_plan(q);
         if (!pl.ok || (size_t)pl.grid * sizeof(double) > lay.part)      // (the layout was sized from this very plan)
             return fail(KCCOT_EUNSUPPORTED, "%s: no tiling for [%d,%d,%d,%d,%d] at radius %d", who, B, H, T, W, C, radius);
         DsArgs a{};
         a.in = in; a.gout = gout; a.out = out; a.mx = max_in; a.stats = stats; a.part = part;
-        ds_geometry(a, s, pl);
+        a.g = tile_geometry(q, pl);
+        a.doT = s.doT; a.doW = s.doW; a.doH = s.doH; a.causal = s.causal;
         a.sd = make_sym_d(sigma, radius);
         if (s.causal) a.cd = make_caus_d(sigma, radius);
         switch (radius) {
@@ -450,6 +378,6 @@ extern "C" int kccot_smooth_dsigma_f32(const float* in, const float* gout, const
         if (rc) return rc;
         nparts = pl.grid;
     }
-    hipLaunchKernelGGL(dsigma_combine, dim3(1), dim3(1024), 0, st, (const double*)part, nparts, dsigma_out);
-    return launch_status("dsigma_combine");
+    hipLaunchKernelGGL(tile_combine<1>, dim3(1), dim3(1024), 0, st, (const double*)part, nparts, 1u, dsigma_out);
+    return launch_status("tile_combine");
 }

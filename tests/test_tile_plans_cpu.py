@@ -137,9 +137,13 @@ def test_the_restated_switches_and_limits_are_those_of_the_sources():
 def test_each_planner_rule_exists_once_and_the_queries_call_it():
     texts = {n: _src(n) for n in os.listdir(CSRC) if n.endswith((".hip", ".h"))}
     count = lambda needle: sum(t.count(needle) for t in texts.values())
-    for needle in ("DsShape ds_shape(", "DsPlan ds_plan(", "void ds_geometry(", "AnPlan an_plan(", "void an_geometry(", "SsPlan ss_plan(",
-                   "constexpr int ds_max_ni(", "constexpr int an_max_ni("):
+    for needle in ("DsShape ds_shape(", "TilePlan tile_plan(", "TileGeom tile_geometry(", "TileSearch ds_search(", "TileSearch an_search(",
+                   "int64_t tile_largest_grid(", "SsPlan ss_plan(", "constexpr int ds_max_ni(", "constexpr int an_max_ni("):
         assert count(needle) == 1, needle
+    # the cost model of the two smoothing planners stands in the sources once (csrc/tile_walk.h), and both files search through it
+    assert count("ragged * idle") == 1 and count("const double strided") == 1
+    assert "ragged * idle" in texts["tile_walk.h"] and "const double strided" in texts["tile_walk.h"]
+    assert "tile_plan(" in texts["smooth_sigma.hip"] and "tile_plan(" in texts["smooth_aniso.hip"]
 
     def body(text, name):
         start = text.index('extern "C" int %s(' % name)
@@ -147,14 +151,16 @@ def test_each_planner_rule_exists_once_and_the_queries_call_it():
 
     q = body(texts["smooth_sigma.hip"], "kccot_smooth_dsigma_plan")
     e = body(texts["smooth_sigma.hip"] + '\nextern "C"', "kccot_smooth_dsigma_f32")
-    for call in ("ds_check_flags(", "ds_check_dims(", "ds_check_size(", "ds_launches(", "ds_shape(", "ds_plan(", "ds_geometry("):
+    for call in ("ds_check_flags(", "ds_check_dims(", "ds_check_size(", "ds_launches(", "ds_shape(", "ds_search(s, radius)", "tile_plan(q)",
+                 "tile_geometry(q, pl)"):
         assert call in q and call in e, call
     q = body(texts["smooth_aniso.hip"], "kccot_smooth_aniso_plan")
-    for call in ("an_check(", "an_allowed(", "an_check_fwd_flags(", "an_check_size(", "an_dsigma_launches(", "an_plan_of(", "an_geometry("):
+    for call in ("an_check(", "an_allowed(", "an_check_fwd_flags(", "an_check_size(", "an_dsigma_launches(", "an_search_of(c, job)", "tile_plan(q)",
+                 "tile_geometry(q, pl)"):
         assert call in q, call
     walk = texts["smooth_aniso.hip"]
     walk = walk[walk.index("int an_walk("):walk.index("int an_bwd(")]
-    assert "an_plan_of(c, job)" in walk and "an_geometry(a, c, pl)" in walk
+    assert "an_search_of(c, job)" in walk and "tile_plan(q)" in walk and "a.g = tile_geometry(q, pl)" in walk
     q = body(texts["ssim.hip"], "kccot_ssim_plan")
     for call in ("ss_check(", "ss_plan(", "ss_check_index("):
         assert call in q, call
