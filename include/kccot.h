@@ -55,6 +55,11 @@ extern "C" {
                                           /* skipped, the solves run on the given matrices (see below)                  */
 #define KCCOT_COST_RBF_SUM 512u           /* kccot_pairwise_cost_f32: C_out is input AND output -- squared distances    */
                                           /* become exp(-sc * C_out) in place, their fp64 sum goes to ws (see below)    */
+#define KCCOT_COST_L1 1024u               /* kccot_pairwise_cost_f32 / kccot_pairwise_cost3_f32: the ground cost is the */
+                                          /* L1 distance sc * sum_k |x[i,k] - y[j,k]| (an extension: the reference's    */
+                                          /* docstrings name it, its code squares) on the direct-difference kernel; it  */
+                                          /* combines with SAME and FORCE_DIRECT only, every other entry point with     */
+                                          /* cost flags refuses it; adjoint: include/kccot_l1.h                         */
 
 /* Sinkhorn stop modes */
 #define KCCOT_STOP_COUNT 0         /* compute_sinkhorn: stop when err<thresh && nits >= Lmin  */

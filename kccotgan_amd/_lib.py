@@ -1,7 +1,7 @@
 """ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
 ``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h``,
-``include/kccot_smooth_causal3.h``, ``include/kccot_smooth_sigma.h``, ``include/kccot_smooth_aniso.h`` and
-``include/kccot_metrics.h``).
+``include/kccot_smooth_causal3.h``, ``include/kccot_smooth_sigma.h``, ``include/kccot_smooth_aniso.h``,
+``include/kccot_metrics.h`` and ``include/kccot_l1.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -22,6 +22,7 @@ EINVAL, EUNSUPPORTED, EWORKSPACE, EABORTED = -1, -2, -3, -4
 COST_SAME, COST_FORCE_DIRECT, COST_FORCE_MFMA, COST_PARTIAL_ONLY = 1, 2, 4, 8
 COST_GRAM_SUMS_ONLY, COST_FROM_GRAM_SUMS, COST_BICAUSAL_TERM_ONLY = 16, 32, 64
 COST_CAUSAL_ADD, MIXED_CMIX_GIVEN, COST_RBF_SUM = 128, 256, 512
+COST_L1 = 1024            # the L1 ground cost on the direct-difference kernel; with COST_SAME / COST_FORCE_DIRECT only
 STOP_COUNT, STOP_INDEX = 0, 1
 SMOOTH_T, SMOOTH_H, SMOOTH_W, SMOOTH_NO_DIVIDE, SMOOTH_EXTERNAL_MAX = 1, 2, 4, 16, 32
 SMOOTH_STATS_ONLY, SMOOTH_EXTERNAL_STATS = 64, 128
@@ -209,6 +210,16 @@ METRICS_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_l1.h one to one (the adjoint of the L1 ground cost, whose forward is the
+# flag COST_L1 of the two cost entry points: an extension outside the versioned surface of kccot.h)
+L1_SIGNATURES = {
+    "kccot_l1_cost_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "kccot_l1_cost_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i64, _f, _u, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_l1_cost3_bwd_workspace_bytes": (_sz, [_i]),
+    "kccot_l1_cost3_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i64, _f, _fp, _fp, _sz, _fp]),
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -253,7 +264,8 @@ def _load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(MODEL_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) +
                               list(CONDITIONAL_SIGNATURES.items()) + list(WEIGHT_GRAD_SIGNATURES.items()) +
                               list(SMOOTH3C_SIGNATURES.items()) + list(SMOOTH_SIGMA_SIGNATURES.items()) +
-                              list(SMOOTH_ANISO_SIGNATURES.items()) + list(METRICS_SIGNATURES.items())):
+                              list(SMOOTH_ANISO_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) +
+                              list(L1_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

@@ -10,7 +10,8 @@
 //
 // Two partial-tile kernels:
 //   cost_direct_partial : VALU, exact direct-difference form (x-y)^2 as the reference computes
-//                         it (gan_utils.py:16).  Any shape.
+//                         it (gan_utils.py:16).  Any shape.  Its L1 instantiation (KCCOT_COST_L1: |x-y| for (x-y)^2,
+//                         an extension) is the only path of that ground cost; adjoint: cost_l1_bwd.hip.
 //   gram128_partial     : (cost_mfma.hip) stacked-Gram form on the f32 MFMA pipe, for operands
 //                         of at most 64 rows (the BASELINE configs[1] shape).
 #include "common.h"
@@ -47,7 +48,15 @@ __device__ __forceinline__ float4 load4_guard(const float* __restrict__ row, int
     return v;
 }
 
-template <int RA>
+// s += |d| in ONE issue.  The packed fp32 instructions carry a neg modifier but no abs, and hipcc, given fabsf, masks the sign
+// with a v_and_b32 per half and adds packed -- four issues per two pairs; with the differences left packed (v_pk_add_f32) and
+// this add the L1 term costs three, where the squared one (v_pk_add_f32, v_pk_fma_f32) costs two.
+__device__ __forceinline__ void add_abs(float& s, float d) {
+    asm("v_add_f32_e64 %0, %0, |%1|" : "+v"(s) : "v"(d));
+}
+
+// L1: the term of a pair is |x - y| instead of (x - y)^2 (KCCOT_COST_L1); everything else is shared.
+template <int RA, bool L1 = false>
 __global__ __launch_bounds__(256) void cost_direct_partial(CostBatch cb, int64_t K, int64_t chunk,
                                                            int vec_ok) {
     constexpr int TROWS = 16 * RA;
@@ -137,8 +146,15 @@ __global__ __launch_bounds__(256) void cost_direct_partial(CostBatch cb, int64_t
                     const cost_f2 xlo = {xv[a].x, xv[a].y}, xhi = {xv[a].z, xv[a].w};
                     const cost_f2 ylo = {yv[b].x, yv[b].y}, yhi = {yv[b].z, yv[b].w};
                     const cost_f2 d0 = xlo - ylo, d1 = xhi - yhi;
-                    acc[a][b] = __builtin_elementwise_fma(d0, d0, acc[a][b]);
-                    acc[a][b] = __builtin_elementwise_fma(d1, d1, acc[a][b]);
+                    if constexpr (L1) {
+                        float sx = acc[a][b].x, sy = acc[a][b].y;
+                        add_abs(sx, d0.x); add_abs(sy, d0.y);
+                        add_abs(sx, d1.x); add_abs(sy, d1.y);
+                        acc[a][b] = cost_f2{sx, sy};
+                    } else {
+                        acc[a][b] = __builtin_elementwise_fma(d0, d0, acc[a][b]);
+                        acc[a][b] = __builtin_elementwise_fma(d1, d1, acc[a][b]);
+                    }
                 }
         }
         __syncthreads();
@@ -263,8 +279,16 @@ static CostPlan plan_direct(int nprob, const int* Bx, const int* By, const int* 
     return pl;
 }
 
+template <bool L1>
+static void launch_direct_partial(int ra, dim3 grid, hipStream_t st, const CostBatch& cb, int64_t K, int64_t chunk, int vec) {
+    if (ra == 8) hipLaunchKernelGGL((cost_direct_partial<8, L1>), grid, dim3(256), 0, st, cb, K, chunk, vec);
+    else if (ra == 4) hipLaunchKernelGGL((cost_direct_partial<4, L1>), grid, dim3(256), 0, st, cb, K, chunk, vec);
+    else if (ra == 2) hipLaunchKernelGGL((cost_direct_partial<2, L1>), grid, dim3(256), 0, st, cb, K, chunk, vec);
+    else hipLaunchKernelGGL((cost_direct_partial<1, L1>), grid, dim3(256), 0, st, cb, K, chunk, vec);
+}
+
 static int run_direct(CostBatch& cb, int64_t K, float sc, int T, int J, void* ws, size_t ws_bytes,
-                      bool partial_only, hipStream_t st) {
+                      bool partial_only, hipStream_t st, bool l1 = false) {
     int Bx[3], By[3], same[3];
     for (int p = 0; p < cb.nprob; ++p) { Bx[p] = cb.p[p].Bx; By[p] = cb.p[p].By; same[p] = cb.p[p].same; }
     CostPlan pl = plan_direct(cb.nprob, Bx, By, same, K);
@@ -287,10 +311,8 @@ static int run_direct(CostBatch& cb, int64_t K, float sc, int T, int J, void* ws
     for (int p = 0; p < cb.nprob; ++p)
         vec = vec && (((uintptr_t)cb.p[p].x | (uintptr_t)cb.p[p].y) % 16 == 0);
     dim3 grid(pl.nchunk, total_tiles);
-    if (ra == 8) hipLaunchKernelGGL(cost_direct_partial<8>, grid, dim3(256), 0, st, cb, K, pl.chunk, vec ? 1 : 0);
-    else if (ra == 4) hipLaunchKernelGGL(cost_direct_partial<4>, grid, dim3(256), 0, st, cb, K, pl.chunk, vec ? 1 : 0);
-    else if (ra == 2) hipLaunchKernelGGL(cost_direct_partial<2>, grid, dim3(256), 0, st, cb, K, pl.chunk, vec ? 1 : 0);
-    else hipLaunchKernelGGL(cost_direct_partial<1>, grid, dim3(256), 0, st, cb, K, pl.chunk, vec ? 1 : 0);
+    if (l1) launch_direct_partial<true>(ra, grid, st, cb, K, pl.chunk, vec ? 1 : 0);
+    else launch_direct_partial<false>(ra, grid, st, cb, K, pl.chunk, vec ? 1 : 0);
     int rc = launch_status("cost_direct_partial");
     if (rc || partial_only) return rc;
     dim3 fgrid((max_by + CAUSAL_TILE - 1) / CAUSAL_TILE, (max_bx + CAUSAL_TILE - 1) / CAUSAL_TILE, cb.nprob);
@@ -309,6 +331,13 @@ static int run_cost(CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J
                     void* ws, size_t ws_bytes, hipStream_t st) {
     if ((flags & KCCOT_COST_FORCE_DIRECT) && (flags & KCCOT_COST_FORCE_MFMA))
         return fail(KCCOT_EINVAL, "pairwise_cost: FORCE_DIRECT and FORCE_MFMA are exclusive");
+    if (flags & KCCOT_COST_L1) {
+        // |x - y| has no Gram form: the direct-difference kernel is its only path
+        const unsigned with = flags & ~(KCCOT_COST_L1 | KCCOT_COST_SAME | KCCOT_COST_FORCE_DIRECT);
+        if (with)
+            return fail(KCCOT_EINVAL, "pairwise_cost: KCCOT_COST_L1 combines with SAME and FORCE_DIRECT only (other flags 0x%x)", with);
+        return run_direct(cb, K, sc, T, J, ws, ws_bytes, false, st, true);
+    }
     bool mfma;
     if (flags & KCCOT_COST_FORCE_MFMA) {
         if (!gram_eligible(cb, K, loss3))
@@ -346,6 +375,11 @@ extern "C" size_t kccot_pairwise_cost_workspace_bytes(int Bx, int By, int64_t K)
     int same = 0;
     size_t a = plan_direct(1, &Bx, &By, &same, K).ws_bytes;
     size_t b = plan_gram(K).ws_bytes;
+    if (Bx == By) {     // an x == y problem skips tiles and may split K further (the L1 cost takes the direct path at any size)
+        same = 1;
+        const size_t s = plan_direct(1, &Bx, &By, &same, K).ws_bytes;
+        if (s > a) a = s;
+    }
     return a > b ? a : b;
 }
 

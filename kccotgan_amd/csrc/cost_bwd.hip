@@ -1455,6 +1455,8 @@ extern "C" int kccot_pairwise_cost_bwd_f32(const float* g, const float* x, const
     if (!g || !x || !y) return fail(KCCOT_EINVAL, "pairwise_cost_bwd: null pointer");
     if (Bx <= 0 || By <= 0 || K <= 0)
         return fail(KCCOT_EINVAL, "pairwise_cost_bwd: bad shape Bx=%d By=%d K=%lld", Bx, By, (long long)K);
+    if (flags & KCCOT_COST_L1)      // dx / dy here are the squared cost's; the L1 adjoint is kccot_l1_cost_bwd_f32 (kccot_l1.h)
+        return fail(KCCOT_EINVAL, "pairwise_cost_bwd: KCCOT_COST_L1 does not apply: the video gradients of the L1 cost come from kccot_l1_cost_bwd_f32");
     const bool same = (flags & KCCOT_COST_SAME) != 0;
     if (same && (x != y || Bx != By || dy))
         return fail(KCCOT_EINVAL, "pairwise_cost_bwd: KCCOT_COST_SAME needs x == y, Bx == By and dy == NULL");

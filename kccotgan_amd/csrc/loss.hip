@@ -101,6 +101,8 @@ static int loss3_fwd(bool bicausal, const LossArgs& a, int Lmin, float thresh, u
         return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_BICAUSAL_TERM_ONLY does not apply to a loss call");
     if (flags & KCCOT_COST_RBF_SUM)                 // the sharded kernel-MMD's step on a finished distance block
         return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_RBF_SUM does not apply to a loss call");
+    if (flags & KCCOT_COST_L1)                      // the one-call losses differentiate the squared cost only (kccot_l1.h)
+        return fail(KCCOT_EINVAL, "sinkhorn_loss_fwd: KCCOT_COST_L1 does not apply to a loss call (its backward is the squared cost's)");
     int rc = kccot_pairwise_cost3_f32(a.real, a.fake, a.B, a.K, a.sc, a.h_fake, a.h_real, a.m_real, a.m_fake, a.T, a.J, flags,
                                       C3, ws, ws_bytes, stream);
     if (rc) return rc;

@@ -276,8 +276,8 @@ extern "C" int kccot_mixed_sinkhorn_loss_fwd_f32(const float* R, const float* F,
         return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: give u_hist and v_hist together, or dCmix_unit, not both");
     if (dCmix_unit && !ticket) return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the fused path needs the ticket");
     if (flags & (KCCOT_COST_GRAM_SUMS_ONLY | KCCOT_COST_FROM_GRAM_SUMS | KCCOT_COST_BICAUSAL_TERM_ONLY | KCCOT_COST_CAUSAL_ADD |
-                 KCCOT_COST_RBF_SUM))
-        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only / causal-add / RBF_SUM flags do not apply");
+                 KCCOT_COST_RBF_SUM | KCCOT_COST_L1))
+        return fail(KCCOT_EINVAL, "mixed_sinkhorn_loss_fwd: the Gram-sum split / term-only / causal-add / RBF_SUM / L1 flags do not apply");
     hipStream_t st = (hipStream_t)stream;
     void* stage = ws;
     size_t stage_bytes = ws_bytes;

@@ -64,31 +64,36 @@ def _same(x, y):
     return x.data_ptr() == y.data_ptr() and x.shape == y.shape
 
 
+def _pairwise_forward(ctx, x, y, h1, M1, h2, M2, sc, flags):
+    """The forward of _PairwiseCost and _PairwiseCostL1: kccot_pairwise_cost_f32 with `flags` (and COST_SAME when x is y)"""
+    Bx, K = x.shape
+    By = y.shape[0]
+    if y.shape[1] != K:
+        raise ValueError("x and y disagree on the feature count: %d vs %d" % (K, y.shape[1]))
+    T = J = 1
+    for h, M in ((h1, M1), (h2, M2)):
+        if h is not None:
+            if h.shape[0] != Bx or M.shape[0] != By or h.shape[1:] != M.shape[1:]:
+                raise ValueError("h must be [Bx,T,J] and M [By,T,J]; got %s and %s"
+                                 % (tuple(h.shape), tuple(M.shape)))
+            T, J = h.shape[1], h.shape[2]
+    same = _same(x, y)
+    flags = (_lib.COST_SAME if same else 0) | flags
+    C = _lib.empty((Bx, By), torch.float32, x.device)
+    ws, wsb = workspace(lib.kccot_pairwise_cost_workspace_bytes(Bx, By, K), x)
+    check(lib.kccot_pairwise_cost_f32(ptr(x), ptr(y), Bx, By, K, sc, ptr(h1), ptr(M1), ptr(h2), ptr(M2),
+                                      T, J, flags, ptr(C), ws, wsb, stream_of(x)), "pairwise_cost")
+    ctx.save_for_backward(x, y, h1, M1, h2, M2)
+    ctx.sc, ctx.same, ctx.TJ = sc, same, (T, J)
+    return C
+
+
 class _PairwiseCost(torch.autograd.Function):
     """C = cost_xy(x, y) [+ causal(h1, M1)] [+ causal(h2, M2)]   (gan_utils.py:6-72)"""
 
     @staticmethod
     def forward(ctx, x, y, h1, M1, h2, M2, sc):
-        Bx, K = x.shape
-        By = y.shape[0]
-        if y.shape[1] != K:
-            raise ValueError("x and y disagree on the feature count: %d vs %d" % (K, y.shape[1]))
-        T = J = 1
-        for h, M in ((h1, M1), (h2, M2)):
-            if h is not None:
-                if h.shape[0] != Bx or M.shape[0] != By or h.shape[1:] != M.shape[1:]:
-                    raise ValueError("h must be [Bx,T,J] and M [By,T,J]; got %s and %s"
-                                     % (tuple(h.shape), tuple(M.shape)))
-                T, J = h.shape[1], h.shape[2]
-        same = _same(x, y)
-        flags = (_lib.COST_SAME if same else 0) | cost_flags
-        C = _lib.empty((Bx, By), torch.float32, x.device)
-        ws, wsb = workspace(lib.kccot_pairwise_cost_workspace_bytes(Bx, By, K), x)
-        check(lib.kccot_pairwise_cost_f32(ptr(x), ptr(y), Bx, By, K, sc, ptr(h1), ptr(M1), ptr(h2), ptr(M2),
-                                          T, J, flags, ptr(C), ws, wsb, stream_of(x)), "pairwise_cost")
-        ctx.save_for_backward(x, y, h1, M1, h2, M2)
-        ctx.sc, ctx.same, ctx.TJ = sc, same, (T, J)
-        return C
+        return _pairwise_forward(ctx, x, y, h1, M1, h2, M2, sc, cost_flags)
 
     @staticmethod
     def backward(ctx, g):
@@ -124,26 +129,31 @@ class _PairwiseCost(torch.autograd.Function):
         return dx, dy, dh1, dM1, dh2, dM2, None
 
 
+def _cost3_forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc, flags):
+    """The forward of _Cost3 and _Cost3L1: kccot_pairwise_cost3_f32 with `flags`"""
+    B, K = real.shape
+    if fake.shape != real.shape:
+        raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
+    T, J = h_fake.shape[1], h_fake.shape[2]
+    for t in (h_fake, h_real, m_real, m_fake):
+        if tuple(t.shape) != (B, T, J):
+            raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
+    C3 = _lib.empty((3, B, B), torch.float32, real.device)
+    ws, wsb = workspace(lib.kccot_pairwise_cost3_workspace_bytes(B, K), real)
+    check(lib.kccot_pairwise_cost3_f32(ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real), ptr(m_real),
+                                       ptr(m_fake), T, J, flags, ptr(C3), ws, wsb, stream_of(real)),
+          "pairwise_cost3")
+    ctx.save_for_backward(real, fake, h_fake, h_real, m_real, m_fake)
+    ctx.sc = sc
+    return C3
+
+
 class _Cost3(torch.autograd.Function):
     """The three cost matrices of compute_sinkhorn_loss (gan_utils.py:221-223), one pass over the videos."""
 
     @staticmethod
     def forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc):
-        B, K = real.shape
-        if fake.shape != real.shape:
-            raise ValueError("real and fake must have the same shape: %s vs %s" % (tuple(real.shape), tuple(fake.shape)))
-        T, J = h_fake.shape[1], h_fake.shape[2]
-        for t in (h_fake, h_real, m_real, m_fake):
-            if tuple(t.shape) != (B, T, J):
-                raise ValueError("h / M must all be [%d,%d,%d]; got %s" % (B, T, J, tuple(t.shape)))
-        C3 = _lib.empty((3, B, B), torch.float32, real.device)
-        ws, wsb = workspace(lib.kccot_pairwise_cost3_workspace_bytes(B, K), real)
-        check(lib.kccot_pairwise_cost3_f32(ptr(real), ptr(fake), B, K, sc, ptr(h_fake), ptr(h_real), ptr(m_real),
-                                           ptr(m_fake), T, J, cost_flags, ptr(C3), ws, wsb, stream_of(real)),
-              "pairwise_cost3")
-        ctx.save_for_backward(real, fake, h_fake, h_real, m_real, m_fake)
-        ctx.sc = sc
-        return C3
+        return _cost3_forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc, cost_flags)
 
     @staticmethod
     def backward(ctx, g3):
@@ -165,6 +175,89 @@ class _Cost3(torch.autograd.Function):
                                                ptr(m_real), ptr(m_fake), T, J, ptr(dfake), ptr(dhf), ptr(dhr),
                                                ptr(dmr), ptr(dmf), ws, wsb, stream_of(real)), "pairwise_cost3_bwd")
         return None, dfake, dhf, dhr, dmr, dmf, None
+
+
+class _PairwiseCostL1(torch.autograd.Function):
+    """_PairwiseCost with the L1 ground cost sc * sum_k |x[i,k] - y[j,k]| (COST_L1; an extension: the reference's docstrings
+    name this cost, its code squares).  The forward is the direct-difference kernel; the video gradients come from
+    kccot_l1_cost_bwd_f32 (include/kccot_l1.h), the feature gradients -- which do not depend on the ground cost -- from the
+    squared cost's backward called without video outputs."""
+
+    @staticmethod
+    def forward(ctx, x, y, h1, M1, h2, M2, sc):
+        return _pairwise_forward(ctx, x, y, h1, M1, h2, M2, sc, _lib.COST_L1)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, h1, M1, h2, M2 = ctx.saved_tensors
+        g = g.contiguous()
+        Bx, K = x.shape
+        By = y.shape[0]
+        T, J = ctx.TJ
+        need = ctx.needs_input_grad
+        want_x = (need[0] or need[1]) if ctx.same else need[0]
+        want_y = need[1] and not ctx.same
+        dx = _lib.empty_like(x) if want_x else None
+        dy = _lib.empty_like(y) if want_y else None
+        flags = _lib.COST_SAME if ctx.same else 0
+        st = stream_of(x)
+        if dx is not None or dy is not None:
+            ws, wsb = workspace(lib.kccot_l1_cost_bwd_workspace_bytes(Bx, By), x)
+            check(lib.kccot_l1_cost_bwd_f32(ptr(g), ptr(x), ptr(y), Bx, By, K, ctx.sc, flags, ptr(dx), ptr(dy), ws, wsb, st),
+                  "l1_cost_bwd")
+        grads = []
+        for k, (h, M) in enumerate(((h1, M1), (h2, M2))):
+            dh = _lib.empty_like(h) if (h is not None and need[2 + 2 * k]) else None
+            dM = _lib.empty_like(M) if (M is not None and need[3 + 2 * k]) else None
+            if dh is not None or dM is not None:
+                check(lib.kccot_pairwise_cost_bwd_f32(ptr(g), ptr(x), ptr(y), Bx, By, K, ctx.sc, ptr(h), ptr(M), T, J, flags,
+                                                      None, None, ptr(dh), ptr(dM), None, 0, st), "pairwise_cost_bwd")
+            grads += [dh, dM]
+        if ctx.same:
+            # x and y are one tensor: its whole gradient is returned once (autograd would add the two)
+            return ((dx if need[0] else None), (dx if (need[1] and not need[0]) else None), *grads, None)
+        return (dx, dy, *grads, None)
+
+
+class _Cost3L1(torch.autograd.Function):
+    """_Cost3 with the L1 ground cost (COST_L1): one pass of the direct-difference kernel over the three problems; dfake from
+    kccot_l1_cost3_bwd_f32, the feature gradients from kccot_pairwise_cost3_bwd_f32 with dfake = NULL."""
+
+    @staticmethod
+    def forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc):
+        return _cost3_forward(ctx, real, fake, h_fake, h_real, m_real, m_fake, sc, _lib.COST_L1)
+
+    @staticmethod
+    def backward(ctx, g3):
+        real, fake, h_fake, h_real, m_real, m_fake = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("the loss path never differentiates w.r.t. real (kernel_train.py:252,289); "
+                                      "use compute_sinkhorn for a gradient w.r.t. both operands")
+        g3 = g3.contiguous()
+        B, K = real.shape
+        T, J = h_fake.shape[1], h_fake.shape[2]
+        need = ctx.needs_input_grad
+        st = stream_of(real)
+        dfake = _lib.empty_like(fake) if need[1] else None
+        if dfake is not None:
+            ws, wsb = workspace(lib.kccot_l1_cost3_bwd_workspace_bytes(B), real)
+            check(lib.kccot_l1_cost3_bwd_f32(ptr(g3), ptr(real), ptr(fake), B, K, ctx.sc, ptr(dfake), ws, wsb, st), "l1_cost3_bwd")
+        dhf = _lib.empty_like(h_fake) if need[2] else None
+        dhr = _lib.empty_like(h_real) if need[3] else None
+        dmr = _lib.empty_like(m_real) if need[4] else None
+        dmf = _lib.empty_like(m_fake) if need[5] else None
+        if any(d is not None for d in (dhf, dhr, dmr, dmf)):      # (no video output: no workspace)
+            check(lib.kccot_pairwise_cost3_bwd_f32(ptr(g3), ptr(real), ptr(fake), B, K, ctx.sc, ptr(h_fake), ptr(h_real),
+                                                   ptr(m_real), ptr(m_fake), T, J, None, ptr(dhf), ptr(dhr), ptr(dmr),
+                                                   ptr(dmf), None, 0, st), "pairwise_cost3_bwd")
+        return None, dfake, dhf, dhr, dmr, dmf, None
+
+
+def _ground(ground_cost):
+    """True for the L1 ground cost, False for the squared one (the reference's code and the default)."""
+    if ground_cost not in ("l1", "l2"):
+        raise ValueError("ground_cost must be 'l2' (squared distance, the reference's code) or 'l1'; got %r" % (ground_cost,))
+    return ground_cost == "l1"
 
 
 class _Sinkhorn(torch.autograd.Function):
@@ -587,40 +680,47 @@ class _Martingale(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------
 # the reference's public functions
 # ------------------------------------------------------------------------------------------------
-def cost_xy(x, y, scaling_coef):
+def cost_xy(x, y, scaling_coef, *, ground_cost="l2"):
     """gan_utils.py:6-18.  x, y: [batch, time steps, features] -> [batch_x, batch_y] matrix of
-    scaling_coef * squared L2 distance summed over time and features."""
-    return _PairwiseCost.apply(_flat2(x), _flat2(y), None, None, None, None, float(scaling_coef))
+    scaling_coef * squared L2 distance summed over time and features.
+
+    ``ground_cost="l1"`` (keyword-only, not in the reference, here and in the functions below): the sum of absolute
+    differences the reference's docstrings describe instead of the squared distance its code computes."""
+    return (_PairwiseCostL1 if _ground(ground_cost) else _PairwiseCost).apply(
+        _flat2(x), _flat2(y), None, None, None, None, float(scaling_coef))
 
 
-def modified_cost(x, y, h, M, scaling_coef):
+def modified_cost(x, y, h, M, scaling_coef, *, ground_cost="l2"):
     """gan_utils.py:21-43.  cost_xy + scaling_coef * sum_{t<T-1} h[i,t]*(M[j,t+1]-M[j,t]):
     h indexes rows, M indexes columns (gan_utils.py:37)."""
-    return _PairwiseCost.apply(_flat2(x), _flat2(y), _feat(h), _feat(M), None, None, float(scaling_coef))
+    return (_PairwiseCostL1 if _ground(ground_cost) else _PairwiseCost).apply(
+        _flat2(x), _flat2(y), _feat(h), _feat(M), None, None, float(scaling_coef))
 
 
-def bi_causal_modified_cost(x, y, hy, Mx, hx, My, scaling_coef):
+def bi_causal_modified_cost(x, y, hy, Mx, hx, My, scaling_coef, *, ground_cost="l2"):
     """gan_utils.py:46-72.  cost_xy + C_hM(hy, Mx) + C_Mh(hx, My)."""
-    return _PairwiseCost.apply(_flat2(x), _flat2(y), _feat(hy), _feat(Mx), _feat(hx), _feat(My),
-                               float(scaling_coef))
+    return (_PairwiseCostL1 if _ground(ground_cost) else _PairwiseCost).apply(
+        _flat2(x), _flat2(y), _feat(hy), _feat(Mx), _feat(hx), _feat(My), float(scaling_coef))
 
 
 def _solve(C, epsilon, L, Lmin, stop_mode, tag):
     return _Sinkhorn.apply(C.unsqueeze(0), float(epsilon), int(L), int(Lmin), stop_mode, tag)[0]
 
 
-def benchmark_sinkhorn(x, y, scaling_coef, epsilon=1.0, L=10, Lmin=10):
+def benchmark_sinkhorn(x, y, scaling_coef, epsilon=1.0, L=10, Lmin=10, *, ground_cost="l2"):
     """gan_utils.py:75-121.  Sinkhorn on the plain cost_xy; the stop rule tests the loop INDEX
     against Lmin (gan_utils.py:116)."""
-    return _solve(cost_xy(x, y, scaling_coef), epsilon, L, Lmin, _lib.STOP_INDEX, "benchmark_sinkhorn")
+    return _solve(cost_xy(x, y, scaling_coef, ground_cost=ground_cost), epsilon, L, Lmin, _lib.STOP_INDEX,
+                  "benchmark_sinkhorn")
 
 
-def compute_sinkhorn(x, y, hy, Mx, scaling_coef, hx=None, My=None, epsilon=1.0, L=100, bi_causal=False):
+def compute_sinkhorn(x, y, hy, Mx, scaling_coef, hx=None, My=None, epsilon=1.0, L=100, bi_causal=False, *,
+                     ground_cost="l2"):
     """gan_utils.py:124-165.  Lmin = 100 is hard-coded in the reference (gan_utils.py:149)."""
     if bi_causal:
-        C = bi_causal_modified_cost(x, y, hy, Mx, hx, My, scaling_coef)
+        C = bi_causal_modified_cost(x, y, hy, Mx, hx, My, scaling_coef, ground_cost=ground_cost)
     else:
-        C = modified_cost(x, y, hy, Mx, scaling_coef)
+        C = modified_cost(x, y, hy, Mx, scaling_coef, ground_cost=ground_cost)
     return _solve(C, epsilon, L, _LMIN, _lib.STOP_COUNT, "compute_sinkhorn")
 
 
@@ -643,7 +743,7 @@ def _loss_inputs(videos, feats, sinkhorn_eps, sinkhorn_l, honor_eps_l):
 
 
 def compute_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
-                          m_fake, video=True, *, honor_eps_l=False):
+                          m_fake, video=True, *, honor_eps_l=False, ground_cost="l2"):
     """gan_utils.py:204-227: 2*W(real,fake) - W(real,real) - W(fake,fake).
 
     As in the reference, ``sinkhorn_eps`` and ``sinkhorn_l`` are accepted and IGNORED: the
@@ -654,9 +754,18 @@ def compute_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l
 
     ``video=True`` inputs are [B,H,T,W,C]; the reference's transpose(0,2,1,3,4)+reshape
     (gan_utils.py:217-220) does not change a sum over all of (T,H,W,C), so the buffer is read as is.
+
+    ``ground_cost="l1"`` (keyword-only, not in the reference): the three cost matrices carry the L1 distance instead of
+    the squared one; the solves, the combination and what ``last_info`` records are the same.
     """
+    l1 = _ground(ground_cost)
     vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l,
                                        honor_eps_l)
+    if l1:      # the cost stage with COST_L1 and its own adjoint, then the divergence on any cost matrices
+        C3 = _Cost3L1.apply(*vids, *feats, float(scaling_coef))
+        loss = _SinkhornDivergence.apply(C3, eps, L, _LMIN, "compute_sinkhorn_loss")      # counts, executed counts, costs
+        last_info["compute_sinkhorn_loss_C3"], last_info["compute_sinkhorn_loss_fused_sweep"] = C3.detach(), False
+        return loss
     # one library call each way; equivalent to _Cost3 (C3 = [xy, xx, yy]) followed by _SinkhornDivergence
     return _SinkhornLoss.apply(_ONE_BATCH, "compute_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats,
                                None, None)
@@ -695,7 +804,7 @@ def compute_mixed_sinkhorn_loss(f_real, f_fake, f_real_p, f_fake_p, scaling_coef
 
 
 def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, sinkhorn_l, h_fake, m_real, h_real,
-                                   m_fake, video=True, *, honor_eps_l=False):
+                                   m_fake, video=True, *, honor_eps_l=False, ground_cost="l2"):
     """Bi-causal Sinkhorn loss, 2 W(x,y) - W(x,x) - W(y,y) with W = compute_sinkhorn(..., bi_causal=True)
     (gan_utils.py:124-136) and x = real, y = fake:
 
@@ -710,8 +819,11 @@ def compute_bicausal_sinkhorn_loss(f_real, f_fake, scaling_coef, sinkhorn_eps, s
     ``honor_eps_l=True`` applies them.  Differentiable w.r.t. the fake videos and all four features; a real video that
     requires a gradient raises NotImplementedError.  Records last_info["compute_bicausal_sinkhorn_loss"] (the three
     reference-equivalent iteration counts), ``..._executed``, ``..._costs`` [3], ``..._C3`` [3,B,B] and
-    ``..._fused_sweep``.
+    ``..._fused_sweep``.  ``ground_cost`` is here because the parameter list is compute_sinkhorn_loss's: only "l2" runs, the
+    bi-causal loss has no L1 form ("l1" raises NotImplementedError).
     """
+    if _ground(ground_cost):
+        raise NotImplementedError("compute_bicausal_sinkhorn_loss has no L1 form; ground_cost='l1' is compute_sinkhorn_loss's")
     vids, feats, eps, L = _loss_inputs((f_real, f_fake), (h_fake, h_real, m_real, m_fake), sinkhorn_eps, sinkhorn_l,
                                        honor_eps_l)
     return _SinkhornLoss.apply(_BICAUSAL, "compute_bicausal_sinkhorn_loss", float(scaling_coef), eps, L, _LMIN, *vids, *feats,

@@ -17,7 +17,8 @@ each rank holds the partial derivative through its own samples).  ``bi_causal=Tr
 refused: the loss itself has a batch-sharded form (``dist.sharded_mixed_sinkhorn_loss``, ``dist.sharded_mixed_loss_step``),
 but the trainer does not call it yet -- its second real minibatch and the eight differentiated shards are not wired.
 ``conditional_bandwidth`` (the kernel-conditional loss, an extension) is single-process only: neither the weighted nor the
-conditional loss has a batch-sharded form.
+conditional loss has a batch-sharded form.  ``ground_cost="l1"`` (the L1 transport cost the reference's docstrings describe, an
+extension; ``"l2"``, the squared distance its code computes, is the default) runs the one-batch loss only, single-process.
 
 ``sample`` is the test-time autoregressive loop (kernel_train.py:340-347), ``fit`` the loop body around the two
 steps (:295-330): per-iteration sigma (annealed or fixed, :308-311), the scalar log ``pM`` / ``Sinkhorn Loss``
@@ -93,7 +94,8 @@ class KCCOTTrainer:
                  g_state_size=8, d_state_size=8, g_filter_size=8, d_filter_size=8, z_channels=128, bn=True,
                  lr=5e-4, warmup=10000, sinkhorn_eps=0.8, sinkhorn_l=100, scaling_coef=15.0, reg_penalty=1.0,
                  kernel="none", device="cuda", seed=1, group=None, mixed_sinkhorn=False,
-                 bi_causal=False, conditional_bandwidth=None, temporal_kernel_size=6, spatial_kernel_size=6):
+                 bi_causal=False, conditional_bandwidth=None, ground_cost="l2", temporal_kernel_size=6,
+                 spatial_kernel_size=6):
         # defaults = kernel_train.py:363-409
         # mixed_sinkhorn=True: the loss is COT-GAN's mixed Sinkhorn divergence over two minibatches
         # (gan_utils.compute_mixed_sinkhorn_loss) -- what the reference's --mixed_sinkhorn flag (:393) names but never runs
@@ -124,6 +126,17 @@ class KCCOTTrainer:
                                           "dist.sharded_sinkhorn_loss, sharded_mixed_sinkhorn_loss and "
                                           "sharded_bicausal_sinkhorn_loss; the weighted and the conditional loss have no "
                                           "sharded form")
+        # ground_cost="l1" (EXTENSION, not in the reference's code): the transport cost is the L1 distance the reference's
+        # docstrings describe (gan_utils.compute_sinkhorn_loss(..., ground_cost="l1")); "l2" is the squared distance it computes
+        if ground_cost not in ("l1", "l2"):
+            raise ValueError("ground_cost must be 'l2' or 'l1' (got %r)" % (ground_cost,))
+        if ground_cost == "l1":
+            if mixed_sinkhorn or bi_causal or conditional_bandwidth is not None:
+                raise ValueError("ground_cost='l1' is exclusive with mixed_sinkhorn=True, bi_causal=True and "
+                                 "conditional_bandwidth: those losses have no L1 form")
+            if data_parallel:
+                raise NotImplementedError("ground_cost='l1' with data parallelism: the batch-sharded losses have no L1 form")
+        self.ground_cost = ground_cost
         self.conditional_bandwidth = None if conditional_bandwidth is None else float(conditional_bandwidth)
         self.mixed_sinkhorn = bool(mixed_sinkhorn)
         self.bi_causal = bool(bi_causal)
@@ -202,7 +215,8 @@ class KCCOTTrainer:
                                             group=self.group)
         else:
             loss = gan_utils.compute_sinkhorn_loss(real.detach(), fake, self.scaling_coef, self.sinkhorn_eps,
-                                                   self.sinkhorn_l, h_fake, m_real, h_real, m_fake, video=True)  # :247
+                                                   self.sinkhorn_l, h_fake, m_real, h_real, m_fake, video=True,  # :247
+                                                   ground_cost=self.ground_cost)
         return loss, m_real
 
     def _smooth(self, v, sigma):
