@@ -338,6 +338,9 @@ static int run_cost(CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J
             return fail(KCCOT_EINVAL, "pairwise_cost: KCCOT_COST_L1 combines with SAME and FORCE_DIRECT only (other flags 0x%x)", with);
         return run_direct(cb, K, sc, T, J, ws, ws_bytes, false, st, true);
     }
+    // the loss's paths with a Gram-sum split: gs says which one the batch takes (the span query reports the same one's sums)
+    const bool al = ((uintptr_t)cb.p[0].x % 16 == 0) && ((uintptr_t)cb.p[0].y % 16 == 0);
+    const GramSplit gs = loss3 ? gram_split(cb.p[0].Bx, K) : GramSplit{};
     bool mfma;
     if (flags & KCCOT_COST_FORCE_MFMA) {
         if (!gram_eligible(cb, K, loss3))
@@ -347,7 +350,7 @@ static int run_cost(CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J
     } else if (flags & KCCOT_COST_FORCE_DIRECT) {
         mfma = false;
     } else {
-        mfma = gram_preferred(cb, K, loss3);
+        mfma = loss3 ? (gs.path == GRAM_PATH_STACK64 && al) : gram_preferred(cb, K, false);
     }
     const bool partial_only = (flags & KCCOT_COST_PARTIAL_ONLY) != 0;
     // split at the fp64 Gram sums for the contraction-sharded caller (include/kccot.h)
@@ -355,14 +358,22 @@ static int run_cost(CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J
     if (stage && (partial_only || (flags & KCCOT_COST_FORCE_DIRECT) || !loss3))
         return fail(KCCOT_EINVAL, "pairwise_cost: the Gram-sum split applies to kccot_pairwise_cost3_f32 on the Gram paths only");
     if (mfma) return run_gram(cb, loss3, K, sc, T, J, ws, ws_bytes, partial_only, st, stage);
-    if (!(flags & KCCOT_COST_FORCE_DIRECT) && !partial_only && gram_q256_eligible(cb, K, loss3))
-        return run_gram_q256(cb, K, sc, T, J, ws, ws_bytes, st, stage);
-    if (!(flags & KCCOT_COST_FORCE_DIRECT) && !partial_only && gram_tiled_eligible(cb, K, loss3))
-        return run_gram_tiled(cb, K, sc, T, J, ws, ws_bytes, st, stage);
+    const bool tiles = !(flags & KCCOT_COST_FORCE_DIRECT) && !partial_only;
+    if (tiles && al && gs.path == GRAM_PATH_TILE256) return run_gram_q256(cb, K, sc, T, J, ws, ws_bytes, st, stage);
+    if (tiles && al && gs.path == GRAM_PATH_TILE128) return run_gram_tiled(cb, K, sc, T, J, ws, ws_bytes, st, stage);
     if (stage) return fail(KCCOT_EUNSUPPORTED, "pairwise_cost3: no Gram path for B=%d K=%lld (Gram-sum split)", cb.p[0].Bx, (long long)K);
-    if (!(flags & KCCOT_COST_FORCE_DIRECT) && !partial_only && gram_blocked_eligible(cb, K, loss3))
-        return run_gram_blocked(cb, K, sc, T, J, ws, ws_bytes, st);
+    if (tiles && gram_blocked_eligible(cb, K, loss3)) return run_gram_blocked(cb, K, sc, T, J, ws, ws_bytes, st);
     return run_direct(cb, K, sc, T, J, ws, ws_bytes, partial_only, st);
+}
+
+// Which of the paths with a Gram-sum split the loss's (B, K) takes under the current options, in the order of preference:
+// the stack of 64 + 64 rows (B <= 64), 256-row tiles, 128-row tiles; none: the blocked form or the direct kernel, no split.
+GramSplit gram_split(int B, int64_t K) {
+    GramSplit s{};
+    if (B <= 0 || K <= 0) return s;
+    if ((s = gram_stack64_split(B, K)).path) return s;
+    if ((s = gram_q256_split(B, K)).path) return s;
+    return gram_tiled_split(B, K);
 }
 
 }  // namespace kccot
@@ -447,12 +458,8 @@ extern "C" size_t kccot_pairwise_cost3_workspace_bytes(int B, int64_t K) {
 
 extern "C" int kccot_pairwise_cost3_gram_sums_span(int B, int64_t K, size_t* byte_offset, size_t* n_doubles) {
     if (!byte_offset || !n_doubles) return fail(KCCOT_EINVAL, "gram_sums_span: null pointer");
-    *byte_offset = 0; *n_doubles = 0;
-    if (B <= 0 || K <= 0 || K % 4 != 0 || K < 256) return 0;
-    const bool x3 = !opt(OPT_GRAM_F32);
-    if (B <= 64) gram_sums_span(B, K, byte_offset, n_doubles);
-    else if (gram_q256_applies(B, K)) gram_q256_sums_span(B, K, byte_offset, n_doubles);
-    else if (x3 && B % 128 == 0 && B <= 4096 && opt(OPT_COST_TILED)) gram_tiled_sums_span(B, K, byte_offset, n_doubles);
+    const GramSplit s = gram_split(B, K);
+    *byte_offset = s.sums_off; *n_doubles = s.sums_n;
     return 0;
 }
 

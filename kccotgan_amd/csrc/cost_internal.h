@@ -1,5 +1,7 @@
-// Internal descriptors shared by cost.hip (direct-difference path + dispatch) and
-// cost_mfma.hip (stacked-Gram f32-MFMA path).
+// Internal descriptors and entry points of the cost assembly: cost.hip (direct-difference path, dispatch and the C ABI),
+// cost_mfma.hip (the stack of 64 + 64 rows and its blocked form), cost_tiled.hip / cost_tile256.hip (the stack in pairs of
+// 128- / 256-row panels), cost_rows.hip (a batch-sharded rank's row block) and the backward files, which use the causal
+// tile and the video-gradient launch declared here.  What the Gram paths' tails share is in gram_tail.h.
 #pragma once
 #include "common.h"
 
@@ -123,25 +125,31 @@ enum GramMode {
     GRAM_SAME = 2,    // src1 = x rows 0..63, src2 = x rows 64..127; output xx (symmetric)
 };
 
+// The loss's paths that split at the fp64 Gram sums (KCCOT_COST_GRAM_SUMS_ONLY / KCCOT_COST_FROM_GRAM_SUMS).  gram_split
+// (cost.hip) is the ONE place that says which of them a batch takes under the current options; the dispatch (run_cost) and
+// kccot_pairwise_cost3_gram_sums_span, at whose answer the all-reducing caller reads the workspace, both ask it.  Pointer
+// alignment is not part of it: run_cost checks it at call time.  Each path's *_split answers for that path alone (path
+// GRAM_PATH_NONE: the shape does not take it) and reports where its sums sit: byte offset, number of doubles.
+enum GramPath { GRAM_PATH_NONE = 0, GRAM_PATH_STACK64, GRAM_PATH_TILE256, GRAM_PATH_TILE128 };
+struct GramSplit { GramPath path; size_t sums_off, sums_n; };
+GramSplit gram_split(int B, int64_t K);
+GramSplit gram_stack64_split(int B, int64_t K);
+GramSplit gram_q256_split(int B, int64_t K);
+GramSplit gram_tiled_split(int B, int64_t K);
+
 bool gram_eligible(const CostBatch& cb, int64_t K, bool loss3);
 bool gram_preferred(const CostBatch& cb, int64_t K, bool loss3);
 GramPlan plan_gram(int64_t K);
 int run_gram(const CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J, void* ws,
              size_t ws_bytes, bool partial_only, hipStream_t st, int stage = 0);
 // cost_tiled.hip: batches that are multiples of 128 -- one Gram of the [real ; fake - real] stack in 128 x 128 tiles
-bool gram_tiled_eligible(const CostBatch& cb, int64_t K, bool loss3);
 size_t gram_tiled_workspace_bytes(int B, int64_t K);
 int run_gram_tiled(const CostBatch& cb, int64_t K, float sc, int T, int J, void* ws, size_t ws_bytes, hipStream_t st,
                    int stage = 0);
-void gram_tiled_sums_span(int B, int64_t K, size_t* off, size_t* n);
-void gram_sums_span(int B, int64_t K, size_t* off, size_t* n);
 // cost_tile256.hip: batches that are multiples of 256 -- the same Gram in 256 x 256 tiles, E written as a by-product
-bool gram_q256_applies(int B, int64_t K);
-bool gram_q256_eligible(const CostBatch& cb, int64_t K, bool loss3);
 size_t gram_q256_workspace_bytes(int B, int64_t K);
 int run_gram_q256(const CostBatch& cb, int64_t K, float sc, int T, int J, void* ws, size_t ws_bytes, hipStream_t st,
                   int stage = 0);
-void gram_q256_sums_span(int B, int64_t K, size_t* off, size_t* n);
 bool gram_blocked_eligible(const CostBatch& cb, int64_t K, bool loss3);
 // cost_bwd_q256.hip: the video gradient on 256 x 256 output tiles (W panel through LDS)
 bool apply_q256_applies(int Bout, int n1, int n2, int64_t K);

@@ -26,6 +26,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include "cost_internal.h"
+#include "gram_tail.h"
 #include "options.h"
 #include "bf16x3.h"
 
@@ -641,19 +642,14 @@ __device__ __forceinline__ void gram_finalize_body(const GramFin& f) {
         const double e_ii = gram_at<COMPACT>(G, 64 + ii, 64 + ii), e_jj = gram_at<COMPACT>(G, 64 + jj, 64 + jj), e_ij = gram_at<COMPACT>(G, 64 + ii, 64 + jj);
         const double x_ii = gram_at<COMPACT>(G, ii, 64 + ii), x_jj = gram_at<COMPACT>(G, jj, 64 + jj);
         const double x_ij = gram_at<COMPACT>(G, ii, 64 + jj), x_ji = gram_at<COMPACT>(G, jj, 64 + ii);
-        const bool diag = ii == jj;
-        const double dxx = diag ? 0.0 : g_ii + g_jj - 2.0 * g_ij;
-        const double dxy = dxx + e_jj - 2.0 * (x_ij - x_jj);
-        const double dee = e_ii + e_jj - 2.0 * e_ij;
-        const double dyy = diag ? 0.0 : dxx + dee + 2.0 * (x_ii - x_ij - x_ji + x_jj);
-        D = (p == 1) ? dxx : (p == 0 ? dxy : dyy);
+        D = gram_loss_distance_raw(p, ii == jj, g_ii, g_jj, g_ij, e_ii, e_jj, e_ij, x_ii, x_jj, x_ij, x_ji);
     } else if (f.mode == GRAM_XY) {
         D = gram_at<COMPACT>(G, ii, ii) + gram_at<COMPACT>(G, 64 + jj, 64 + jj) - 2.0 * gram_at<COMPACT>(G, ii, 64 + jj);
     } else {  // GRAM_SAME: row i of x is stack row i (rows 64.. come from src2 = x + 64 rows)
         const double g_ii = gram_at<COMPACT>(G, ii, ii), g_jj = gram_at<COMPACT>(G, jj, jj), g_ij = gram_at<COMPACT>(G, ii, jj);
         D = (ii == jj) ? 0.0 : g_ii + g_jj - 2.0 * g_ij;
     }
-    if (D < 0.0) D = 0.0;   // a squared distance; rounding of the Gram terms may leave -tiny
+    D = gram_clamp0(D);
     float c = (float)D * f.sc;
     if (f.out_t) {
         // mirror block of an x == y problem (blocked path): blockIdx.z == 0 is the block itself with the (h, M) term,
@@ -729,11 +725,12 @@ static unsigned gram_mask(int mode, int n1, int n2) {
     return m;
 }
 
-void gram_sums_span(int B, int64_t K, size_t* off, size_t* n) {
-    const GramPlan pl = plan_gram(K);
-    *off = pl.gpart_bytes;
+// whether the loss's (B, K) takes this path (pointer alignment aside: gram_preferred), and where the fp64 sums then sit in
+// the workspace
+GramSplit gram_stack64_split(int B, int64_t K) {
+    if (B > 64 || K % 4 != 0 || K < 256) return GramSplit{};
     // more than 32 rows per operand: all ten sub-tiles, and on the bf16 pipe the compact record (run_gram)
-    *n = (B > 32 && gram_use_x3()) ? GRAM_CPT : GRAM_ELEMS;
+    return GramSplit{GRAM_PATH_STACK64, plan_gram(K).gpart_bytes, (size_t)((B > 32 && gram_use_x3()) ? GRAM_CPT : GRAM_ELEMS)};
 }
 
 // stage 0: everything; 1: stop after the fp64 Gram sums and the causal sums are in the workspace; 2: finalize only
@@ -792,16 +789,19 @@ int run_gram(const CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J,
     int split_mode = (ga.mask == 0x3FFu) ? GRAM_SPLIT_89 : GRAM_SPLIT_NONE;
     const bool compact = ga.mask == 0x3FFu && gram_use_x3();   // gram128_partial_x3ws writes compact records
     gf.compact = compact ? 1 : 0;
+    gf.gsum = gsum; gf.caus = cp.caus; gf.mode = mode; gf.sc = sc; gf.T = T; gf.J = J;
+    auto finalize = [&]() {
+        hipLaunchKernelGGL(gram_finalize, dim3((gf.B2 + CAUSAL_TILE - 1) / CAUSAL_TILE, (gf.B1 + CAUSAL_TILE - 1) / CAUSAL_TILE, nout),
+                           dim3(256), 0, st, gf);
+        return launch_status("gram_finalize");
+    };
     if (stage == 2) {
         if (ncausal > 0) {
             hipLaunchKernelGGL(causal_pre_only, dim3(ncausal), dim3(256), 0, st, cp);
             const int rcc = launch_status("causal_pre_only");
             if (rcc) return rcc;
         }
-        gf.gsum = gsum; gf.caus = cp.caus; gf.mode = mode; gf.sc = sc; gf.T = T; gf.J = J;
-        hipLaunchKernelGGL(gram_finalize, dim3((gf.B2 + CAUSAL_TILE - 1) / CAUSAL_TILE, (gf.B1 + CAUSAL_TILE - 1) / CAUSAL_TILE, nout),
-                           dim3(256), 0, st, gf);
-        return launch_status("gram_finalize");
+        return finalize();
     }
     if (compact) {
         // 16 spare workgroups (one per CU the 240-way K-split leaves idle) take the causal tiles
@@ -823,10 +823,7 @@ int run_gram(const CostBatch& cb, bool loss3, int64_t K, float sc, int T, int J,
                            (const float*)ga.gpart, pl.nchunk, ga.mask, split_mode, gsum, cp);
     rc = launch_status("gram_reduce");
     if (rc || stage == 1) return rc;
-    gf.gsum = gsum; gf.caus = cp.caus; gf.mode = mode; gf.sc = sc; gf.T = T; gf.J = J;
-    hipLaunchKernelGGL(gram_finalize, dim3((gf.B2 + CAUSAL_TILE - 1) / CAUSAL_TILE, (gf.B1 + CAUSAL_TILE - 1) / CAUSAL_TILE, nout),
-                       dim3(256), 0, st, gf);
-    return launch_status("gram_finalize");
+    return finalize();
 }
 
 }  // namespace kccot

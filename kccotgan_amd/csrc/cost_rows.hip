@@ -22,6 +22,7 @@
 //   row_norms                       g_ii, e_ii, x_ii of a range of rows in fp64
 #include "common.h"
 #include "cost_internal.h"
+#include "gram_tail.h"
 #include "options.h"
 #include "gram_q.h"
 
@@ -190,22 +191,12 @@ __global__ __launch_bounds__(256) void rows_gram(RowsArgs a) {
     }
 }
 
-// fp64 sum over the chunks, fixed order; eight loads in flight.  grid (elems / 256, panels).  accumulate != 0: added to what
+// fp64 sum over the chunks (gram_chunk_sum).  grid (elems / 256, panels).  accumulate != 0: added to what
 // gsum holds (a caller that feeds the columns in several calls, kccot_pairwise_cost3_rows_gram_sums_f64).
 __global__ __launch_bounds__(256) void rows_gram_reduce(const float* __restrict__ part, int nstride, int nchunk, int elems,
                                                         double* __restrict__ gsum, int accumulate) {
     const int e = blockIdx.x * 256 + threadIdx.x;
-    const float* p = part + (int64_t)blockIdx.y * nstride * elems + e;
-    double s = 0.0;
-    int c = 0;
-    for (; c + 8 <= nchunk; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = p[(int64_t)(c + i) * elems];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += (double)v[i];
-    }
-    for (; c < nchunk; ++c) s += (double)p[(int64_t)c * elems];
+    const double s = gram_chunk_sum(part + (int64_t)blockIdx.y * nstride * elems + e, elems, nchunk);
     double* g = gsum + (int64_t)blockIdx.y * elems + e;
     *g = accumulate ? *g + s : s;
 }
@@ -221,8 +212,8 @@ struct RowsFin {
     int T, J;
 };
 
-// One 16 x 16 output tile per block; blockIdx.z = problem (xy, xx, yy).  The formulas of gram_finalize (cost_mfma.hip) with
-// the diagonal Gram entries taken from `norms`.
+// One 16 x 16 output tile per block; blockIdx.z = problem (xy, xx, yy).  The distances of gram_tail.h with the diagonal Gram
+// entries taken from `norms`.
 __global__ __launch_bounds__(256) void rows_gram_finalize(RowsFin f) {
     __shared__ __attribute__((aligned(16))) float sh[CAUSAL_TILE * CAUSAL_PITCH];
     __shared__ __attribute__((aligned(16))) float sm[CAUSAL_TILE * CAUSAL_PITCH];
@@ -238,12 +229,7 @@ __global__ __launch_bounds__(256) void rows_gram_finalize(RowsFin f) {
     const double g_ij = G(i, j), e_ij = G(m + i, B + j);
     const double x_ij = diag ? x_jj : G(i, B + j);            // x_i . e_j (the diagonal one exactly the norm pass's)
     const double x_ji = diag ? x_jj : G(m + i, j);            // e_i . x_j
-    const double dxx = diag ? 0.0 : g_ii + g_jj - 2.0 * g_ij;
-    const double dxy = dxx + e_jj - 2.0 * (x_ij - x_jj);
-    const double dee = e_ii + e_jj - 2.0 * e_ij;
-    const double dyy = diag ? 0.0 : dxx + dee + 2.0 * (x_ii - x_ij - x_ji + x_jj);
-    double D = (p == 1) ? dxx : (p == 0 ? dxy : dyy);
-    if (D < 0.0) D = 0.0;
+    const double D = gram_loss_distance(p, diag, g_ii, g_jj, g_ij, e_ii, e_jj, e_ij, x_ii, x_jj, x_ij, x_ji);
     float c = (float)D * f.sc;
     if (f.h[p]) c += causal_tile16(f.h[p], f.M[p], i0, j0, m, B, f.T, f.J, sh, sm) * f.sc;
     f.out[p][(int64_t)i * B + j] = c;

@@ -23,10 +23,11 @@
 //   gram_q256<EPAIR>  pairs (X_i, E_i), writes E             partial tiles [pair][chunk][256][256] fp32
 //   gram_q256<DIAG>   pairs (p, p): one panel staged
 //   gram_q256<OFF>    every other pair (pa < pb)
-//   gram_q256_reduce  fp64 sum over the chunks (fixed order)
-//   gram_q256_finalize  distances from the Gram entries in fp64 (the formulas of gram_finalize), scale, causal term
+//   gram_stack_reduce<Tile256>    fp64 sum over the chunks (fixed order)                              } gram_tail.h, shared
+//   gram_stack_finalize<Tile256>  distances from the Gram entries in fp64, scale, causal term         } with cost_tiled.hip
 #include "common.h"
 #include "cost_internal.h"
+#include "gram_tail.h"
 #include "options.h"
 #include "gram_q.h"
 
@@ -147,7 +148,7 @@ __device__ __forceinline__ void q256_body(const Q256Args& a, int pa, int pb, int
     //     wave 0: rows {0,1} x cols {0..3} (its (1,0) is redundant) + (2,2), (2,3)      wave 2: rows {0,1} x cols {4..7} + (3,3)
     //     wave 1: rows {4,5} x cols {4..7} (its (5,4) is redundant) + (6,6), (6,7)      wave 3: rows {2,3} x cols {4..7} + (7,7)
     // (waves 2 and 3 run their extra tile twice instead of branching; the copy is not stored).  The tiles below the
-    // diagonal are never written: gram_q256_reduce zeroes them, q256_gram reads (min, max).
+    // diagonal are never written: gram_stack_reduce zeroes them (Tile256::never_computed), Tile256::gram reads (min, max).
     constexpr int NT = SAME ? 10 : 16;
     const int wr = wave >> 1, wc = wave & 1;
     const int lo = (lane & 31) * QROWB + 16 * (lane >> 5);                   // row (lane & 31), k half (lane >> 5) of the step
@@ -301,76 +302,26 @@ __global__ __launch_bounds__(256) void gram_q256(Q256Args a) {
                                                              __builtin_amdgcn_readfirstlane(chunk_id), zs0, zs1);
 }
 
-// fp64 sum over the chunks, fixed order; eight loads in flight
-__global__ __launch_bounds__(256) void gram_q256_reduce(const float* __restrict__ part, int nstride, int nchunk, int nt,
-                                                        double* __restrict__ gsum) {
-    const int qs = blockIdx.y;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    {   // the tiles below the diagonal of a diagonal pair are never computed (gram_q256<DIAG>): their sums are defined as 0
+// Where the sums of a pair's 256 x 256 tile sit (gram_tail.h: gram_stack_reduce, gram_stack_finalize)
+struct Tile256 {
+    static constexpr int ELEMS = QELEMS;
+    // Gram entry of stack rows (a, b)
+    static __device__ __forceinline__ double gram(const double* __restrict__ gs, int nt, int a, int b) {
+        const bool sw = a > b;                                               // panel order, and row <= column inside a diagonal pair
+        const int a2 = sw ? b : a, b2 = sw ? a : b;
+        return gs[(int64_t)q256_pair_slot(nt, a2 >> 8, b2 >> 8) * QELEMS + (a2 & 255) * QP + (b2 & 255)];
+    }
+    // the 32 x 32 tiles below the diagonal of a diagonal pair are never computed (gram_q256<DIAG>): their sums are defined as 0
+    static __device__ __forceinline__ bool never_computed(int nt, int qs, int e) {
         int pa = 0, r = qs;
         while (r >= nt - pa) { r -= nt - pa; ++pa; }
-        if (r == 0 && ((e >> 8) >> 5) > ((e & 255) >> 5)) { gsum[(int64_t)qs * QELEMS + e] = 0.0; return; }
+        return r == 0 && ((e >> 8) >> 5) > ((e & 255) >> 5);
     }
-    const float* p = part + (int64_t)qs * nstride * QELEMS + e;
-    double s = 0.0;
-    int c = 0;
-    for (; c + 8 <= nchunk; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = p[(int64_t)(c + i) * QELEMS];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += (double)v[i];
-    }
-    for (; c < nchunk; ++c) s += (double)p[(int64_t)c * QELEMS];
-    gsum[(int64_t)qs * QELEMS + e] = s;
-}
-
-struct Q256Fin {
-    const double* gsum;
-    int B, nt;
-    float* out[3];
-    const float* h[3];
-    const float* M[3];
-    float sc;
-    int T, J;
 };
 
-// Gram entry of stack rows (a, b)
-__device__ __forceinline__ double q256_gram(const double* __restrict__ gs, int nt, int a, int b) {
-    const bool sw = a > b;                                                   // panel order, and row <= column inside a diagonal pair
-    const int a2 = sw ? b : a, b2 = sw ? a : b;
-    return gs[(int64_t)q256_pair_slot(nt, a2 >> 8, b2 >> 8) * QELEMS + (a2 & 255) * QP + (b2 & 255)];
-}
-
-// One 16 x 16 output tile per block; blockIdx.z = problem (xy, xx, yy).  Formulas of gram_finalize (cost_mfma.hip).
-__global__ __launch_bounds__(256) void gram_q256_finalize(Q256Fin f) {
-    __shared__ __attribute__((aligned(16))) float sh[CAUSAL_TILE * CAUSAL_PITCH];
-    __shared__ __attribute__((aligned(16))) float sm[CAUSAL_TILE * CAUSAL_PITCH];
-    const int p = blockIdx.z, B = f.B, nt = f.nt;
-    const int i0 = blockIdx.y * CAUSAL_TILE, j0 = blockIdx.x * CAUSAL_TILE;
-    const int i = i0 + (threadIdx.x >> 4), j = j0 + (threadIdx.x & 15);      // B % 16 == 0: always in range
-    const double* G = f.gsum;
-    const double g_ii = q256_gram(G, nt, i, i), g_jj = q256_gram(G, nt, j, j), g_ij = q256_gram(G, nt, i, j);
-    const double e_ii = q256_gram(G, nt, B + i, B + i), e_jj = q256_gram(G, nt, B + j, B + j), e_ij = q256_gram(G, nt, B + i, B + j);
-    const double x_ii = q256_gram(G, nt, i, B + i), x_jj = q256_gram(G, nt, j, B + j);
-    const double x_ij = q256_gram(G, nt, i, B + j), x_ji = q256_gram(G, nt, j, B + i);
-    const bool diag = i == j;
-    const double dxx = diag ? 0.0 : g_ii + g_jj - 2.0 * g_ij;
-    const double dxy = dxx + e_jj - 2.0 * (x_ij - x_jj);
-    const double dee = e_ii + e_jj - 2.0 * e_ij;
-    const double dyy = diag ? 0.0 : dxx + dee + 2.0 * (x_ii - x_ij - x_ji + x_jj);
-    double D = (p == 1) ? dxx : (p == 0 ? dxy : dyy);
-    if (D < 0.0) D = 0.0;   // a squared distance; rounding of the Gram terms may leave -tiny
-    float c = (float)D * f.sc;
-    if (f.h[p]) c += causal_tile16(f.h[p], f.M[p], i0, j0, B, B, f.T, f.J, sh, sm) * f.sc;
-    f.out[p][(int64_t)i * B + j] = c;
-}
-
 // ---- host side ---------------------------------------------------------------------------------------
-struct Q256Plan { int nx, nt, npairs, nchunk; int64_t chunk; size_t part_bytes, gsum_bytes, e_bytes, ws_bytes; };
-
-static Q256Plan plan_q256(int B, int64_t K) {
-    Q256Plan pl{};
+static StackPlan plan_q256(int B, int64_t K) {
+    StackPlan pl{};
     pl.nx = B / QP;                                                          // 0 for B == 128: one panel [X ; E]
     pl.nt = pl.nx ? 2 * pl.nx : 1;
     pl.npairs = pl.nt * (pl.nt + 1) / 2;
@@ -397,8 +348,8 @@ static Q256Plan plan_q256(int B, int64_t K) {
     pl.chunk = ((ngran + best - 1) / best) * QG;
     pl.part_bytes = align_up((size_t)pl.npairs * pl.nchunk * QELEMS * sizeof(float), 256);
     pl.gsum_bytes = align_up((size_t)pl.npairs * QELEMS * sizeof(double), 256);
-    pl.e_bytes = pl.nx ? align_up((size_t)B * K * sizeof(float), 256) : 0;    // the single-panel form never writes E
-    pl.ws_bytes = pl.part_bytes + pl.gsum_bytes + pl.e_bytes;
+    pl.extra_bytes = pl.nx ? align_up((size_t)B * K * sizeof(float), 256) : 0;    // the single-panel form never writes E
+    pl.ws_bytes = pl.part_bytes + pl.gsum_bytes + pl.extra_bytes;
     return pl;
 }
 
@@ -406,67 +357,38 @@ static bool q256_shape_ok(int B, int64_t K) {
     return (B == QP / 2 || (B >= QP && B % QP == 0)) && B <= 4096 && K % 4 == 0 && K >= 256 && K <= (1 << 22);   // K: 32-bit panel offsets
 }
 
-void gram_q256_sums_span(int B, int64_t K, size_t* off, size_t* n) {
-    const Q256Plan pl = plan_q256(B, K);
-    *off = pl.part_bytes;
-    *n = (size_t)pl.npairs * QELEMS;
-}
-
 size_t gram_q256_workspace_bytes(int B, int64_t K) { return q256_shape_ok(B, K) ? plan_q256(B, K).ws_bytes : 0; }
 
-bool gram_q256_applies(int B, int64_t K) {
-    return q256_shape_ok(B, K) && opt(OPT_COST_TILED) && opt(OPT_COST_TILE256) && !opt(OPT_GRAM_F32);
+// whether (B, K) takes this path under the current options, and where the fp64 sums then sit in the workspace
+GramSplit gram_q256_split(int B, int64_t K) {
+    if (!q256_shape_ok(B, K) || !opt(OPT_COST_TILED) || !opt(OPT_COST_TILE256) || opt(OPT_GRAM_F32)) return GramSplit{};
+    const StackPlan pl = plan_q256(B, K);
+    return GramSplit{GRAM_PATH_TILE256, pl.part_bytes, (size_t)pl.npairs * QELEMS};
 }
 
-bool gram_q256_eligible(const CostBatch& cb, int64_t K, bool loss3) {
-    if (!loss3 || cb.nprob != 3) return false;
-    const int B = cb.p[0].Bx;
-    if (cb.p[0].By != B || !gram_q256_applies(B, K)) return false;
-    return ((uintptr_t)cb.p[0].x % 16 == 0) && ((uintptr_t)cb.p[0].y % 16 == 0);
+template <int MODE>
+static void launch_q256(const Q256Args& qa, int np, bool ragged, hipStream_t st) {
+    const dim3 grid(np * qa.nchunk), block(256);
+    if (ragged) hipLaunchKernelGGL((gram_q256<MODE, true>), grid, block, 0, st, qa);
+    else hipLaunchKernelGGL((gram_q256<MODE, false>), grid, block, 0, st, qa);
 }
 
 int run_gram_q256(const CostBatch& cb, int64_t K, float sc, int T, int J, void* ws, size_t ws_bytes, hipStream_t st,
-                  int stage) {   // stage 0: everything; 1: stop after the fp64 sums; 2: finalize only
+                  int stage) {
     const int B = cb.p[0].Bx;
-    const Q256Plan pl = plan_q256(B, K);
-    if (!ws || ws_bytes < pl.ws_bytes)
-        return fail(KCCOT_EWORKSPACE, "pairwise_cost3(tile256): workspace %zu < required %zu", ws_bytes, pl.ws_bytes);
-    float* part = static_cast<float*>(ws);
-    double* gsum = reinterpret_cast<double*>(static_cast<char*>(ws) + pl.part_bytes);
-    float* e = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.part_bytes + pl.gsum_bytes);
-    int rc;
-    if (stage != 2) {
-        Q256Args qa{cb.p[0].x, cb.p[0].y, e, B, pl.nx, pl.nt, pl.nchunk, K, pl.chunk, part};
-        const bool ragged = K % QG != 0;
+    const StackPlan pl = plan_q256(B, K);
+    return run_gram_stack<Tile256>("tile256", pl, cb, K, sc, T, J, ws, ws_bytes, st, stage, [&](float* part, float* e) {
+        const Q256Args qa{cb.p[0].x, cb.p[0].y, e, B, pl.nx, pl.nt, pl.nchunk, K, pl.chunk, part};
+        static void (*const launch[4])(const Q256Args&, int, bool, hipStream_t) = {launch_q256<Q256_EPAIR>, launch_q256<Q256_DIAG>,
+                                                                                  launch_q256<Q256_OFF>, launch_q256<Q256_HALF>};
         for (int mode = 0; mode < 4; ++mode) {
             const int np = q256_mode_pairs(mode, pl.nx);
             if (np == 0) continue;
-            const dim3 grid(np * pl.nchunk), block(256);
-            if (mode == Q256_EPAIR) {
-                if (ragged) hipLaunchKernelGGL((gram_q256<Q256_EPAIR, true>), grid, block, 0, st, qa);
-                else hipLaunchKernelGGL((gram_q256<Q256_EPAIR, false>), grid, block, 0, st, qa);
-            } else if (mode == Q256_DIAG) {
-                if (ragged) hipLaunchKernelGGL((gram_q256<Q256_DIAG, true>), grid, block, 0, st, qa);
-                else hipLaunchKernelGGL((gram_q256<Q256_DIAG, false>), grid, block, 0, st, qa);
-            } else if (mode == Q256_HALF) {
-                if (ragged) hipLaunchKernelGGL((gram_q256<Q256_HALF, true>), grid, block, 0, st, qa);
-                else hipLaunchKernelGGL((gram_q256<Q256_HALF, false>), grid, block, 0, st, qa);
-            } else {
-                if (ragged) hipLaunchKernelGGL((gram_q256<Q256_OFF, true>), grid, block, 0, st, qa);
-                else hipLaunchKernelGGL((gram_q256<Q256_OFF, false>), grid, block, 0, st, qa);
-            }
-            if ((rc = launch_status("gram_q256"))) return rc;
+            launch[mode](qa, np, K % QG != 0, st);
+            if (int rc = launch_status("gram_q256")) return rc;
         }
-        const int nvalid = (int)((K + pl.chunk - 1) / pl.chunk);
-        hipLaunchKernelGGL(gram_q256_reduce, dim3(QELEMS / 256, pl.npairs), dim3(256), 0, st, (const float*)part, pl.nchunk, nvalid, pl.nt, gsum);
-        if ((rc = launch_status("gram_q256_reduce"))) return rc;
-        if (stage == 1) return 0;
-    }
-    Q256Fin f{};
-    f.gsum = gsum; f.B = B; f.nt = pl.nt; f.sc = sc; f.T = T; f.J = J;
-    for (int p = 0; p < 3; ++p) { f.out[p] = cb.p[p].out; f.h[p] = cb.p[p].h1; f.M[p] = cb.p[p].M1; }
-    hipLaunchKernelGGL(gram_q256_finalize, dim3(B / CAUSAL_TILE, B / CAUSAL_TILE, 3), dim3(256), 0, st, f);
-    return launch_status("gram_q256_finalize");
+        return 0;
+    });
 }
 
 }  // namespace kccot

@@ -12,11 +12,11 @@
 // one pair is served from L2 / Infinity Cache to the other pairs that need it.
 //
 //   gram_tile_x3      partial tiles [pair][chunk][128][128] fp32
-//   gram_tile_reduce  fp64 sum over the chunks (fixed order)
-//   gram_tile_finalize  distances from the Gram entries in fp64 (the formulas of gram_finalize with global
-//                     indices), scale, causal term (causal_tile16)
+//   gram_stack_reduce<Tile128>    fp64 sum over the chunks (fixed order)                              } gram_tail.h, shared
+//   gram_stack_finalize<Tile128>  distances from the Gram entries in fp64, scale, causal term         } with cost_tile256.hip
 #include "common.h"
 #include "cost_internal.h"
+#include "gram_tail.h"
 #include "options.h"
 #include "bf16x3.h"
 
@@ -260,78 +260,28 @@ __global__ __launch_bounds__(512) void gram_tile_x3(TileArgs ta) {
     }
 }
 
-// fp64 sum over the chunks, fixed order; eight loads in flight
-__global__ __launch_bounds__(256) void gram_tile_reduce(const float* __restrict__ part, int nstride, int nchunk,
-                                                        double* __restrict__ gsum) {
-    // nstride: chunk slots per pair; nchunk: the non-empty ones
-    const int q = blockIdx.y;
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    const float* p = part + (int64_t)q * nstride * TELEMS + e;
-    double s = 0.0;
-    int c = 0;
-    for (; c + 8 <= nchunk; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = p[(int64_t)(c + i) * TELEMS];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s += (double)v[i];
+// Where the sums of a pair's 128 x 128 tile sit (gram_tail.h: gram_stack_reduce, gram_stack_finalize): pairs row-major over the
+// upper triangle of panels, every entry of a tile computed (diagonal pairs compute their lower triangle too)
+struct Tile128 {
+    static constexpr int ELEMS = TELEMS;
+    // Gram entry of stack rows (a, b)
+    static __device__ __forceinline__ double gram(const double* __restrict__ gs, int nt, int a, int b) {
+        const bool sw = (a >> 7) > (b >> 7);
+        const int a2 = sw ? b : a, b2 = sw ? a : b;
+        const int pa = a2 >> 7, pb = b2 >> 7;
+        const int q = pa * nt - (pa * (pa - 1)) / 2 + (pb - pa);
+        return gs[(int64_t)q * TELEMS + (a2 & 127) * TP + (b2 & 127)];
     }
-    for (; c < nchunk; ++c) s += (double)p[(int64_t)c * TELEMS];
-    gsum[(int64_t)q * TELEMS + e] = s;
-}
-
-struct TileFin {
-    const double* gsum;
-    int B, nt;
-    float* out[3];
-    const float* h[3];
-    const float* M[3];
-    float sc;
-    int T, J;
+    static __device__ __forceinline__ bool never_computed(int, int, int) { return false; }
 };
 
-// Gram entry of stack rows (a, b)
-__device__ __forceinline__ double tgram(const double* __restrict__ gs, int nt, int a, int b) {
-    const bool sw = (a >> 7) > (b >> 7);
-    const int a2 = sw ? b : a, b2 = sw ? a : b;
-    const int pa = a2 >> 7, pb = b2 >> 7;
-    const int q = pa * nt - (pa * (pa - 1)) / 2 + (pb - pa);
-    return gs[(int64_t)q * TELEMS + (a2 & 127) * TP + (b2 & 127)];
-}
-
-// One 16 x 16 output tile per block; blockIdx.z = problem (xy, xx, yy).  Formulas of gram_finalize (cost_mfma.hip).
-__global__ __launch_bounds__(256) void gram_tile_finalize(TileFin f) {
-    __shared__ __attribute__((aligned(16))) float sh[CAUSAL_TILE * CAUSAL_PITCH];
-    __shared__ __attribute__((aligned(16))) float sm[CAUSAL_TILE * CAUSAL_PITCH];
-    const int p = blockIdx.z, B = f.B, nt = f.nt;
-    const int i0 = blockIdx.y * CAUSAL_TILE, j0 = blockIdx.x * CAUSAL_TILE;
-    const int i = i0 + (threadIdx.x >> 4), j = j0 + (threadIdx.x & 15);      // B % 16 == 0: always in range
-    const double* G = f.gsum;
-    const double g_ii = tgram(G, nt, i, i), g_jj = tgram(G, nt, j, j), g_ij = tgram(G, nt, i, j);
-    const double e_ii = tgram(G, nt, B + i, B + i), e_jj = tgram(G, nt, B + j, B + j), e_ij = tgram(G, nt, B + i, B + j);
-    const double x_ii = tgram(G, nt, i, B + i), x_jj = tgram(G, nt, j, B + j);
-    const double x_ij = tgram(G, nt, i, B + j), x_ji = tgram(G, nt, j, B + i);
-    const bool diag = i == j;
-    const double dxx = diag ? 0.0 : g_ii + g_jj - 2.0 * g_ij;
-    const double dxy = dxx + e_jj - 2.0 * (x_ij - x_jj);
-    const double dee = e_ii + e_jj - 2.0 * e_ij;
-    const double dyy = diag ? 0.0 : dxx + dee + 2.0 * (x_ii - x_ij - x_ji + x_jj);
-    double D = (p == 1) ? dxx : (p == 0 ? dxy : dyy);
-    if (D < 0.0) D = 0.0;   // a squared distance; rounding of the Gram terms may leave -tiny
-    float c = (float)D * f.sc;
-    if (f.h[p]) c += causal_tile16(f.h[p], f.M[p], i0, j0, B, B, f.T, f.J, sh, sm) * f.sc;
-    f.out[p][(int64_t)i * B + j] = c;
-}
-
 // ---- host side ---------------------------------------------------------------------------------------
-struct TilePlan { int nt, npairs, nchunk; int64_t chunk; size_t part_bytes, gsum_bytes, ediff_bytes, ws_bytes; };
-
 // E = fake - real materialised once for B >= 512.  Measured cost stage, the extra pass included (profiles/r03ac_ab_ediff.txt):
 // B = 512 (K = 2.36 M) 22.6 -> 21.1-21.3 ms for 4.8 GB more workspace; B = 384 equal; B = 256 SLOWER (1.12 vs 1.04 ms).
 static bool tiled_ediff(int B) { return B >= 512; }
 
-static TilePlan plan_tiled(int B, int64_t K) {
-    TilePlan pl{};
+static StackPlan plan_tiled(int B, int64_t K) {
+    StackPlan pl{};
     pl.nt = 2 * B / TP;
     pl.npairs = pl.nt * (pl.nt + 1) / 2;
     const int64_t ksteps = (K + TK - 1) / TK;
@@ -359,61 +309,38 @@ static TilePlan plan_tiled(int B, int64_t K) {
     pl.nchunk = (int)nchunk;                                  // trailing chunks may be empty (kbeg >= K): they return at once
     pl.part_bytes = align_up((size_t)pl.npairs * pl.nchunk * TELEMS * sizeof(float), 256);
     pl.gsum_bytes = align_up((size_t)pl.npairs * TELEMS * sizeof(double), 256);
-    pl.ediff_bytes = tiled_ediff(B) ? align_up((size_t)B * K * sizeof(float), 256) : 0;
-    pl.ws_bytes = pl.part_bytes + pl.gsum_bytes + pl.ediff_bytes;
+    pl.extra_bytes = tiled_ediff(B) ? align_up((size_t)B * K * sizeof(float), 256) : 0;
+    pl.ws_bytes = pl.part_bytes + pl.gsum_bytes + pl.extra_bytes;
     return pl;
 }
 
-// where the fp64 sums sit in the workspace (the all-reducing caller's view)
-void gram_tiled_sums_span(int B, int64_t K, size_t* off, size_t* n) {
-    const TilePlan pl = plan_tiled(B, K);
-    *off = pl.part_bytes;
-    *n = (size_t)pl.npairs * TELEMS;
-}
+static bool tiled_shape_ok(int B) { return B >= TP && B % TP == 0 && B <= 4096; }
 
-size_t gram_tiled_workspace_bytes(int B, int64_t K) {
-    if (B < TP || B % TP != 0 || B > 4096) return 0;
-    return plan_tiled(B, K).ws_bytes;
-}
+size_t gram_tiled_workspace_bytes(int B, int64_t K) { return tiled_shape_ok(B) ? plan_tiled(B, K).ws_bytes : 0; }
 
-bool gram_tiled_eligible(const CostBatch& cb, int64_t K, bool loss3) {
-    if (!loss3 || cb.nprob != 3 || !opt(OPT_COST_TILED)) return false;
-    if (opt(OPT_GRAM_F32)) return false;                      // the f32-input MFMA request keeps the other paths
-    const int B = cb.p[0].Bx;
-    if (B < TP || B % TP != 0 || B > 4096 || cb.p[0].By != B || K % 4 != 0 || K < 256) return false;
-    return ((uintptr_t)cb.p[0].x % 16 == 0) && ((uintptr_t)cb.p[0].y % 16 == 0);
+// whether (B, K) takes this path under the current options (the f32-input MFMA request keeps the other paths), and where the
+// fp64 sums then sit in the workspace (the all-reducing caller's view)
+GramSplit gram_tiled_split(int B, int64_t K) {
+    if (!tiled_shape_ok(B) || K % 4 != 0 || K < 256 || !opt(OPT_COST_TILED) || opt(OPT_GRAM_F32)) return GramSplit{};
+    const StackPlan pl = plan_tiled(B, K);
+    return GramSplit{GRAM_PATH_TILE128, pl.part_bytes, (size_t)pl.npairs * TELEMS};
 }
 
 int run_gram_tiled(const CostBatch& cb, int64_t K, float sc, int T, int J, void* ws, size_t ws_bytes, hipStream_t st,
-                   int stage) {   // stage 0: everything; 1: stop after the fp64 sums; 2: finalize only
+                   int stage) {
     const int B = cb.p[0].Bx;
-    const TilePlan pl = plan_tiled(B, K);
-    if (!ws || ws_bytes < pl.ws_bytes)
-        return fail(KCCOT_EWORKSPACE, "pairwise_cost3(tiled): workspace %zu < required %zu", ws_bytes, pl.ws_bytes);
-    if (pl.nchunk > 65535) return fail(KCCOT_EUNSUPPORTED, "pairwise_cost3(tiled): %d chunks", pl.nchunk);
-    float* part = static_cast<float*>(ws);
-    double* gsum = reinterpret_cast<double*>(static_cast<char*>(ws) + pl.part_bytes);
-    int rc;
-    if (stage != 2) {
+    const StackPlan pl = plan_tiled(B, K);
+    return run_gram_stack<Tile128>("tiled", pl, cb, K, sc, T, J, ws, ws_bytes, st, stage, [&](float* part, float* e) {
+        if (pl.nchunk > 65535) return fail(KCCOT_EUNSUPPORTED, "pairwise_cost3(tiled): %d chunks", pl.nchunk);
         TileArgs ta{cb.p[0].x, cb.p[0].y, B, pl.nt, pl.nchunk, K, pl.chunk, part, nullptr};
-        if (pl.ediff_bytes) {
-            float* e = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.part_bytes + pl.gsum_bytes);
+        if (pl.extra_bytes) {
             hipLaunchKernelGGL(ediff_rows, dim3(2048), dim3(256), 0, st, cb.p[0].x, cb.p[0].y, (int64_t)B * K / 4, e);
-            if ((rc = launch_status("ediff_rows"))) return rc;
+            if (int rc = launch_status("ediff_rows")) return rc;
             ta.ediff = e;
         }
         hipLaunchKernelGGL(gram_tile_x3, dim3(pl.npairs * pl.nchunk), dim3(512), 0, st, ta);
-        if ((rc = launch_status("gram_tile_x3"))) return rc;
-        const int nvalid = (int)((K + pl.chunk - 1) / pl.chunk);
-        hipLaunchKernelGGL(gram_tile_reduce, dim3(TELEMS / 256, pl.npairs), dim3(256), 0, st, (const float*)part, pl.nchunk, nvalid, gsum);
-        if ((rc = launch_status("gram_tile_reduce"))) return rc;
-        if (stage == 1) return 0;
-    }
-    TileFin f{};
-    f.gsum = gsum; f.B = B; f.nt = pl.nt; f.sc = sc; f.T = T; f.J = J;
-    for (int p = 0; p < 3; ++p) { f.out[p] = cb.p[p].out; f.h[p] = cb.p[p].h1; f.M[p] = cb.p[p].M1; }
-    hipLaunchKernelGGL(gram_tile_finalize, dim3(B / CAUSAL_TILE, B / CAUSAL_TILE, 3), dim3(256), 0, st, f);
-    return launch_status("gram_tile_finalize");
+        return launch_status("gram_tile_x3");
+    });
 }
 
 }  // namespace kccot
