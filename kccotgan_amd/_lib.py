@@ -1,7 +1,7 @@
 """ctypes binding of the C-ABI library ``csrc/libkccot.so`` (declared in ``include/kccot.h``, ``include/kccot_models.h``,
 ``include/kccot_weighted.h``, ``include/kccot_conditional.h``, ``include/kccot_weight_grad.h``,
 ``include/kccot_smooth_causal3.h``, ``include/kccot_smooth_sigma.h``, ``include/kccot_smooth_aniso.h``,
-``include/kccot_metrics.h`` and ``include/kccot_l1.h``).
+``include/kccot_metrics.h``, ``include/kccot_l1.h`` and ``include/kccot_swd.h``).
 
 The HIP library is the product: there is NO CPU fallback anywhere in this package.  If the
 shared object is missing or a call is made without a GPU tensor the import / call fails loudly.
@@ -31,6 +31,7 @@ SMOOTH_CAUSAL_T = 8       # one-sided (past-only) T stencil; with SMOOTH_T alone
 _c = ctypes
 _fp = _c.c_void_p      # device pointers travel as plain addresses
 _i, _i64, _f, _u, _sz = _c.c_int, _c.c_int64, _c.c_float, _c.c_uint, _c.c_size_t
+_u64 = _c.c_uint64
 
 # name -> (restype, argtypes); mirrors include/kccot.h one to one
 SIGNATURES = {
@@ -220,6 +221,17 @@ L1_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/kccot_swd.h one to one (the sliced Wasserstein distance between two batches on
+# directions generated on chip, and its adjoint: an extension outside the versioned surface of kccot.h)
+SWD_SIGNATURES = {
+    "kccot_swd_workspace_bytes": (_sz, [_i, _i64, _i]),
+    "kccot_swd_fwd_f32": (_i, [_fp, _fp, _i, _i64, _i, _u64, _fp, _fp, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_swd_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i64, _i, _u64, _fp, _fp, _fp, _sz, _fp]),
+    "kccot_swd_directions_f32": (_i, [_u64, _i64, _i, _i, _fp, _fp]),
+    "kccot_swd_plan": (_i, [_i, _i64, _i, _fp]),      # host only; out: SWD_PLAN_INTS ints
+}
+
+
 class KccotError(RuntimeError):
     pass
 
@@ -227,6 +239,8 @@ class KccotError(RuntimeError):
 # ---- the host-only plan queries: which tiling, and which instantiation of the tile kernel, a launch would use (no device
 # call: they work without a GPU).  The field names are those of the headers.
 DSIGMA_PLAN_INTS, ANISO_PLAN_INTS, SSIM_PLAN_INTS = 17, 13, 8
+SWD_PLAN_INTS = 8
+_SWD_PLAN = ("kc", "chunks", "pt", "rt", "npt", "nrt", "np", "kt")
 _DSIGMA_PLAN = ("launches", "R", "NI", "tt", "wt", "ct", "hs", "ntt", "ntw", "ntc", "nseg", "grid", "Bv", "Hv", "Tv", "Wv", "Cv")
 _ANISO_PLAN = ("launches", "RS", "NI", "job", "tt", "wt", "ct", "hs", "ntt", "ntw", "ntc", "nseg", "grid")
 _SSIM_PLAN = ("wt", "ct", "hs", "nt", "ntw", "ntc", "nseg", "grid")
@@ -255,6 +269,11 @@ def ssim_plan(shape, radius, backward):
     return _plan(lib.kccot_ssim_plan, _SSIM_PLAN, "ssim_plan", *shape, radius, int(bool(backward)))
 
 
+def swd_plan(B, K, P):
+    """kccot_swd_plan as a dict (include/kccot_swd.h)"""
+    return _plan(lib.kccot_swd_plan, _SWD_PLAN, "swd_plan", B, K, P)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -265,7 +284,7 @@ def _load():
                               list(CONDITIONAL_SIGNATURES.items()) + list(WEIGHT_GRAD_SIGNATURES.items()) +
                               list(SMOOTH3C_SIGNATURES.items()) + list(SMOOTH_SIGMA_SIGNATURES.items()) +
                               list(SMOOTH_ANISO_SIGNATURES.items()) + list(METRICS_SIGNATURES.items()) +
-                              list(L1_SIGNATURES.items())):
+                              list(L1_SIGNATURES.items()) + list(SWD_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError here = headers and library out of step
         fn.restype = res
         fn.argtypes = args

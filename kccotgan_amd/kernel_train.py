@@ -362,6 +362,29 @@ class KCCOTTrainer:
         return _mmd.rbf_mmd2(real, fake)
 
     @torch.no_grad()
+    def swd(self, real_data, sigma=None, n_projections=128, seed=0):
+        """Monitor, not part of the reference's loop: the squared sliced Wasserstein distance (``swd.sliced_wasserstein2``,
+        ``n_projections`` directions drawn from ``seed``) between a [B,H,T,W,C] batch and what the generator makes of its
+        context frames, generated as ``_forward`` does (fresh z, training-mode networks) and, when ``sigma`` is given, smoothed
+        as there.  It depends on no discriminator, epsilon or bandwidth, so with one ``seed`` it compares across runs.
+        Data-parallel runs: THIS rank's batch only, nothing is all-reduced (as ``evaluate``).  No gradient, no optimiser step;
+        the BatchNorm running statistics are put back.  It draws z from the torch RNG."""
+        from . import swd as _swd
+        real_data = real_data.to(self.device, torch.float32)
+        real_in = real_data[:, :, :self.int_time_steps]
+        nets = (self.context_encoder, self.decoder)
+        buffers = [(b, b.clone()) for net in nets for b in net.buffers()]
+        with gan.conv_guard():
+            hidden_z = torch.randn(self.z_shape, device=self.device)
+            fake_pred = self.decoder(self.context_encoder(real_data), hidden_z)
+            real, fake = real_data, torch.cat((real_in, fake_pred), dim=2)
+            if sigma is not None:
+                real, fake = self._smooth(real, sigma), self._smooth(fake, sigma)
+        for b, saved in buffers:
+            b.copy_(saved)
+        return _swd.sliced_wasserstein2(real, fake, n_projections, seed)
+
+    @torch.no_grad()
     def evaluate(self, test_data, data_range=1.0, win_size=11, ssim_sigma=1.5):
         """Sample quality, not part of the reference's loop (it publishes no such figure): ``sample(test_data)``, then
         ``metrics.frame_metrics`` of the ``pred_time_steps`` predicted frames against the same frames of ``test_data``
